@@ -13,9 +13,18 @@ A "step" is one whole fit of the hot path with the raw field resident in HBM:
 On one GPU that is ONE engine call (eofx_fit_f32): the statistics ride on the first pass, the field is read 16 times.
 value = algorithmic SVD bytes (16 * n * p * 4 B, the reference's 16 GEMM passes) / step time.
 
-One JSON line on rank 0; see the task contract for the fields.  Extra objects:
+One JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (wall time of one timed step: --steps
+steps after --warmup untimed ones), the workload's config and the phase split of the timed steps.
   roofline      the streaming kernels (atb_f16_kernel / atb_f16_fit_kernel for X^T Z, axb_f16_dma_kernel for X Y):
-                algorithmic bytes per launch (n p_local 4 B) / mean launch duration from HIP events on the launch stream.
+                algorithmic bytes per launch (n p_local 4 B) / mean launch duration from HIP events on the launch stream
+                of the timed steps; `traffic` is quoted from the committed profile unless --full re-counts it.
+  comm          (N > 1) the collectives of one timed fit: count, bytes, milliseconds between events around them.
+--dump-outputs DIR writes what the last timed step returned (U, s, V, the total variance; --config 3 / 5: the fit's
+factors and spectrum) as DIR/<name>.npy; the inputs are fixed by the arguments (seeded synthetic fields).
+
+A plain run does only that.  --full adds everything else, after the timed region:
+  comm probe    (N > 1) the engine communicator's rank count and per-collective latency, before the timed region.
+  roofline      `traffic` re-counted with rocprofv3 PMC passes over this command.
   cpu_baseline  the oracle's sklearn-restated randomized_svd (oracle/, "port") timed on the host cores on a
                 bounded sample (the workload itself where the host holds it, else its n and k on half of its grid, fp32); "f64": the same kernel in
                 float64 and the whole oracle fit on the config-2 shape (what xeofs itself computes in).
@@ -25,8 +34,9 @@ One JSON line on rank 0; see the task contract for the fields.  Extra objects:
                 model level, config 2, config 3 (MCA with the total squared covariance), config 5 (Hilbert + complex
                 rSVD), and the reference's own published workload (docs/perf/xeofs_timings.py:18-57) with its ratio to
                 the published 39.5 s (`configs.published.speedup`; `vs_baseline` is null: no published number
-                exists for the headline metric itself).
-  comm          (N > 1) the collectives of one fit: count, bytes, milliseconds between events around them.
+                exists for the headline metric itself); `model_level` and `f64_mode` legs of the headline workload.
+  configs_sharded  (N > 1) configs 3 and 5 on the same ranks through the engine's sharded entries.
+The --config 3 / 5 lines are unchanged by --full.
 """
 
 from __future__ import annotations
@@ -132,6 +142,72 @@ def timed(fn, reps=3):
         _sync()
         ts.append(1e3 * (time.perf_counter() - t0))
     return min(ts), float(np.mean(ts)), out
+
+
+# ------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path returned in its last step, so that two builds can be compared output for output
+# ------------------------------------------------------------------------------------------------------------
+DUMP_MAX_ROWS = 65536
+DUMP_MAX_BYTES = 64 << 20
+
+
+def sample_rows(total, row_bytes, budget):
+    """the rows of a `total`-row factor that are written: all of them when they fit `budget` bytes (and DUMP_MAX_ROWS),
+    else a fixed, seeded sample (sorted), the same for every run, build and rank count"""
+    cap = max(1, min(DUMP_MAX_ROWS, budget // max(row_bytes, 1)))
+    if total <= cap:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(12345).choice(total, cap, replace=False)).astype(np.int64)
+
+
+def gather_rows(A, lo, rows, world, device):
+    """rows `rows` (global indices) of a factor whose local block on this rank starts at global row `lo`, summed over the
+    ranks (every rank must call) -> host array; complex factors come back with a trailing (re, im) axis"""
+    import torch
+
+    A = torch.as_tensor(A, device=device)
+    if A.is_complex():
+        A = torch.view_as_real(A)
+    r = torch.as_tensor(rows, dtype=torch.int64, device=device)
+    mine = (r >= lo) & (r < lo + A.shape[0])
+    out = torch.zeros((len(rows),) + tuple(A.shape[1:]), dtype=A.dtype, device=device)
+    out[mine] = A[r[mine] - lo]
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.all_reduce(out)
+    return out.cpu().numpy()
+
+
+def factor_outputs(outs, name, A, lo, total, world, device, budget, itemsize=4):
+    """outs[name] = (a sample of) the rows of factor A (`total` rows over all ranks); outs[name + "_rows"] = the sampled
+    global row indices when it is a sample; complex factors as name_re / name_im"""
+    k = int(A.shape[1]) if len(A.shape) > 1 else 1
+    rows = sample_rows(total, itemsize * k, budget)
+    a = gather_rows(A, lo, rows, world, device)
+    if a.ndim == 3:
+        outs[name + "_re"], outs[name + "_im"] = a[..., 0], a[..., 1]
+    else:
+        outs[name] = a
+    if rows.size < total:
+        outs[name + "_rows"] = rows.astype(np.float64)
+
+
+def write_outputs(d, outs):
+    """DIR/<name>.npy for every array, float32 or float64 (integers as float64), at most DUMP_MAX_BYTES in all"""
+    arrs = {}
+    for name, a in outs.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) and a.dtype.itemsize < 4 else np.float64)
+        arrs[name] = np.ascontiguousarray(a)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} B > {DUMP_MAX_BYTES} B")
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    print(f"[bench] wrote {len(arrs)} arrays ({total / 2**20:.1f} MiB) to {d}", file=sys.stderr)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -666,13 +742,14 @@ def leg_model_level(device, quick=False):
     return out
 
 
-def leg_sharded_config(cfg, ctx, comm, device, world, rank, native, steps, warmup):
+def leg_sharded_config(cfg, ctx, comm, device, world, rank, native, steps, warmup, dump_dir=None):
     """BASELINE config 3 / config 5 as multi-GPU jobs (both are defined at 8 GPUs): every rank generates and keeps its slice of
     each field's feature axis; with the engine's communicator attached (`native`) a fit is engine calls only -- the global facts
     of the preprocess through eofx_ctx_comm_allreduce_f64, the decomposition through eofx_crosscov_rsvd_sharded_f32 (config 3)
     or eofx_rsvd_hilbert_sharded_c64 (config 5: the operator route, the imaginary part is never written) -- otherwise the
     panel-level python drivers with torch.distributed collectives between engine calls.  World size 1 without a communicator:
-    the single-GPU entries.  -> {"line": the JSON line of `bench.py --config cfg`, "gate": failed size-independent properties}"""
+    the single-GPU entries.  dump_dir: --dump-outputs of the last timed fit.
+    -> {"line": the JSON line of `bench.py --config cfg`, "gate": failed size-independent properties}"""
     import torch
     import torch.distributed as dist
 
@@ -764,6 +841,20 @@ def leg_sharded_config(cfg, ctx, comm, device, world, rank, native, steps, warmu
     barrier()
     dt = time.perf_counter() - t0
     cstats = engine.comm_stats(ctx) if native else None
+    if dump_dir:
+        if cfg == 3:    # components: this rank's rows of each field's feature axis; scores: replicated
+            outs = {"singular_values": np.asarray(res["singular_values"], dtype=np.float64),
+                    "total_squared_covariance": np.array([res["total_squared_covariance"]], dtype=np.float64)}
+            for j in (1, 2):
+                factor_outputs(outs, f"components{j}", res[f"components{j}"], lo1, Ph, world, device, 12 << 20)
+                factor_outputs(outs, f"scores{j}", res[f"scores{j}"], 0, n, 1, device, 12 << 20)
+        else:           # complex factors as _re / _im
+            outs = {"norms": np.asarray(res["norms"], dtype=np.float64),
+                    "total_variance": np.array([res["total_variance"]], dtype=np.float64)}
+            factor_outputs(outs, "components", res["components"], lo1, P, world, device, 24 << 20, itemsize=8)
+            factor_outputs(outs, "scores", res["scores"], 0, n, 1, device, 24 << 20, itemsize=8)
+        if rank == 0:
+            write_outputs(dump_dir, outs)
     tt = torch.tensor([dt], dtype=torch.float64, device=device)
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -887,13 +978,23 @@ def main():
                     help="4 (default): the headline, EOF k=50 on 10000x(720x1440).  3 / 5: the line is BASELINE config 3 (MCA k=20 on two "
                          "5000x(360x360) halves) / config 5 (Hilbert EOF k=20 on 8000x(720x1440)) on --gpus N ranks, each field sharded "
                          "along its feature axis, through the engine's own sharded entries (eofx_crosscov_rsvd_sharded_f32 / "
-                         "eofx_rsvd_hilbert_sharded_c64); a --gpus N run of the headline carries both as `configs_sharded` as well")
+                         "eofx_rsvd_hilbert_sharded_c64); a --full --gpus N run of the headline carries both as `configs_sharded` as well")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: parity checks of the timed fit, the roofline traffic re-count, the "
+                         "CPU baseline and float64 gates, the other BASELINE configs, the model-level and f64-mode legs, the "
+                         "communicator probe and (N > 1) `configs_sharded`.  The --no-* options trim this set.  Without --full a "
+                         "run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64; factors taller than a fixed budget as a fixed, seeded sample of their rows, the row "
+                         "indices beside them as <name>_rows.npy)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # Started without a launcher: become `torch.distributed.run` with one rank per GPU (the driver's own
-        # command line), same arguments.  Rank 0 of the child job prints the JSON line on this stdout.
+        # Started without a launcher: run `torch.distributed.run` with one rank per GPU (the driver's own command line),
+        # same arguments, as a child process.  Rank 0 of the child job prints the JSON line on this stdout.
         import socket
+        import subprocess
 
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
@@ -902,7 +1003,7 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execvpe(sys.executable, cmd, env)
+        sys.exit(subprocess.run(cmd, env=env).returncode)
 
     real_stdout = os.fdopen(os.dup(1), "w")
     os.dup2(2, 1)
@@ -945,7 +1046,7 @@ def main():
     # self-diagnosis of the engine's communicator, before anything is timed (RCCL has only ever run at world
     # size 1 here): the rank count it really reduces over and the cost of each collective of a sharded fit
     comm_probe = None
-    if native:
+    if native and (args.full or args.config != 4):
         n_pad_c, l_c = (n + 511) // 512 * 512, 64
         cases = [(n_pad_c * l_c, "f32"), (l_c * l_c, "f64"), (2 * l_c, "f32"), (1, "i32")]
         try:
@@ -958,7 +1059,8 @@ def main():
 
     if args.config != 4:
         # the line IS config 3 / config 5 on `world` ranks (engine-owned sharded entries when a communicator is attached)
-        leg = leg_sharded_config(args.config, ctx, comm, device, world, rank, native, args.steps, args.warmup)
+        leg = leg_sharded_config(args.config, ctx, comm, device, world, rank, native, args.steps, args.warmup,
+                                 dump_dir=args.dump_outputs)
         if rank == 0:
             leg["line"]["n_gpus"] = world
             leg["line"]["comm"] = dict(leg["line"].get("comm", {}), **(comm_probe or {}), world=world,
@@ -1085,30 +1187,41 @@ def main():
     dt = float(tt.item())
     ms_step = 1e3 * dt / args.steps
     mat, st, U, s, V = last
+    if args.dump_outputs:
+        # U[n, k] (replicated on every rank), s[k], V[P, k] (feature-sharded), the total variance of the Scaler's statistics
+        outs = {"s": np.asarray(s, dtype=np.float32)}
+        factor_outputs(outs, "U", U, 0, n, 1, device, 24 << 20)
+        factor_outputs(outs, "V", V, lo, P, world, device, 24 << 20)
+        if isinstance(st, dict) and st.get("total_variance") is not None:
+            outs["total_variance"] = np.array([st["total_variance"]], dtype=np.float64)
+        if rank == 0:
+            write_outputs(args.dump_outputs, outs)
 
     # ---- size-independent parity checks at full size: X V = U diag(s), orthonormal U ----------
-    Ud = U if torch.is_tensor(U) else torch.as_tensor(U, device=device)
-    Vd = V if torch.is_tensor(V) else torch.as_tensor(V, device=device)
-    sd = torch.as_tensor(np.asarray(s, dtype=np.float64), device=device)
-    XV = torch.as_tensor(engine.project(ctx, mat, Vd), device=device).double()
-    if world > 1:
-        dist.all_reduce(XV)
-    Us = Ud.double() * sd
-    relres = float((XV - Us).norm() / Us.norm())
-    orth_u = float((Ud.double().T @ Ud.double() - torch.eye(k, device=device, dtype=torch.float64)).abs().max())
-    vtv = Vd.double().T @ Vd.double()
-    if world > 1:
-        dist.all_reduce(vtv)
-    orth_v = float((vtv - torch.eye(k, device=device, dtype=torch.float64)).abs().max())
-    parity = {"XV_eq_Us_relerr": relres, "orth_U_maxabs": orth_u, "orth_V_maxabs": orth_v,
-              "s_head": [float(x) for x in np.asarray(s)[:3]]}
-    if one_call:   # the statistics of the fused pass against a plain float64 reduction of the field (device)
-        tv_ref = 0.0
-        for c0 in range(0, hi - lo, 65536):
-            blk = Xraw[:, c0:c0 + 65536].double()
-            tv_ref += float(blk.var(dim=0, unbiased=True).sum())
-            del blk
-        parity["total_variance_relerr_vs_f64"] = abs(st["total_variance"] - tv_ref) / tv_ref
+    parity = None
+    if args.full:
+        Ud = U if torch.is_tensor(U) else torch.as_tensor(U, device=device)
+        Vd = V if torch.is_tensor(V) else torch.as_tensor(V, device=device)
+        sd = torch.as_tensor(np.asarray(s, dtype=np.float64), device=device)
+        XV = torch.as_tensor(engine.project(ctx, mat, Vd), device=device).double()
+        if world > 1:
+            dist.all_reduce(XV)
+        Us = Ud.double() * sd
+        relres = float((XV - Us).norm() / Us.norm())
+        orth_u = float((Ud.double().T @ Ud.double() - torch.eye(k, device=device, dtype=torch.float64)).abs().max())
+        vtv = Vd.double().T @ Vd.double()
+        if world > 1:
+            dist.all_reduce(vtv)
+        orth_v = float((vtv - torch.eye(k, device=device, dtype=torch.float64)).abs().max())
+        parity = {"XV_eq_Us_relerr": relres, "orth_U_maxabs": orth_u, "orth_V_maxabs": orth_v,
+                  "s_head": [float(x) for x in np.asarray(s)[:3]]}
+        if one_call:   # the statistics of the fused pass against a plain float64 reduction of the field (device)
+            tv_ref = 0.0
+            for c0 in range(0, hi - lo, 65536):
+                blk = Xraw[:, c0:c0 + 65536].double()
+                tv_ref += float(blk.var(dim=0, unbiased=True).sum())
+                del blk
+            parity["total_variance_relerr_vs_f64"] = abs(st["total_variance"] - tv_ref) / tv_ref
 
     n_iter = sharded.rsvd_auto_iters(k, n, P)
     passes = 2 * n_iter + 2
@@ -1117,7 +1230,7 @@ def main():
     launch_ms = prof["ms"] / max(prof["launches"], 1)
     achieved_tflops = alg_flops_launch / (launch_ms * 1e-3) / 1e12 if launch_ms > 0 else 0.0
     pmc_traffic, traffic_src, traffic_by = None, None, None
-    if world == 1 and rank == 0 and not args.no_traffic and args.precision == "f16x3":
+    if args.full and world == 1 and rank == 0 and not args.no_traffic and args.precision == "f16x3":
         pmc_traffic, traffic_by, traffic_src = measure_traffic(args, n, P)
         if pmc_traffic is None:
             print(f"[bench] traffic not re-counted ({traffic_src}); quoting the committed profile", file=sys.stderr)
@@ -1193,7 +1306,7 @@ def main():
     cpu_baseline = None
     configs = None
     gate_failed = []
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import eof_oracle as orc   # checker / baseline only
 
         mat.free()
@@ -1310,7 +1423,7 @@ def main():
     # ---- the 8-GPU forms of configs 3 and 5 on the same ranks: every multi-rank run of the headline also
     #      times them through the engine's own sharded entries, so the first real --gpus 8 run measures the fast routes
     configs_sharded = None
-    if (world > 1 or args.force_sharded) and not args.no_configs:
+    if args.full and (world > 1 or args.force_sharded) and not args.no_configs:
         try:            # (a world-1 --force-sharded run has been through the CPU-baseline leg, which released these already)
             mat.free()
         except Exception:
@@ -1365,9 +1478,11 @@ def main():
             "phase_ms": {"preprocess": round(1e3 * phase["pre"] / args.steps, 3),
                          "svd": round(1e3 * phase["svd"] / args.steps, 3)},
             "svd_only_GBps": round(alg_bytes / (phase["svd"] / args.steps) / 1e9, 2),
-            "roofline": roofline, "cpu_baseline": cpu_baseline, "parity": parity,
+            "roofline": roofline, "cpu_baseline": cpu_baseline,
             "datagen_s": round(t_gen, 2),
         }
+        if parity is not None:
+            line["parity"] = parity
         if configs is not None:
             line["configs"] = configs
         if configs_sharded is not None:

@@ -165,7 +165,8 @@ def test_two_rank_sharded_path_on_one_gpu(ctx):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     common = ["--steps", "1", "--warmup", "1", "--nlat", "90", "--nlon", "180", "--nsamples", "1500", "--modes", "12",
-              "--no-cpu-baseline", "--no-configs"]      # (--no-configs: without the full-size config-3 / config-5 legs of a multi-rank line)
+              "--full", "--no-cpu-baseline", "--no-configs"]  # (--full: the parity checks; --no-configs: without the full-size
+    #                                                            config-3 / config-5 legs of a multi-rank line)
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29517", os.path.join(root, "bench.py"),
@@ -201,6 +202,44 @@ def test_two_rank_sharded_path_on_one_gpu(ctx):
     assert self2.returncode == 0, self2.stderr[-2000:]
     ds = json.loads([ln for ln in self2.stdout.strip().splitlines() if ln.startswith("{")][-1])
     assert ds["n_gpus"] == 2 and np.allclose(ds["parity"]["s_head"], d2["parity"]["s_head"], rtol=1e-7)
+
+
+def test_bench_plain_run_and_dump_outputs(ctx, tmp_path):
+    """A plain bench run is the headline alone (--steps timed steps, ms_per_step, no parity / baseline legs), and
+    --dump-outputs writes what its last step returned: the same arguments give the same outputs, and they are a valid
+    decomposition (orthonormal factors, descending spectrum)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, p, k = 1500, 90 * 180, 12
+    common = ["--steps", "3", "--warmup", "1", "--nlat", "90", "--nlon", "180", "--nsamples", str(n), "--modes", str(k)]
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + ["--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=300, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len(r.stdout.strip().splitlines()) == 1
+        line = json.loads(r.stdout)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert "parity" not in line and "configs" not in line and line["cpu_baseline"] is None
+        assert sorted(os.listdir(d)) == ["U.npy", "V.npy", "s.npy", "total_variance.npy"]
+        runs.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    out = runs[0]
+    assert out["U"].shape == (n, k) and out["V"].shape == (p, k) and out["s"].shape == (k,)
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    for name in out:
+        assert np.array_equal(out[name], runs[1][name]), name
+    eye = np.eye(k)
+    assert np.abs(out["U"].astype(np.float64).T @ out["U"] - eye).max() < 1e-5
+    assert np.abs(out["V"].astype(np.float64).T @ out["V"] - eye).max() < 1e-5
+    assert np.all(np.diff(out["s"]) <= 0) and out["s"][-1] > 0
+    assert (out["s"].astype(np.float64) ** 2).sum() / (n - 1) <= out["total_variance"][0] * (1 + 1e-5)
 
 
 @pytest.mark.parametrize("nan,pca", [(False, False), (True, False), (False, True)])
