@@ -423,6 +423,28 @@ int eofx_resample_f32(eofx_ctx *ctx, const eofx_mat *src, const int64_t *rows, i
  * rowptr [n + 1] = segment starts of `order` per source row (device int64).  Float64 sums in draw order: reproducible. */
 int eofx_panel_bootstrap_f32(eofx_ctx *ctx, const float *P_in, int64_t n, int64_t rows_pad, int L, const int64_t *idx,
                              const int64_t *order, const int64_t *rowptr, int transpose, float *P_out);
+/* ---- delay embedding of Extended EOF analysis (xeofs/single/eeof.py:124-150) as an operator ---------------------
+ * The embedded matrix of `embedding` = E lags spaced `tau` samples apart, X_ext[t, (e, j)] = X[t + e tau, j] for
+ * t < n' = n - (E - 1) tau, centred per embedded column over its own window (mean mu[e, j]), is never written: both
+ * products run on the resident matrix m (any layout of a compacted matrix: owned, raw in place, sample-contiguous; not
+ * a masked in-place matrix) with the lags moved onto the sample-side panel.  Feature-side panels of the embedded operator
+ * are (E p_pad) x L, lag-major (row e p_pad + j, zero padding rows j >= p in every lag block); sample-side panels are
+ * n'_pad x L with n'_pad = n' rounded up to 512 (rows >= n' zero).  Lags are processed in groups of at most 1024 / L
+ * lags (the field is read once per group).  Float64 sums in a fixed order: reproducible bit for bit.  `prec` as in
+ * eofx_panel_tmul_f32.  EOFX_ERR_SHAPE when n' < 2.                                                                  */
+/* mean [E p_pad] (device, float64) = the window means mu (0 on the padding rows); total_variance (host, may be NULL) =
+ * sum_{e,j} (sum_window x^2 - n' mu^2) / (n' - 1), the total variance of the centred embedded matrix.  One read of
+ * the field.                                                                                                        */
+int eofx_lag_stats_f64(eofx_ctx *ctx, const eofx_mat *m, int tau, int embedding, double *mean, double *total_variance);
+/* Ye [(E p_pad) x L] = X_ext^T Zn - mu (1^T Zn), Zn [n'_pad x L] (device; L a multiple of 32)                           */
+int eofx_lag_tmul_f32(eofx_ctx *ctx, const eofx_mat *m, int tau, int embedding, const double *mean, const float *Zn, int L,
+                      float *Ye, int prec);
+/* Wn [n'_pad x L] = X_ext Ye - 1 (mu^T Ye), Ye [(E p_pad) x L] (device; L a multiple of 32)                             */
+int eofx_lag_mul_f32(eofx_ctx *ctx, const eofx_mat *m, int tau, int embedding, const double *mean, const float *Ye, int L,
+                     float *Wn, int prec);
+/* out [n' x E p] (device, row-major) = X_ext, not centred: the embedded matrix itself, for the exact decomposition of a
+ * small embedded matrix (the caller checks that it fits)                                                               */
+int eofx_lag_embed_f32(eofx_ctx *ctx, const eofx_mat *m, int tau, int embedding, float *out);
 /* Gram matrix of a resident matrix (float32, device): side 0 = sample space G[n_pad x n_pad] = X X^T,
  * side 1 = feature space G[p_pad x p_pad] = X^T X (rows/columns beyond n / p are zero).  Used for
  * (a) the total squared covariance sum(|X^T Y|^2) = <X X^T, Y Y^T> (cross/cpcca.py:991-1000) when X and

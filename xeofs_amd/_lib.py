@@ -106,6 +106,10 @@ SIGNATURES = {
     "eofx_mat_feature_norms_f64": (_int, [_vp, _vp, _vp]),
     "eofx_mat_sample_norms_f64": (_int, [_vp, _vp, _vp]),
     "eofx_panel_bootstrap_f32": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _int, _vp]),
+    "eofx_lag_stats_f64": (_int, [_vp, _vp, _int, _int, _vp, _pd]),
+    "eofx_lag_tmul_f32": (_int, [_vp, _vp, _int, _int, _vp, _vp, _int, _vp, _int]),
+    "eofx_lag_mul_f32": (_int, [_vp, _vp, _int, _int, _vp, _vp, _int, _vp, _int]),
+    "eofx_lag_embed_f32": (_int, [_vp, _vp, _int, _int, _vp]),
     "eofx_resample_f32": (_int, [_vp, _vp, _vp, _i64, _int, C.POINTER(_vp), _vp, _pd]),
     "eofx_mat_gram_f32": (_int, [_vp, _vp, _int, _vp]),
     "eofx_mat_cross_gram_f32": (_int, [_vp, _vp, _vp, _int, _vp]),

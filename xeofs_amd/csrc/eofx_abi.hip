@@ -8,6 +8,7 @@
 #include "eofx_gram.hpp"
 #include "eofx_axb_dma.hpp"
 #include "eofx_hosteig.hpp"
+#include "eofx_lag.hpp"
 #ifndef EOFX_AXB_DMA_DEFAULT
 #define EOFX_AXB_DMA_DEFAULT 1
 #endif
@@ -6088,6 +6089,193 @@ extern "C" int eofx_panel_rot_step_f64(eofx_ctx* ctx, const float* X, int64_t ro
   KCHK();
   const int64_t count = (int64_t)L * L;
   hipLaunchKernelGGL(f64_reduce_kernel, dim3((int)((count + 63) / 64)), dim3(256), 0, ctx->stream, part, G, count, nbx);
+  KCHK();
+  return EOFX_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// delay embedding of Extended EOF analysis as an operator on the resident field (eofx_lag.hpp)
+// ------------------------------------------------------------------------------------
+// Lags are processed in groups whose side-by-side sample panel is at most this many columns wide: the wide product then
+// stays on the wide-panel kernels (the MFMA NT kernel of eofx_gram.hpp from 512 columns, the 128-column streaming tiles
+// below) while E = 100 lags of a 64-column panel do not ask for a 6400-column intermediate.  The field is read once
+// per group.
+constexpr int EOFX_LAG_GROUP_COLS = 1024;
+
+static int lag_groupsize(int E, int L) { return std::max(1, std::min(E, EOFX_LAG_GROUP_COLS / std::max(L, 1))); }
+
+static int lag_check(eofx_ctx* ctx, const eofx_mat* m, int tau, int E, int64_t* nprime) {
+  if (!m || tau < 1 || E < 1) return set_err(ctx, EOFX_ERR_ARG, "bad argument (tau >= 1, embedding >= 1)");
+  if (m->masked) return set_err(ctx, EOFX_ERR_ARG, "the lag operator needs a compacted matrix (no masked in-place layout)");
+  const int64_t np = m->n - (int64_t)(E - 1) * tau;
+  if (np < 2)
+    return set_err(ctx, EOFX_ERR_SHAPE, "embedding %d with tau %d leaves %lld of %lld samples (at least 2 are needed)", E, tau,
+                   (long long)np, (long long)m->n);
+  *nprime = np;
+  return EOFX_OK;
+}
+
+static int lag_source(eofx_ctx* ctx, const eofx_mat* m, LagSrc& s) {
+  if (!m->X && m->raw && m->aff) {
+    s.a = m->raw;
+    s.ld = m->raw_ld;
+    s.mode = 1;
+    s.aff = m->aff;
+    s.aff_ld = m->p_pad;
+  } else if (m->X || !m->Xt) {
+    CHK(ensure_X(ctx, m));
+    s.a = m->X;
+    s.ld = m->p_pad;
+    s.mode = 0;
+  } else {
+    s.a = m->Xt;
+    s.ld = m->n_pad;
+    s.mode = 2;
+  }
+  return EOFX_OK;
+}
+
+static int lag_blocks(int64_t total4) { return (int)std::max<int64_t>(1, std::min<int64_t>((total4 + 255) / 256, 8192)); }
+
+extern "C" int eofx_lag_stats_f64(eofx_ctx* ctx, const eofx_mat* m, int tau, int embedding, double* mean,
+                                  double* total_variance) {
+  if (!ctx || !mean) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  int64_t np = 0;
+  CHK(lag_check(ctx, m, tau, embedding, &np));
+  if (!is_device_ptr(mean)) return set_err(ctx, EOFX_ERR_ARG, "mean must be a device buffer of embedding * p_pad doubles");
+  ENTER(ctx);
+  const int E = embedding;
+  // window boundaries: (row, lag, sign) sorted by row -- F(e tau) leaves the window sum, F(e tau + n') enters it
+  std::vector<int64_t> ev;
+  ev.reserve(6 * (size_t)E);
+  std::vector<std::pair<int64_t, std::pair<int64_t, int64_t>>> evs;
+  for (int e = 0; e < E; ++e) {
+    evs.push_back({(int64_t)e * tau, {e, -1}});
+    evs.push_back({(int64_t)e * tau + np, {e, 1}});
+  }
+  std::sort(evs.begin(), evs.end());
+  for (auto& x : evs) {
+    ev.push_back(x.first);
+    ev.push_back(x.second.first);
+    ev.push_back(x.second.second);
+  }
+  CHK(arena_reserve(ctx, ev.size() * sizeof(int64_t) + (size_t)(m->p_pad + 1) * sizeof(double) + 4096));
+  ArenaScope scope(ctx);
+  ARENA(int64_t, dev_ev, ev.size());
+  ARENA(double, tvpart, m->p_pad);
+  ARENA(double, tv, 1);
+  LagSrc src;
+  CHK(lag_source(ctx, m, src));
+  HIPCHK(hipMemcpyAsync(dev_ev, ev.data(), ev.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(lag_stats_kernel, dim3((unsigned)((m->p_pad + 255) / 256)), dim3(256), 0, ctx->stream, src, m->n, m->p,
+                     m->p_pad, tau, E, np, (const int64_t*)dev_ev, (int)(ev.size() / 3), mean, tvpart);
+  KCHK();
+  hipLaunchKernelGGL(lag_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)tvpart, m->p_pad, tv);
+  KCHK();
+  double h = 0.0;
+  HIPCHK(hipMemcpyAsync(&h, tv, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));      // (also: `ev` leaves scope)
+  if (total_variance) *total_variance = h;
+  return EOFX_OK;
+}
+
+static size_t lag_tmul_scratch(eofx_ctx* ctx, const eofx_mat* m, int Lg, int prec) {
+  size_t need = atb_scratch_bytes(m->p_pad, round_up(m->n, ATB_KG), Lg);
+  if (prec == EOFX_PREC_F16X3 && tmul_nt_ok(m, Lg)) need = std::max(need, tmul_nt_scratch(ctx, m, Lg));
+  return need;
+}
+
+extern "C" int eofx_lag_tmul_f32(eofx_ctx* ctx, const eofx_mat* m, int tau, int embedding, const double* mean, const float* Zn,
+                                 int L, float* Ye, int prec) {
+  if (!ctx || !mean || !Zn || !Ye || L <= 0 || L % 32 || !valid_prec(prec)) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  int64_t np = 0;
+  CHK(lag_check(ctx, m, tau, embedding, &np));
+  if (!is_device_ptr(mean)) return set_err(ctx, EOFX_ERR_ARG, "mean must be a device buffer (eofx_lag_stats_f64)");
+  ENTER(ctx);
+  const int E = embedding, G = lag_groupsize(E, L), Gl = E - (E - 1) / G * G;   // full groups of G lags, the last of Gl
+  const int Lg = G * L;
+  const int NPART = 64;
+  size_t need = (size_t)m->n_pad * Lg * sizeof(float) + (size_t)m->p_pad * Lg * sizeof(float) + (size_t)(NPART + 1) * L * 8 + 8192;
+  need += std::max(lag_tmul_scratch(ctx, m, Lg, prec), lag_tmul_scratch(ctx, m, Gl * L, prec));
+  CHK(arena_reserve(ctx, need));
+  ArenaScope scope(ctx);
+  ARENA(double, part, (size_t)NPART * L);
+  ARENA(double, cs, L);
+  ARENA(float, W, (size_t)m->n_pad * Lg);
+  ARENA(float, P, (size_t)m->p_pad * Lg);
+  // 1^T Z over the n' rows of the sample-side panel
+  hipLaunchKernelGGL(panel_colsum_part_kernel, dim3(NPART), dim3(256), 0, ctx->stream, Zn, np, L, part);
+  KCHK();
+  hipLaunchKernelGGL(panel_colsum_final_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)part, NPART, L, cs);
+  KCHK();
+  for (int e0 = 0; e0 < E; e0 += G) {
+    const int ng = std::min(G, E - e0), Lw = ng * L;
+    hipLaunchKernelGGL(lag_spread_kernel, dim3(lag_blocks(m->n_pad * (Lw / 4))), dim3(256), 0, ctx->stream, Zn, np, L, m->n_pad,
+                       Lw, e0, tau, W);
+    KCHK();
+    CHK(panel_tmul(ctx, m, W, P, Lw, prec));
+    hipLaunchKernelGGL(lag_gather_kernel, dim3(lag_blocks((int64_t)ng * m->p_pad * (L / 4))), dim3(256), 0, ctx->stream,
+                       (const float*)P, Lw, m->p, m->p_pad, L, e0, ng, mean, (const double*)cs, Ye);
+    KCHK();
+  }
+  return EOFX_OK;
+}
+
+extern "C" int eofx_lag_mul_f32(eofx_ctx* ctx, const eofx_mat* m, int tau, int embedding, const double* mean, const float* Ye,
+                                int L, float* Wn, int prec) {
+  if (!ctx || !mean || !Ye || !Wn || L <= 0 || L % 32 || !valid_prec(prec)) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  int64_t np = 0;
+  CHK(lag_check(ctx, m, tau, embedding, &np));
+  if (!is_device_ptr(mean)) return set_err(ctx, EOFX_ERR_ARG, "mean must be a device buffer (eofx_lag_stats_f64)");
+  ENTER(ctx);
+  const int E = embedding, G = lag_groupsize(E, L), Gl = E - (E - 1) / G * G;
+  const int Lg = G * L;
+  const int64_t np_pad = round_up(np, ATB_BM);
+  const bool grouped = G < E;
+  // partials of mu^T Y: one per ~8k rows of the (E p_pad)-row panel, at least 64 (a fixed count per shape: reproducible)
+  const int NPART = (int)std::min<int64_t>(2048, std::max<int64_t>(64, (int64_t)E * m->p_pad / 8192));
+  size_t need = (size_t)m->p_pad * Lg * sizeof(float) + (size_t)m->n_pad * Lg * sizeof(float) + (size_t)(NPART + 1) * L * 8 +
+                (grouped ? (size_t)np_pad * L * sizeof(double) : 0) + 8192;
+  need += std::max(atb_scratch_bytes(m->n_pad, round_up(m->p, ATB_KG), Lg), atb_scratch_bytes(m->n_pad, round_up(m->p, ATB_KG), Gl * L));
+  CHK(arena_reserve(ctx, need));
+  ArenaScope scope(ctx);
+  ARENA(double, part, (size_t)NPART * L);
+  ARENA(double, cs, L);
+  double* acc = nullptr;
+  if (grouped) {
+    ARENA(double, a, (size_t)np_pad * L);
+    acc = a;
+  }
+  ARENA(float, Yg, (size_t)m->p_pad * Lg);
+  ARENA(float, P, (size_t)m->n_pad * Lg);
+  // mu^T Y over all E p_pad rows (the padding rows carry mean 0)
+  hipLaunchKernelGGL(lag_wcolsum_part_kernel, dim3(NPART), dim3(256), 0, ctx->stream, Ye, mean, (int64_t)E * m->p_pad, L, part);
+  KCHK();
+  hipLaunchKernelGGL(panel_colsum_final_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)part, NPART, L, cs);
+  KCHK();
+  for (int e0 = 0; e0 < E; e0 += G) {
+    const int ng = std::min(G, E - e0), Lw = ng * L;
+    hipLaunchKernelGGL(lag_relayout_kernel, dim3(lag_blocks(m->p_pad * (Lw / 4))), dim3(256), 0, ctx->stream, Ye, m->p_pad, L, e0,
+                       ng, Yg);
+    KCHK();
+    CHK(panel_mul(ctx, m, Yg, P, Lw, prec));
+    hipLaunchKernelGGL(lag_fold_kernel, dim3(lag_blocks(np_pad * (L / 4))), dim3(256), 0, ctx->stream, (const float*)P, Lw, L, e0,
+                       ng, tau, np, np_pad, acc, (int)(e0 == 0), (int)(e0 + ng == E), (const double*)cs, Wn);
+    KCHK();
+  }
+  return EOFX_OK;
+}
+
+extern "C" int eofx_lag_embed_f32(eofx_ctx* ctx, const eofx_mat* m, int tau, int embedding, float* out) {
+  if (!ctx || !out) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  int64_t np = 0;
+  CHK(lag_check(ctx, m, tau, embedding, &np));
+  if (!is_device_ptr(out)) return set_err(ctx, EOFX_ERR_ARG, "out must be a device buffer of n' x embedding * p floats");
+  ENTER(ctx);
+  LagSrc src;
+  CHK(lag_source(ctx, m, src));
+  hipLaunchKernelGGL(lag_embed_kernel, dim3(lag_blocks(np * embedding * m->p)), dim3(256), 0, ctx->stream, src, m->p, embedding,
+                     tau, np, out);
   KCHK();
   return EOFX_OK;
 }

@@ -1054,6 +1054,59 @@ def panel_bootstrap(ctx: Context, P, n: int, idx, order, rowptr, transpose: bool
     return out
 
 
+# --------------------------------------------------------------------------- #
+# delay embedding of Extended EOF analysis (eofx_lag_*, csrc/eofx_lag.hpp)       #
+# --------------------------------------------------------------------------- #
+def lag_samples(mat: ResidentMatrix, tau: int, embedding: int) -> int:
+    """n' = n - (embedding - 1) tau: the rows of the embedded matrix"""
+    return mat.n - (int(embedding) - 1) * int(tau)
+
+
+def lag_stats(ctx: Context, mat: ResidentMatrix, tau: int, embedding: int):
+    """-> (window means mu as a float64 device tensor [embedding * p_pad], lag-major with zero padding rows; total variance
+    of the centred embedded matrix)"""
+    torch = _torch()
+    mean = torch.empty(int(embedding) * mat.p_pad, dtype=torch.float64, device=f"cuda:{ctx.device}")
+    tv = C.c_double()
+    raise_for(ctx.lib.eofx_lag_stats_f64(ctx.handle, mat.handle, int(tau), int(embedding), ptr(mean), C.byref(tv)), ctx.handle)
+    return mean, tv.value
+
+
+def lag_tmul(ctx: Context, mat: ResidentMatrix, tau: int, embedding: int, mean, Zn, out=None, prec="f32"):
+    """Ye[embedding * p_pad, L] = X_ext^T Zn - mu (1^T Zn), Zn[n'_pad, L]"""
+    torch = _torch()
+    L = Zn.shape[1]
+    if out is None:
+        out = torch.empty((int(embedding) * mat.p_pad, L), dtype=torch.float32, device=Zn.device)
+    raise_for(ctx.lib.eofx_lag_tmul_f32(ctx.handle, mat.handle, int(tau), int(embedding), ptr(mean), ptr(Zn), L, ptr(out),
+                                        _lib.PREC[prec]), ctx.handle)
+    return out
+
+
+def lag_mul(ctx: Context, mat: ResidentMatrix, tau: int, embedding: int, mean, Ye, out=None, prec="f32"):
+    """Wn[n'_pad, L] = X_ext Ye - 1 (mu^T Ye), Ye[embedding * p_pad, L]"""
+    torch = _torch()
+    L = Ye.shape[1]
+    if out is None:
+        rows = (lag_samples(mat, tau, embedding) + 511) // 512 * 512
+        out = torch.empty((rows, L), dtype=torch.float32, device=Ye.device)
+    raise_for(ctx.lib.eofx_lag_mul_f32(ctx.handle, mat.handle, int(tau), int(embedding), ptr(mean), ptr(Ye), L, ptr(out),
+                                       _lib.PREC[prec]), ctx.handle)
+    return out
+
+
+def lag_embed(ctx: Context, mat: ResidentMatrix, tau: int, embedding: int, out=None):
+    """the embedded matrix X_ext [n', embedding * p] (not centred) as a float32 device tensor"""
+    torch = _torch()
+    shape = (lag_samples(mat, tau, embedding), int(embedding) * mat.p)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=f"cuda:{ctx.device}")
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {shape} tensor")
+    raise_for(ctx.lib.eofx_lag_embed_f32(ctx.handle, mat.handle, int(tau), int(embedding), ptr(out)), ctx.handle)
+    return out
+
+
 def panel_rownorm(ctx: Context, P, rows: int) -> np.ndarray:
     out = np.empty(rows, np.float64)
     raise_for(ctx.lib.eofx_panel_rownorm_f64(ctx.handle, ptr(P), rows, P.shape[1], ptr(out)), ctx.handle)

@@ -473,7 +473,8 @@ def sharded_rsvd(ops, comm: Comm, k: int, p_total: int, p_offset: int, n_oversam
         Z = ops.import_panel(omega[p_offset:p_offset + p_loc], "p")
 
     # rows of a feature-side panel that can carry data (a masked in-place matrix keeps its physical rows, zero where masked)
-    p_rows = int(getattr(getattr(ops, "mat", None), "p_phys", p_loc))
+    # (an operator whose feature-side panels interleave padding rows names its own count: `p_rows`)
+    p_rows = int(getattr(ops, "p_rows", getattr(getattr(ops, "mat", None), "p_phys", p_loc)))
 
     def to_side(P, side, final):
         """product that lands on `side` from a panel on the other side; `final` selects the
