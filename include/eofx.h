@@ -445,6 +445,38 @@ int eofx_lag_mul_f32(eofx_ctx *ctx, const eofx_mat *m, int tau, int embedding, c
 /* out [n' x E p] (device, row-major) = X_ext, not centred: the embedded matrix itself, for the exact decomposition of a
  * small embedded matrix (the caller checks that it fits)                                                               */
 int eofx_lag_embed_f32(eofx_ctx *ctx, const eofx_mat *m, int tau, int embedding, float *out);
+/* ---- geographically weighted PCA (xeofs/single/gwpca.py:133-230, xeofs/utils/optional/numba_utils.py:13-76) ----------
+ * For every location i (row of the compacted resident matrix m, n x p, read in its feature-contiguous layout) the local
+ * PCA of all locations weighted by w_ij = K(d_ij / bandwidth): W_i = sum w_ij, mu_i = sum w_ij x_j / W_i,
+ * C_i = sum w_ij (x_j - mu_i)(x_j - mu_i)^T, eigenpairs of C_i / W_i (= the reference's s^2 / sum w).
+ * xy [n x 2] (host, float64) = per-location coordinates: (lon, lat) in degrees for haversine (km, radius 6371.0),
+ * (x, y) for euclidean.  Kernels (xeofs/utils/optional/kernels.py): bisquare (1 - u^2)^2 for d <= b else 0, gaussian
+ * exp(-u^2 / 2), exponential exp(-u / 2), u = d / b.  Locations are tiled spatially; a pair of tiles is skipped only
+ * when every weight in it is exactly 0 in float64 (so pruning never changes a result).  Float64 moments with a shared
+ * per-tile shift; no atomics, fixed summation order: reproducible bit for bit.  EOFX_ERR_ARG for bandwidth <= 0, an
+ * unknown metric or kernel, k < 1 or k > p, a coordinate that is not finite; EOFX_ERR_SHAPE for p > 256.                                              */
+#define EOFX_GW_METRIC_EUCLIDEAN 0
+#define EOFX_GW_METRIC_HAVERSINE 1
+#define EOFX_GW_KERNEL_BISQUARE 0
+#define EOFX_GW_KERNEL_GAUSSIAN 1
+#define EOFX_GW_KERNEL_EXPONENTIAL 2
+/* the whole fit for p <= 64 (EOFX_ERR_SHAPE above; eofx_gw_cov_f64 + a library eigensolver there).  The centres go in
+ * chunks of `chunk` locations (rounded up to a multiple of 16; 0 = automatic: the chunk's moment buffers within 256 MiB)
+ * taken in the spatial (Morton) order of the tiling, so a chunk is compact whatever the input order.  Device outputs in
+ * location order: components [n x p x k] float32, explained_variance [n x k] = the k largest eigenvalues (descending,
+ * clamped at 0), total_variance [n] = trace(C_i) / W_i.  Eigenvectors signed by get_deterministic_sign_multiplier
+ * (xeofs/linalg/_numpy/_svd.py:13-33).  stats (host, may be NULL) [8]: tile pairs visited, tile pairs in all, chunks,
+ * tiles, microseconds of tiling (host), covariance (device), eigensolver (device), locations per chunk.               */
+int eofx_gwpca_f64(eofx_ctx *ctx, const eofx_mat *m, const double *xy, int metric, int kernel, double bandwidth, int k,
+                   int64_t chunk, float *components, double *explained_variance, double *total_variance, int64_t *stats);
+/* the local covariances C_i / W_i of locations [first, first + count) (one chunk, tiled among themselves) as dense p x p float64 matrices (device,
+ * cov [count x p x p]) and their traces (device, total_variance [count]); stats as above                            */
+int eofx_gw_cov_f64(eofx_ctx *ctx, const eofx_mat *m, const double *xy, int metric, int kernel, double bandwidth,
+                    int64_t first, int64_t count, double *cov, double *total_variance, int64_t *stats);
+/* batched symmetric eigensolver, 1 <= p <= 64, 1 <= k <= p (device buffers): A [batch x p x p] (upper triangle read),
+ * w [batch x k] the k largest eigenvalues (descending, index-stable ties, clamped at 0), V [batch x p x k] orthonormal
+ * eigenvectors with the sign rule above.  Cyclic Jacobi in LDS, one workgroup per matrix.                            */
+int eofx_batched_syev_f64(eofx_ctx *ctx, const double *A, int64_t batch, int p, int k, double *w, double *V);
 /* Gram matrix of a resident matrix (float32, device): side 0 = sample space G[n_pad x n_pad] = X X^T,
  * side 1 = feature space G[p_pad x p_pad] = X^T X (rows/columns beyond n / p are zero).  Used for
  * (a) the total squared covariance sum(|X^T Y|^2) = <X X^T, Y Y^T> (cross/cpcca.py:991-1000) when X and

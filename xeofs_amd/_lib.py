@@ -110,6 +110,9 @@ SIGNATURES = {
     "eofx_lag_tmul_f32": (_int, [_vp, _vp, _int, _int, _vp, _vp, _int, _vp, _int]),
     "eofx_lag_mul_f32": (_int, [_vp, _vp, _int, _int, _vp, _vp, _int, _vp, _int]),
     "eofx_lag_embed_f32": (_int, [_vp, _vp, _int, _int, _vp]),
+    "eofx_gwpca_f64": (_int, [_vp, _vp, _vp, _int, _int, C.c_double, _int, _i64, _vp, _vp, _vp, _pi64]),
+    "eofx_gw_cov_f64": (_int, [_vp, _vp, _vp, _int, _int, C.c_double, _i64, _i64, _vp, _vp, _pi64]),
+    "eofx_batched_syev_f64": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "eofx_resample_f32": (_int, [_vp, _vp, _vp, _i64, _int, C.POINTER(_vp), _vp, _pd]),
     "eofx_mat_gram_f32": (_int, [_vp, _vp, _int, _vp]),
     "eofx_mat_cross_gram_f32": (_int, [_vp, _vp, _vp, _int, _vp]),

@@ -9,6 +9,7 @@
 #include "eofx_axb_dma.hpp"
 #include "eofx_hosteig.hpp"
 #include "eofx_lag.hpp"
+#include "eofx_gw.hpp"
 #ifndef EOFX_AXB_DMA_DEFAULT
 #define EOFX_AXB_DMA_DEFAULT 1
 #endif
@@ -17,6 +18,7 @@
 #include <immintrin.h>
 #endif
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <complex>
@@ -6277,5 +6279,342 @@ extern "C" int eofx_lag_embed_f32(eofx_ctx* ctx, const eofx_mat* m, int tau, int
   hipLaunchKernelGGL(lag_embed_kernel, dim3(lag_blocks(np * embedding * m->p)), dim3(256), 0, ctx->stream, src, m->p, embedding,
                      tau, np, out);
   KCHK();
+  return EOFX_OK;
+}
+
+// ---- geographically weighted PCA (csrc/eofx_gw.hpp) ------------------------------------------------------------------
+namespace {
+
+// One set of locations cut into tiles of GW_T in Morton order of their (normalised) coordinates, with a bound per tile
+// and per group of 16 tiles: for haversine the unit-vector centre and angular radius (handles the dateline and the
+// poles), for euclidean the bounding box.
+struct GwTiles {
+  std::vector<int64_t> perm;   // sorted position -> row of X
+  std::vector<double> geo;     // [3 x sorted position] (eofx_gw.hpp gw_weight)
+  std::vector<std::array<double, 4>> tile, group;
+  int64_t count = 0, ntiles = 0;
+};
+
+static double gw_angle(const double* a, const double* b) {
+  const double cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
+  return std::atan2(std::sqrt(cx * cx + cy * cy + cz * cz), a[0] * b[0] + a[1] * b[1] + a[2] * b[2]);
+}
+
+static std::array<double, 4> gw_bound(const std::vector<double>& u, int64_t s0, int64_t s1, int metric) {
+  if (metric == EOFX_GW_METRIC_EUCLIDEAN) {
+    std::array<double, 4> b{u[3 * s0], u[3 * s0], u[3 * s0 + 1], u[3 * s0 + 1]};
+    for (int64_t s = s0 + 1; s < s1; ++s) {
+      b[0] = std::min(b[0], u[3 * s]);
+      b[1] = std::max(b[1], u[3 * s]);
+      b[2] = std::min(b[2], u[3 * s + 1]);
+      b[3] = std::max(b[3], u[3 * s + 1]);
+    }
+    return b;
+  }
+  double c[3] = {0.0, 0.0, 0.0};
+  for (int64_t s = s0; s < s1; ++s)
+    for (int d = 0; d < 3; ++d) c[d] += u[3 * s + d];
+  const double nrm = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+  for (int d = 0; d < 3; ++d) c[d] = nrm > 1e-9 * (double)(s1 - s0) ? c[d] / nrm : u[3 * s0 + d];
+  double rho = 0.0;
+  for (int64_t s = s0; s < s1; ++s) rho = std::max(rho, gw_angle(c, &u[3 * s]));
+  return {c[0], c[1], c[2], rho};
+}
+
+// a lower bound of every distance between two bounded sets (km for haversine, less a margin of 1e-9 rad for rounding)
+static double gw_lower(const std::array<double, 4>& a, const std::array<double, 4>& b, int metric) {
+  if (metric == EOFX_GW_METRIC_EUCLIDEAN) {
+    const double dx = std::max({0.0, a[0] - b[1], b[0] - a[1]}), dy = std::max({0.0, a[2] - b[3], b[2] - a[3]});
+    return std::sqrt(dx * dx + dy * dy);
+  }
+  const double th = gw_angle(a.data(), b.data()) - a[3] - b[3] - 1e-9;
+  return th > 0.0 ? GW_EARTH_RADIUS * th : 0.0;
+}
+
+// true when every weight at a distance >= dlb is exactly 0 in float64 (bisquare: beyond the bandwidth; gaussian and
+// exponential: exp of an argument below -750 underflows to 0)
+static bool gw_zero(double dlb, int kernel, double bw) {
+  const double u = dlb / bw;
+  if (kernel == EOFX_GW_KERNEL_BISQUARE) return dlb > bw;
+  if (kernel == EOFX_GW_KERNEL_GAUSSIAN) return 0.5 * u * u > 750.0;
+  return 0.5 * u > 750.0;
+}
+
+static uint64_t gw_morton(uint32_t x, uint32_t y) {
+  uint64_t k = 0;
+  for (int b = 0; b < 16; ++b) k |= (uint64_t)((x >> b) & 1u) << (2 * b) | (uint64_t)((y >> b) & 1u) << (2 * b + 1);
+  return k;
+}
+
+static void gw_tile(const double* xy, int64_t first, int64_t count, int metric, const double* box, GwTiles& t) {
+  t.count = count;
+  t.ntiles = (count + GW_T - 1) / GW_T;
+  std::vector<std::pair<uint64_t, int64_t>> key((size_t)count);
+  for (int64_t i = 0; i < count; ++i) {
+    const double* c = xy + 2 * (first + i);
+    const double fx = box[1] > box[0] ? (c[0] - box[0]) / (box[1] - box[0]) : 0.0;
+    const double fy = box[3] > box[2] ? (c[1] - box[2]) / (box[3] - box[2]) : 0.0;
+    key[(size_t)i] = {gw_morton((uint32_t)std::min(65535.0, std::max(0.0, fx * 65535.0)),
+                                (uint32_t)std::min(65535.0, std::max(0.0, fy * 65535.0))), first + i};
+  }
+  std::sort(key.begin(), key.end());
+  t.perm.resize((size_t)count);
+  t.geo.resize(3 * (size_t)count);
+  std::vector<double> u(3 * (size_t)count);
+  for (int64_t s = 0; s < count; ++s) {
+    const int64_t i = key[(size_t)s].second;
+    t.perm[(size_t)s] = i;
+    const double x = xy[2 * i], y = xy[2 * i + 1];
+    if (metric == EOFX_GW_METRIC_HAVERSINE) {
+      const double lon = x * (M_PI / 180.0), lat = y * (M_PI / 180.0);
+      t.geo[3 * s] = lon;
+      t.geo[3 * s + 1] = lat;
+      t.geo[3 * s + 2] = std::cos(lat);
+      u[3 * s] = std::cos(lat) * std::cos(lon);
+      u[3 * s + 1] = std::cos(lat) * std::sin(lon);
+      u[3 * s + 2] = std::sin(lat);
+    } else {
+      t.geo[3 * s] = u[3 * s] = x;
+      t.geo[3 * s + 1] = u[3 * s + 1] = y;
+      t.geo[3 * s + 2] = u[3 * s + 2] = 0.0;
+    }
+  }
+  t.tile.clear();
+  t.group.clear();
+  for (int64_t a = 0; a < t.ntiles; ++a) t.tile.push_back(gw_bound(u, a * GW_T, std::min(count, (a + 1) * GW_T), metric));
+  for (int64_t g = 0; g < t.ntiles; g += 16)
+    t.group.push_back(gw_bound(u, g * GW_T, std::min(count, (g + 16) * GW_T), metric));
+}
+
+// Per chunk of centres: its tiles and the CSR list (ascending) of neighbour tiles that hold a weight > 0
+struct GwChunk {
+  int64_t first = 0, count = 0, off_tiles = 0, off_cols = 0;
+  GwTiles c;
+};
+
+struct GwPlan {
+  GwTiles nb;
+  std::vector<GwChunk> chunks;
+  std::vector<int> rowptr, cols;     // concatenated over the chunks (rowptr entries relative to the chunk's off_cols)
+  int64_t visited = 0, possible = 0, ctiles = 0;
+  int64_t first = 0;                 // the location range [first, first + count) of an unsorted plan (0 when sorted)
+  bool sorted = false;
+};
+
+// sorted: the centres are ALL locations in the neighbours' Morton order, cut into chunks of `chunk` (a multiple of GW_T)
+// sorted positions, so a chunk's tiles are the neighbour tiles themselves and spatially compact whatever the input order.
+// Otherwise the centres are the locations [first, first + count) as ONE chunk, tiled among themselves.
+static void gw_plan(const double* xy, int64_t n, int64_t first, int64_t count, int64_t chunk, bool sorted, int metric, int kernel,
+                    double bw, GwPlan& plan) {
+  double box[4] = {xy[0], xy[0], xy[1], xy[1]};
+  for (int64_t i = 0; i < n; ++i) {
+    box[0] = std::min(box[0], xy[2 * i]);
+    box[1] = std::max(box[1], xy[2 * i]);
+    box[2] = std::min(box[2], xy[2 * i + 1]);
+    box[3] = std::max(box[3], xy[2 * i + 1]);
+  }
+  gw_tile(xy, 0, n, metric, box, plan.nb);
+  plan.sorted = sorted;
+  plan.first = sorted ? 0 : first;
+  if (!sorted) chunk = count;
+  const int64_t ng = (int64_t)plan.nb.group.size();
+  const int64_t lo = sorted ? 0 : first, hi = sorted ? n : first + count;
+  for (int64_t c0 = lo; c0 < hi; c0 += chunk) {
+    GwChunk ch;
+    ch.first = c0;
+    ch.count = std::min(chunk, hi - c0);
+    ch.off_tiles = plan.ctiles;
+    ch.off_cols = (int64_t)plan.cols.size();
+    if (sorted) {
+      GwTiles& t = ch.c;
+      t.count = ch.count;
+      t.ntiles = (ch.count + GW_T - 1) / GW_T;
+      t.perm.assign(plan.nb.perm.begin() + c0, plan.nb.perm.begin() + c0 + ch.count);
+      t.geo.assign(plan.nb.geo.begin() + 3 * c0, plan.nb.geo.begin() + 3 * (c0 + ch.count));
+      t.tile.assign(plan.nb.tile.begin() + c0 / GW_T, plan.nb.tile.begin() + c0 / GW_T + t.ntiles);
+    } else {
+      gw_tile(xy, c0, ch.count, metric, box, ch.c);
+    }
+    for (int64_t a = 0; a < ch.c.ntiles; ++a) {
+      plan.rowptr.push_back((int)((int64_t)plan.cols.size() - ch.off_cols));
+      for (int64_t g = 0; g < ng; ++g) {
+        if (gw_zero(gw_lower(ch.c.tile[a], plan.nb.group[g], metric), kernel, bw)) continue;
+        for (int64_t t = g * 16; t < std::min(plan.nb.ntiles, (g + 1) * 16); ++t)
+          if (!gw_zero(gw_lower(ch.c.tile[a], plan.nb.tile[t], metric), kernel, bw)) plan.cols.push_back((int)t);
+      }
+    }
+    plan.rowptr.push_back((int)((int64_t)plan.cols.size() - ch.off_cols));
+    plan.ctiles += ch.c.ntiles;
+    plan.possible += ch.c.ntiles * plan.nb.ntiles;
+    plan.chunks.push_back(std::move(ch));
+  }
+  plan.visited = (int64_t)plan.cols.size();
+}
+
+static int gw_check(eofx_ctx* ctx, const eofx_mat* m, const double* xy, int metric, int kernel, double bw) {
+  if (!ctx || !m || !xy) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (!(bw > 0.0)) return set_err(ctx, EOFX_ERR_ARG, "bandwidth must be > 0, got %g", bw);
+  if (metric != EOFX_GW_METRIC_EUCLIDEAN && metric != EOFX_GW_METRIC_HAVERSINE)
+    return set_err(ctx, EOFX_ERR_ARG, "unknown metric %d", metric);
+  if (kernel < EOFX_GW_KERNEL_BISQUARE || kernel > EOFX_GW_KERNEL_EXPONENTIAL)
+    return set_err(ctx, EOFX_ERR_ARG, "unknown kernel %d", kernel);
+  if (m->masked) return set_err(ctx, EOFX_ERR_ARG, "GWPCA needs a compacted matrix (no masked in-place layout)");
+  if (m->p > GW_PMAX) return set_err(ctx, EOFX_ERR_SHAPE, "GWPCA supports at most %d features, got %lld", GW_PMAX, (long long)m->p);
+  if (m->n < 1) return set_err(ctx, EOFX_ERR_SHAPE, "no locations");
+  for (int64_t i = 0; i < 2 * m->n; ++i)
+    if (!std::isfinite(xy[i])) return set_err(ctx, EOFX_ERR_ARG, "coordinate %lld of location %lld is not finite", (long long)(i % 2), (long long)(i / 2));
+  return EOFX_OK;
+}
+
+// the covariances C / W of a plan's chunks, chunk by chunk, and (comps != nullptr) their eigenpairs into the outputs;
+// the device stages are timed with events (microseconds added to us_cov / us_eig)
+static int gw_run(eofx_ctx* ctx, const eofx_mat* m, const GwPlan& plan, int metric, int kernel, double bw, double* A_ext,
+                  double* tv_ext, int k, float* comps, double* ev, double* us_cov, double* us_eig) {
+  const int p = (int)m->p;
+  const int64_t q = p + 1, P2a = q * (q + 1) / 2, n = m->n;
+  int64_t cmax = 0;
+  for (auto& ch : plan.chunks) cmax = std::max(cmax, ch.count);
+  const int64_t cpad = (cmax + GW_T - 1) / GW_T * GW_T;
+  size_t need = (size_t)n * (8 + 24) * 2 + (plan.rowptr.size() + plan.cols.size()) * 4 + (size_t)cpad * P2a * 8 + 16384;
+  if (!A_ext) need += (size_t)cmax * p * p * 8;
+  CHK(ensure_X(ctx, m));
+  CHK(arena_reserve(ctx, need));
+  ArenaScope scope(ctx);
+  ARENA(int64_t, perm_n, n);
+  ARENA(double, geo_n, 3 * n);
+  ARENA(int64_t, perm_c, n);
+  ARENA(double, geo_c, 3 * n);
+  ARENA(int, rowptr, plan.rowptr.size());
+  ARENA(int, cols, std::max<size_t>(1, plan.cols.size()));
+  ARENA(double, S, (size_t)cpad * P2a);
+  double* A = A_ext;
+  if (!A) {
+    ARENA(double, Aw, (size_t)cmax * p * p);
+    A = Aw;
+  }
+  std::vector<int64_t> pc;
+  std::vector<double> gc;
+  pc.reserve((size_t)n);
+  gc.reserve(3 * (size_t)n);
+  for (auto& ch : plan.chunks) {
+    pc.insert(pc.end(), ch.c.perm.begin(), ch.c.perm.end());
+    gc.insert(gc.end(), ch.c.geo.begin(), ch.c.geo.end());
+  }
+  HIPCHK(hipMemcpyAsync(perm_n, plan.nb.perm.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(geo_n, plan.nb.geo.data(), 3 * n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(perm_c, pc.data(), pc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(geo_c, gc.data(), gc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(rowptr, plan.rowptr.data(), plan.rowptr.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (!plan.cols.empty())
+    HIPCHK(hipMemcpyAsync(cols, plan.cols.data(), plan.cols.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  std::vector<hipEvent_t> evs(3 * plan.chunks.size());
+  for (auto& e : evs) HIPCHK(hipEventCreate(&e));
+  int rc = EOFX_OK;
+  int64_t off = 0;
+  for (size_t c = 0; c < plan.chunks.size() && rc == EOFX_OK; ++c) {
+    const GwChunk& ch = plan.chunks[c];
+    const unsigned passes = (unsigned)((GW_T * P2a + 256 * GW_R - 1) / (256 * GW_R));
+    (void)hipEventRecord(evs[3 * c], ctx->stream);
+    hipLaunchKernelGGL(gw_cov_kernel, dim3((unsigned)ch.c.ntiles, passes), dim3(256), 0, ctx->stream, (const float*)m->X,
+                       m->p_pad, p, (const double*)geo_n, (const int64_t*)perm_n, n, (const double*)(geo_c + 3 * off),
+                       (const int64_t*)(perm_c + off), ch.count, (const int*)(rowptr + ch.off_tiles + (int64_t)c),
+                       (const int*)(cols + ch.off_cols), metric, kernel, bw, S);
+    if (hipGetLastError() != hipSuccess) rc = set_err(ctx, EOFX_ERR_HIP, "gw_cov_kernel launch failed");
+    // sorted plans: A in the chunk's sorted order, the eigensolver writes row perm_c[s] of the outputs
+    hipLaunchKernelGGL(gw_finalize_kernel, dim3((unsigned)ch.count), dim3(256), 0, ctx->stream, (const double*)S, p,
+                       (const int64_t*)(perm_c + off), plan.first, plan.sorted ? 1 : 0, A, tv_ext);
+    if (hipGetLastError() != hipSuccess) rc = set_err(ctx, EOFX_ERR_HIP, "gw_finalize_kernel launch failed");
+    (void)hipEventRecord(evs[3 * c + 1], ctx->stream);
+    if (comps) {
+      hipLaunchKernelGGL(gw_syev_kernel<float>, dim3((unsigned)ch.count), dim3(256), 0, ctx->stream, (const double*)A, p, k, 30,
+                         (const int64_t*)(plan.sorted ? perm_c + off : nullptr), ev, comps);
+      if (hipGetLastError() != hipSuccess) rc = set_err(ctx, EOFX_ERR_HIP, "gw_syev_kernel launch failed");
+    }
+    (void)hipEventRecord(evs[3 * c + 2], ctx->stream);
+    off += ch.count;
+  }
+  const hipError_t se = hipStreamSynchronize(ctx->stream);
+  for (size_t c = 0; c < plan.chunks.size(); ++c) {
+    float t0 = 0.f, t1 = 0.f;
+    if (rc == EOFX_OK && se == hipSuccess && hipEventElapsedTime(&t0, evs[3 * c], evs[3 * c + 1]) == hipSuccess &&
+        hipEventElapsedTime(&t1, evs[3 * c + 1], evs[3 * c + 2]) == hipSuccess) {
+      *us_cov += 1e3 * t0;
+      *us_eig += 1e3 * t1;
+    }
+  }
+  for (auto& e : evs) (void)hipEventDestroy(e);
+  if (se != hipSuccess && rc == EOFX_OK) rc = set_err(ctx, EOFX_ERR_HIP, "GWPCA: %s", hipGetErrorString(se));
+  return rc;
+}
+
+static void gw_stats(int64_t* stats, const GwPlan& plan, double us_tile, double us_cov, double us_eig, int64_t chunk) {
+  if (!stats) return;
+  stats[0] = plan.visited;
+  stats[1] = plan.possible;
+  stats[2] = (int64_t)plan.chunks.size();
+  stats[3] = plan.ctiles;
+  stats[4] = (int64_t)us_tile;
+  stats[5] = (int64_t)us_cov;
+  stats[6] = (int64_t)us_eig;
+  stats[7] = chunk;
+}
+
+}  // namespace
+
+extern "C" int eofx_gwpca_f64(eofx_ctx* ctx, const eofx_mat* m, const double* xy, int metric, int kernel, double bandwidth,
+                              int k, int64_t chunk, float* components, double* explained_variance, double* total_variance,
+                              int64_t* stats) {
+  CHK(gw_check(ctx, m, xy, metric, kernel, bandwidth));
+  if (k < 1 || k > m->p) return set_err(ctx, EOFX_ERR_ARG, "k must be in [1, p = %lld], got %d", (long long)m->p, k);
+  if (m->p > GW_EIG_PMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "eofx_gwpca_f64 solves p <= %d (p = %lld: eofx_gw_cov_f64 and a library eigensolver)",
+                   GW_EIG_PMAX, (long long)m->p);
+  if (!is_device_ptr(components) || !is_device_ptr(explained_variance) || !is_device_ptr(total_variance))
+    return set_err(ctx, EOFX_ERR_ARG, "components, explained_variance and total_variance must be device buffers");
+  ENTER(ctx);
+  const int64_t p = m->p, P2a = (p + 1) * (p + 2) / 2;
+  // chunks keep the packed moments and the dense covariances of a chunk within 256 MiB
+  if (chunk < 0) return set_err(ctx, EOFX_ERR_ARG, "chunk must be >= 0, got %lld", (long long)chunk);
+  if (chunk == 0) chunk = ((int64_t)256 << 20) / (8 * (P2a + p * p));
+  chunk = std::min(round_up(m->n, GW_T), std::max<int64_t>(GW_T, round_up(chunk, GW_T)));
+  const auto t0 = std::chrono::steady_clock::now();
+  GwPlan plan;
+  gw_plan(xy, m->n, 0, m->n, chunk, true, metric, kernel, bandwidth, plan);
+  const double us_tile = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  double us_cov = 0.0, us_eig = 0.0;
+  CHK(gw_run(ctx, m, plan, metric, kernel, bandwidth, nullptr, total_variance, k, components, explained_variance, &us_cov,
+             &us_eig));
+  gw_stats(stats, plan, us_tile, us_cov, us_eig, chunk);
+  return EOFX_OK;
+}
+
+extern "C" int eofx_gw_cov_f64(eofx_ctx* ctx, const eofx_mat* m, const double* xy, int metric, int kernel, double bandwidth,
+                               int64_t first, int64_t count, double* cov, double* total_variance, int64_t* stats) {
+  CHK(gw_check(ctx, m, xy, metric, kernel, bandwidth));
+  if (first < 0 || count < 1 || first + count > m->n) return set_err(ctx, EOFX_ERR_ARG, "location range out of bounds");
+  if (!is_device_ptr(cov) || !is_device_ptr(total_variance))
+    return set_err(ctx, EOFX_ERR_ARG, "cov and total_variance must be device buffers");
+  ENTER(ctx);
+  const auto t0 = std::chrono::steady_clock::now();
+  GwPlan plan;
+  gw_plan(xy, m->n, first, count, count, false, metric, kernel, bandwidth, plan);
+  const double us_tile = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  double us_cov = 0.0, us_eig = 0.0;
+  CHK(gw_run(ctx, m, plan, metric, kernel, bandwidth, cov, total_variance, 0, nullptr, nullptr, &us_cov, &us_eig));
+  gw_stats(stats, plan, us_tile, us_cov, us_eig, count);
+  return EOFX_OK;
+}
+
+extern "C" int eofx_batched_syev_f64(eofx_ctx* ctx, const double* A, int64_t batch, int p, int k, double* w, double* V) {
+  if (!ctx || !A || !w || !V || batch < 0) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (p < 1 || p > GW_EIG_PMAX) return set_err(ctx, EOFX_ERR_ARG, "p must be in [1, %d], got %d", GW_EIG_PMAX, p);
+  if (k < 1 || k > p) return set_err(ctx, EOFX_ERR_ARG, "k must be in [1, p = %d], got %d", p, k);
+  if (!is_device_ptr(A) || !is_device_ptr(w) || !is_device_ptr(V)) return set_err(ctx, EOFX_ERR_ARG, "A, w and V must be device buffers");
+  if (batch == 0) return EOFX_OK;
+  ENTER(ctx);
+  hipLaunchKernelGGL(gw_syev_kernel<double>, dim3((unsigned)batch), dim3(256), 0, ctx->stream, A, p, k, 30,
+                     (const int64_t*)nullptr, w, V);
+  KCHK();
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   return EOFX_OK;
 }

@@ -1268,3 +1268,99 @@ def hilbert_sumsq(ctx: Context, A: ResidentMatrix, padding="exp", decay_factor: 
     raise_for(ctx.lib.eofx_hilbert_sumsq_f64(ctx.handle, A.handle, int(padding == "exp"), float(decay_factor), C.byref(out)),
               ctx.handle)
     return float(out.value)
+
+
+# --------------------------------------------------------------------------- #
+# geographically weighted PCA (eofx_gwpca_f64 / eofx_gw_cov_f64 / eofx_batched_syev_f64, csrc/eofx_gw.hpp)   #
+# --------------------------------------------------------------------------- #
+GW_METRICS = {"euclidean": 0, "haversine": 1}
+GW_KERNELS = {"bisquare": 0, "gaussian": 1, "exponential": 2}
+GW_EIG_PMAX = 64          # the batched Jacobi solver's limit; wider local covariances go to torch.linalg.eigh
+GW_PMAX = 256             # the covariance kernel stages a neighbour tile of 16 x (p + 1) float64 in LDS
+GW_LIB_CHUNK_BYTES = 256 << 20
+
+
+def _gw_stats(st) -> dict:
+    return dict(tile_pairs_visited=int(st[0]), tile_pairs_total=int(st[1]), chunks=int(st[2]), tiles=int(st[3]),
+                ms_tiling=st[4] / 1e3, ms_covariance=st[5] / 1e3, ms_eigen=st[6] / 1e3, chunk=int(st[7]))
+
+
+def batched_syev(ctx: Context, A, k: int):
+    """A [batch, p, p] float64 device tensor (upper triangle read, p <= 64) -> (w [batch, k], V [batch, p, k]) float64 device
+    tensors: the k largest eigenpairs, descending, clamped at 0, signed by the reference's deterministic rule"""
+    torch = _torch()
+    batch, p = A.shape[0], A.shape[1]
+    A = A.to(torch.float64).contiguous()
+    w = torch.empty((batch, int(k)), dtype=torch.float64, device=A.device)
+    V = torch.empty((batch, p, int(k)), dtype=torch.float64, device=A.device)
+    raise_for(ctx.lib.eofx_batched_syev_f64(ctx.handle, ptr(A), batch, p, int(k), ptr(w), ptr(V)), ctx.handle)
+    return w, V
+
+
+def gw_cov(ctx: Context, mat: ResidentMatrix, xy: np.ndarray, metric: str, kernel: str, bandwidth: float, first: int,
+           count: int):
+    """-> (local covariances C_i / W_i [count, p, p], total variances [count]) of locations [first, first + count), float64
+    device tensors, and the tiling statistics"""
+    torch = _torch()
+    xy = np.ascontiguousarray(xy, dtype=np.float64)
+    cov = torch.empty((int(count), mat.p, mat.p), dtype=torch.float64, device=f"cuda:{ctx.device}")
+    tv = torch.empty(int(count), dtype=torch.float64, device=cov.device)
+    st = (C.c_int64 * 8)()
+    raise_for(ctx.lib.eofx_gw_cov_f64(ctx.handle, mat.handle, xy.ctypes.data, GW_METRICS[metric], GW_KERNELS[kernel],
+                                      float(bandwidth), int(first), int(count), ptr(cov), ptr(tv), st), ctx.handle)
+    return cov, tv, _gw_stats(st)
+
+
+def gwpca(ctx: Context, mat: ResidentMatrix, xy: np.ndarray, k: int, bandwidth: float, metric: str = "haversine",
+          kernel: str = "bisquare", chunk: int | None = None):
+    """Local PCAs of every location (row) of the resident matrix; xy [n, 2] = (lon, lat) in degrees or (x, y).
+    -> (components [n, p, k] float32, explained_variance [n, k], total_variance [n], stats) as host arrays.
+    p <= 64: one engine call (eofx_gwpca_f64).  Wider: eofx_gw_cov_f64 per chunk of locations, then the library's batched
+    float64 eigensolver (torch.linalg.eigh), the same ordering, clamping and sign rule as the Jacobi kernel.  `chunk`:
+    locations per chunk (None: the automatic size, whose buffers stay within 256 MiB)."""
+    torch = _torch()
+    n, p, k = mat.n, mat.p, int(k)
+    xy = np.ascontiguousarray(xy, dtype=np.float64)
+    if xy.shape != (n, 2):
+        raise ValueError(f"xy must have shape ({n}, 2), got {xy.shape}")
+    dev = f"cuda:{ctx.device}"
+    if p <= GW_EIG_PMAX:
+        comps = torch.empty((n, p, k), dtype=torch.float32, device=dev)
+        ev = torch.empty((n, k), dtype=torch.float64, device=dev)
+        tv = torch.empty(n, dtype=torch.float64, device=dev)
+        st = (C.c_int64 * 8)()
+        raise_for(ctx.lib.eofx_gwpca_f64(ctx.handle, mat.handle, xy.ctypes.data, GW_METRICS[metric], GW_KERNELS[kernel],
+                                         float(bandwidth), k, int(chunk or 0), ptr(comps), ptr(ev), ptr(tv), st), ctx.handle)
+        return comps.cpu().numpy(), ev.cpu().numpy(), tv.cpu().numpy(), _gw_stats(st)
+    if not 1 <= k <= p:
+        raise ValueError(f"n_modes must be in [1, {p}], got {k}")
+    comps = np.empty((n, p, k), np.float32)
+    ev = np.empty((n, k))
+    tv = np.empty(n)
+    chunk = int(chunk) if chunk else max(1, GW_LIB_CHUNK_BYTES // (16 * p * p))
+    agg = None
+    for c0 in range(0, n, chunk):
+        cnt = min(chunk, n - c0)
+        cov, t, st = gw_cov(ctx, mat, xy, metric, kernel, bandwidth, c0, cnt)
+        torch.cuda.synchronize(ctx.device)
+        t_eig = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t_eig[0].record()
+        w, V = torch.linalg.eigh(cov)                                    # ascending
+        del cov
+        order = torch.sort(w, dim=1, descending=True, stable=True).indices[:, :k]
+        w = torch.gather(w, 1, order).clamp_min(0.0)
+        V = torch.gather(V, 2, order[:, None, :].expand(cnt, p, k))
+        sign = torch.where(V.amax(dim=1).abs() >= V.amin(dim=1).abs(), 1.0, -1.0)
+        V = V * sign[:, None, :]
+        t_eig[1].record()
+        comps[c0:c0 + cnt] = V.to(torch.float32).cpu().numpy()
+        ev[c0:c0 + cnt] = w.cpu().numpy()
+        tv[c0:c0 + cnt] = t.cpu().numpy()
+        st["ms_eigen"] = t_eig[0].elapsed_time(t_eig[1])
+        if agg is None:
+            agg = dict(st, tile_pairs_total=0, tile_pairs_visited=0, tiles=0, chunks=0, ms_tiling=0.0, ms_covariance=0.0,
+                       ms_eigen=0.0, chunk=chunk)
+        for key in ("tile_pairs_total", "tile_pairs_visited", "tiles", "ms_tiling", "ms_covariance", "ms_eigen"):
+            agg[key] += st[key]
+        agg["chunks"] += 1
+    return comps, ev, tv, agg
