@@ -477,6 +477,32 @@ int eofx_gw_cov_f64(eofx_ctx *ctx, const eofx_mat *m, const double *xy, int metr
  * w [batch x k] the k largest eigenvalues (descending, index-stable ties, clamped at 0), V [batch x p x k] orthonormal
  * eigenvectors with the sign rule above.  Cyclic Jacobi in LDS, one workgroup per matrix.                            */
 int eofx_batched_syev_f64(eofx_ctx *ctx, const double *A, int64_t batch, int p, int k, double *w, double *V);
+/* ---- sparse PCA by variable projection (xeofs/single/_numpy/_sparse_pca.py:383-563, csrc/eofx_spca.hpp) -----------------
+ * The solver runs on V [p x l] (device, row-major, orthonormal columns) and D [l] (host, descending) of the thin SVD
+ * C = U diag(D) V^T of the matrix it is given.  B starts as V[:, :k]; alpha and beta are the caller's values (scaled by
+ * D[0]^2 here, as the reference does).  Each iteration is one streaming pass over V and B plus one single-workgroup step on
+ * l x k matrices; the host reads the finished flag once per batch of 16 iterations.  check != 0: stop after the first
+ * iteration t > 0 with |obj[t-1] - obj[t]| / obj[t] < tol; check == 0: exactly max_iter iterations.  Outputs: B [p x k]
+ * (device, the sparse components), Qa [l x k] (host, A = V Qa), dtilde [k] (host, the singular values of V^T Z of the last
+ * iteration, descending), objective [max_iter] (host, may be NULL; the first *n_iter entries are written), *n_iter.
+ * Float64, no atomics, fixed summation order.  EOFX_ERR_ARG for k > p, k > l, a non-finite or negative alpha / beta / tol,
+ * max_iter < 1, an unknown regularizer, D not finite or D[0] == 0; EOFX_ERR_SHAPE for k > 64 or l > 128.               */
+#define EOFX_SPCA_L1 0
+#define EOFX_SPCA_L0 1
+int eofx_spca_loop_f64(eofx_ctx *ctx, const double *V, int64_t p, int l, const double *D, int k, double alpha, double beta,
+                       int regularizer, int max_iter, double tol, int check, double *B, double *Qa, double *dtilde,
+                       double *objective, int *n_iter);
+/* out [a x b] (device) = X^T Y over `rows` rows of X [rows x a] and Y [rows x b] (device, row strides ldx, ldy; a stride of
+ * 0 repeats one row), summed in a fixed order (per-workgroup partials, then a fixed tree)                             */
+int eofx_spca_gram_f64(eofx_ctx *ctx, const double *X, int64_t ldx, int a, const double *Y, int64_t ldy, int b, int64_t rows,
+                       double *out);
+/* Y [rows x b] = X [rows x a] M [a x b] (device; row strides ldx, ldy; M row-major, a <= 4096)                          */
+int eofx_spca_rowmul_f64(eofx_ctx *ctx, const double *X, int64_t ldx, int a, const double *M, int b, int64_t rows, double *Y,
+                         int64_t ldy);
+/* out[e] = prox(X[e] + s Y[e], kappa) for e < count (device; Y may be NULL; out may alias X): soft threshold (l1) or
+ * hard threshold, zero where x^2 < 2 kappa (l0)                                                                       */
+int eofx_spca_prox_f64(eofx_ctx *ctx, const double *X, const double *Y, double s, int64_t count, int regularizer, double kappa,
+                       double *out);
 /* Gram matrix of a resident matrix (float32, device): side 0 = sample space G[n_pad x n_pad] = X X^T,
  * side 1 = feature space G[p_pad x p_pad] = X^T X (rows/columns beyond n / p are zero).  Used for
  * (a) the total squared covariance sum(|X^T Y|^2) = <X X^T, Y Y^T> (cross/cpcca.py:991-1000) when X and

@@ -113,6 +113,11 @@ SIGNATURES = {
     "eofx_gwpca_f64": (_int, [_vp, _vp, _vp, _int, _int, C.c_double, _int, _i64, _vp, _vp, _vp, _pi64]),
     "eofx_gw_cov_f64": (_int, [_vp, _vp, _vp, _int, _int, C.c_double, _i64, _i64, _vp, _vp, _pi64]),
     "eofx_batched_syev_f64": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
+    "eofx_spca_loop_f64": (_int, [_vp, _vp, _i64, _int, _vp, _int, C.c_double, C.c_double, _int, _int, C.c_double, _int, _vp,
+                                  _vp, _vp, _vp, C.POINTER(_int)]),
+    "eofx_spca_gram_f64": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _int, _i64, _vp]),
+    "eofx_spca_rowmul_f64": (_int, [_vp, _vp, _i64, _int, _vp, _int, _i64, _vp, _i64]),
+    "eofx_spca_prox_f64": (_int, [_vp, _vp, _vp, C.c_double, _i64, _int, C.c_double, _vp]),
     "eofx_resample_f32": (_int, [_vp, _vp, _vp, _i64, _int, C.POINTER(_vp), _vp, _pd]),
     "eofx_mat_gram_f32": (_int, [_vp, _vp, _int, _vp]),
     "eofx_mat_cross_gram_f32": (_int, [_vp, _vp, _vp, _int, _vp]),

@@ -10,6 +10,7 @@
 #include "eofx_hosteig.hpp"
 #include "eofx_lag.hpp"
 #include "eofx_gw.hpp"
+#include "eofx_spca.hpp"
 #ifndef EOFX_AXB_DMA_DEFAULT
 #define EOFX_AXB_DMA_DEFAULT 1
 #endif
@@ -6616,5 +6617,138 @@ extern "C" int eofx_batched_syev_f64(eofx_ctx* ctx, const double* A, int64_t bat
                      (const int64_t*)nullptr, w, V);
   KCHK();
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  return EOFX_OK;
+}
+
+// ---- sparse PCA by variable projection (csrc/eofx_spca.hpp) -----------------------------------------------------------
+namespace {
+
+constexpr int SPCA_BATCH = 16;      // iterations enqueued between two reads of the finished flag
+
+// workgroups of a streaming pass over `rows` rows whose partials hold `entries` doubles each: about 128 rows per
+// workgroup, at most SPCA_GMAX, the partials within 32 MiB (a function of the shape alone: results never depend on the device)
+static int spca_grid(int64_t rows, int64_t entries) {
+  const int64_t g = std::min<int64_t>(SPCA_GMAX, std::max<int64_t>(1, (rows + 127) / 128));
+  const int64_t cap = std::max<int64_t>(1, ((int64_t)4 << 20) / std::max<int64_t>(1, entries));
+  return (int)std::max<int64_t>(1, std::min(g, cap));
+}
+
+}  // namespace
+
+extern "C" int eofx_spca_loop_f64(eofx_ctx* ctx, const double* V, int64_t p, int l, const double* D, int k, double alpha,
+                                  double beta, int regularizer, int max_iter, double tol, int check, double* B, double* Qa,
+                                  double* dtilde, double* objective, int* n_iter) {
+  if (!ctx || !V || !D || !B || !Qa || !dtilde || !n_iter) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (p < 1 || l < 1 || k < 1) return set_err(ctx, EOFX_ERR_ARG, "p, l and k must be >= 1 (p = %lld, l = %d, k = %d)", (long long)p, l, k);
+  if (k > p) return set_err(ctx, EOFX_ERR_ARG, "n_components must be less than the number of columns of X (%lld), got %d", (long long)p, k);
+  if (k > l) return set_err(ctx, EOFX_ERR_ARG, "k = %d exceeds the %d columns of V", k, l);
+  if (k > SPCA_KMAX || l > SPCA_LMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the sparse PCA kernels take k <= %d and l <= %d (k = %d, l = %d)", SPCA_KMAX, SPCA_LMAX, k, l);
+  if (!std::isfinite(alpha) || !std::isfinite(beta) || !std::isfinite(tol) || alpha < 0.0 || beta < 0.0 || tol < 0.0)
+    return set_err(ctx, EOFX_ERR_ARG, "alpha, beta and tol must be finite and >= 0 (%g, %g, %g)", alpha, beta, tol);
+  if (max_iter < 1) return set_err(ctx, EOFX_ERR_ARG, "max_iter must be >= 1, got %d", max_iter);
+  if (regularizer != EOFX_SPCA_L1 && regularizer != EOFX_SPCA_L0) return set_err(ctx, EOFX_ERR_ARG, "unknown regularizer %d", regularizer);
+  for (int i = 0; i < l; ++i)
+    if (!std::isfinite(D[i]) || D[i] < 0.0) return set_err(ctx, EOFX_ERR_ARG, "singular value %d is %g", i, D[i]);
+  if (!(D[0] > 0.0)) return set_err(ctx, EOFX_ERR_ARG, "the matrix is zero (largest singular value 0)");
+  if (!is_device_ptr(V) || !is_device_ptr(B)) return set_err(ctx, EOFX_ERR_ARG, "V and B must be device buffers");
+  ENTER(ctx);
+  // compute_spca's scaling (_sparse_pca.py:506-510)
+  const double d0 = D[0] * D[0], a2 = alpha * d0, b2 = beta * d0, nu = 1.0 / (d0 + b2), kappa = nu * a2;
+  const int lk = l * k;
+  const int G = spca_grid(p, lk + 2);
+  const size_t nst = (size_t)3 * lk + 2 + k + max_iter;
+  CHK(arena_reserve(ctx, ((size_t)(lk + 2) * G + nst + l) * 8 + 64 + 4 * 256));
+  ArenaScope scope(ctx);
+  ARENA(double, part, (size_t)(lk + 2) * G);
+  ARENA(double, st, nst);
+  ARENA(double, d2, l);
+  ARENA(int, ctl, 4);
+  std::vector<double> D2h((size_t)l);
+  for (int i = 0; i < l; ++i) D2h[(size_t)i] = D[i] * D[i];
+  HIPCHK(hipMemcpyAsync(d2, D2h.data(), (size_t)l * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(ctl, 0, 4 * sizeof(int), ctx->stream));
+  HIPCHK(hipMemsetAsync(st, 0, nst * 8, ctx->stream));
+  HIPCHK(hipMemcpy2DAsync(B, (size_t)k * 8, V, (size_t)l * 8, (size_t)k * 8, (size_t)p, hipMemcpyDeviceToDevice, ctx->stream));
+  const size_t lds = ((size_t)lk + (size_t)SPCA_R * (l + k) + 512) * 8;
+  if (lds > (64u << 10)) (void)hipFuncSetAttribute((const void*)spca_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  double* W = st + 2 * lk + 2;
+  auto update = [&](int apply) {
+    hipLaunchKernelGGL(spca_update_kernel, dim3((unsigned)G), dim3(256), lds, ctx->stream, V, p, l, k, B, (const double*)W, nu,
+                       b2, kappa, regularizer, apply, (const int*)ctl, part);
+    hipLaunchKernelGGL(spca_sum_kernel, dim3((unsigned)(lk + 2)), dim3(256), 0, ctx->stream, (const double*)part, G,
+                       (const int*)ctl, st);
+  };
+  auto step = [&](int t) {
+    hipLaunchKernelGGL(spca_step_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)d2, l, k, a2, b2, t, max_iter,
+                       check ? 1 : 0, tol, st, ctl);
+  };
+  update(0);
+  step(0);
+  KCHK();
+  int t = 1, h[4] = {0, 0, 0, 0};
+  while (true) {
+    for (int b = 0; b < SPCA_BATCH && t <= max_iter; ++b, ++t) {
+      update(1);
+      step(t);
+    }
+    KCHK();
+    HIPCHK(hipMemcpyAsync(h, ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (h[SPCA_CTL_DONE]) break;
+    if (t > max_iter) return set_err(ctx, EOFX_ERR_HIP, "internal: sparse PCA loop did not finish after %d iterations", max_iter);
+  }
+  const int iters = h[SPCA_CTL_ITERS];
+  HIPCHK(hipMemcpyAsync(Qa, st + lk + 2, (size_t)lk * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(dtilde, st + 3 * lk + 2, (size_t)k * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (objective) HIPCHK(hipMemcpyAsync(objective, st + 3 * lk + 2 + k, (size_t)iters * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *n_iter = iters;
+  return EOFX_OK;
+}
+
+extern "C" int eofx_spca_gram_f64(eofx_ctx* ctx, const double* X, int64_t ldx, int a, const double* Y, int64_t ldy, int b,
+                                  int64_t rows, double* out) {
+  if (!ctx || !X || !Y || !out || a < 1 || b < 1 || rows < 1 || ldx < 0 || ldy < 0 || (ldx > 0 && ldx < a) || (ldy > 0 && ldy < b))
+    return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (!is_device_ptr(X) || !is_device_ptr(Y) || !is_device_ptr(out)) return set_err(ctx, EOFX_ERR_ARG, "X, Y and out must be device buffers");
+  ENTER(ctx);
+  const int64_t ab = (int64_t)a * b;
+  const int G = spca_grid(rows, ab);
+  CHK(arena_reserve(ctx, (size_t)ab * G * 8 + 256));
+  ArenaScope scope(ctx);
+  ARENA(double, part, (size_t)ab * G);
+  const unsigned ny = (unsigned)((ab + 256 * SPCA_GRAM_E - 1) / (256 * SPCA_GRAM_E));
+  hipLaunchKernelGGL(spca_gram_kernel, dim3((unsigned)G, ny), dim3(256), 0, ctx->stream, X, ldx, a, Y, ldy, b, rows, part);
+  KCHK();
+  hipLaunchKernelGGL(spca_sum_kernel, dim3((unsigned)ab), dim3(256), 0, ctx->stream, (const double*)part, G, (const int*)nullptr, out);
+  KCHK();
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return EOFX_OK;
+}
+
+extern "C" int eofx_spca_rowmul_f64(eofx_ctx* ctx, const double* X, int64_t ldx, int a, const double* M, int b, int64_t rows,
+                                    double* Y, int64_t ldy) {
+  if (!ctx || !X || !M || !Y || a < 1 || a > 4096 || b < 1 || rows < 0 || ldx < a || ldy < b) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (!is_device_ptr(X) || !is_device_ptr(M) || !is_device_ptr(Y)) return set_err(ctx, EOFX_ERR_ARG, "X, M and Y must be device buffers");
+  if (rows == 0) return EOFX_OK;
+  ENTER(ctx);
+  const int64_t count = rows * b;
+  hipLaunchKernelGGL(spca_rowmul_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, X, ldx, a, M, b, rows, Y, ldy);
+  KCHK();
+  return EOFX_OK;
+}
+
+extern "C" int eofx_spca_prox_f64(eofx_ctx* ctx, const double* X, const double* Y, double s, int64_t count, int regularizer,
+                                  double kappa, double* out) {
+  if (!ctx || !X || !out || count < 0) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (regularizer != EOFX_SPCA_L1 && regularizer != EOFX_SPCA_L0) return set_err(ctx, EOFX_ERR_ARG, "unknown regularizer %d", regularizer);
+  if (!std::isfinite(s) || !std::isfinite(kappa) || kappa < 0.0) return set_err(ctx, EOFX_ERR_ARG, "s and kappa must be finite, kappa >= 0");
+  if (!is_device_ptr(X) || !is_device_ptr(out) || (Y && !is_device_ptr(Y))) return set_err(ctx, EOFX_ERR_ARG, "X, Y and out must be device buffers");
+  if (count == 0) return EOFX_OK;
+  ENTER(ctx);
+  hipLaunchKernelGGL(spca_prox_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, X, Y, s, count, regularizer,
+                     kappa, out);
+  KCHK();
   return EOFX_OK;
 }
