@@ -46,16 +46,17 @@ def test_fused_plan_and_lean_rules():
 
 
 def test_complex_deflated_norms_formula():
-    """`ComplexCPCCA._deflated_norms`: ||(Sx - r1 b1^H)^H (Sy - r2 b2^H)||_F^2 per mode from inner products of n-vectors,
-    against the dense expression (the residual form of the squared covariance fraction, cpcca.py:418-512)."""
-    from xeofs_amd.cross.complex_mca import ComplexCPCCA
+    """`cross._surface._deflated_norms` (the two analysis sides as `HostSide` objects): ||(Sx - r1 b1^H)^H (Sy - r2 b2^H)||_F^2
+    per mode from inner products of n-vectors, against the dense expression (the residual form of the squared covariance
+    fraction, cpcca.py:418-512)."""
+    from xeofs_amd.cross._surface import HostSide, _deflated_norms
 
     rng = np.random.default_rng(0)
     c = lambda *s: rng.standard_normal(s) + 1j * rng.standard_normal(s)
     for n, m1, m2, k in ((50, 7, 9, 3), (31, 12, 4, 4)):
         Sx, Sy, R1, R2, B1, B2 = c(n, m1), c(n, m2), c(n, k), c(n, k), c(m1, k), c(m2, k)
         M = Sx.conj().T @ Sy
-        got = ComplexCPCCA._deflated_norms(Sx, Sy, R1, R2, B1, B2, (np.abs(M) ** 2).sum())
+        got = _deflated_norms(HostSide(Sx), HostSide(Sy), R1, R2, B1, B2, (np.abs(M) ** 2).sum())
         ref = [np.linalg.norm((Sx - np.outer(R1[:, j], B1[:, j].conj())).conj().T @ (Sy - np.outer(R2[:, j], B2[:, j].conj()))) ** 2
                for j in range(k)]
         assert np.allclose(got, ref, rtol=1e-10)
@@ -63,7 +64,7 @@ def test_complex_deflated_norms_formula():
     Sx, Sy = rng.standard_normal((40, 6)), rng.standard_normal((40, 5))
     U, s, Vt = np.linalg.svd(Sx.T @ Sy, full_matrices=False)
     R1, R2 = Sx @ U[:, :2], Sy @ Vt[:2].T
-    got = ComplexCPCCA._deflated_norms(Sx, Sy, R1, R2, U[:, :2], Vt[:2].T, (s ** 2).sum())
+    got = _deflated_norms(HostSide(Sx), HostSide(Sy), R1, R2, U[:, :2], Vt[:2].T, (s ** 2).sum())
     assert np.allclose(got, (s ** 2).sum() - s[:2] ** 2, rtol=1e-10)       # alpha = 1: deflation removes sigma_i^2
 
 

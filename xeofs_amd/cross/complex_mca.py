@@ -17,6 +17,8 @@ hundreds, and the m_x x m_y complex cross-covariance matrix is decomposed exactl
 scipy's svds(lobpcg): same singular values / subspaces to its tolerance, vectors up to a unit phase per mode).
 Without PCA (`use_pca=False`) the fields themselves are the analysis matrices: supported while they are small enough to
 decompose densely (n * p <= MAX_DENSE); beyond that use the default PCA route.
+Accessors and diagnostics are those of `cross/_surface.py` on the host analysis matrices (`HostSide`); the rotator shares
+`cpcca_rotator.CrossRotator` with the real one.
 """
 
 from __future__ import annotations
@@ -27,18 +29,16 @@ import warnings
 
 import numpy as np
 
-from .. import __version__, engine, labelled
+from .. import __version__, engine, labelled, rotation
 from .._deferred import Deferred
 from ..cpca import ComplexResidentPCA
 from ..linalg.decomposer import sanity_check_n_modes
 from ..pca import ResidentPCA
-from ..preprocessing import Preprocessor
+from ..preprocessing import Preprocessor, parse_scores
+from ._surface import ComplexPairSurface, HostSide, ModelSurface, _pair, covariance_fraction_CD95, warn_ill_conditioned
+from .cpcca_rotator import CrossRotator
 
 MAX_DENSE = 50_000_000      # elements of a field decomposed without PCA pre-reduction
-
-
-def _pair(v):
-    return list(v) if isinstance(v, (list, tuple)) else [v, v]
 
 
 def _hermitian_power(C, power):
@@ -68,6 +68,13 @@ def _part32(vals, imag):
     with ThreadPoolExecutor(nt) as ex:
         list(ex.map(block, range(nt)))
     return out
+
+
+def _re_im(Z):
+    """Re and Im of a labelled (complex) array as two labelled float32 arrays"""
+    vals, dims, coords, name, attrs = labelled.unpack(Z)
+    vals = np.asarray(vals)
+    return [labelled.pack(_part32(vals, imag), dims, coords, name, attrs, Z) for imag in (False, True)]
 
 
 def _leading_svd_device(C, k, device, block=24, max_iter=80, tol=1e-10):
@@ -121,11 +128,13 @@ class _Field:
         self.parts = ()
 
 
-class ComplexCPCCA(Deferred):
+class ComplexCPCCA(ComplexPairSurface, ModelSurface, Deferred):
     """Drop-in for xeofs.cross.ComplexCPCCA (cross/cpcca.py:1023-1326)."""
 
     _model_name = "Complex CPCCA"
     _hilbert = False
+    _suffix = ("_X", "_Y")
+    covariance_fraction_CD95 = covariance_fraction_CD95
 
     def __init__(self, n_modes: int = 2, alpha=0.2, standardize=False, use_coslat=False, check_nans=True, use_pca=True,
                  n_pca_modes=0.999, pca_init_rank_reduction=0.3, compute: bool = True, sample_name: str = "sample",
@@ -165,14 +174,10 @@ class ComplexCPCCA(Deferred):
 
     def _complex_parts(self, i, Z, dim, weights):
         """preprocess Re and Im of a complex input with the same centring / weights (as `ComplexEOF`)"""
-        vals, dims, coords, name, attrs = labelled.unpack(Z)
-        if not np.iscomplexobj(vals):
+        if not np.iscomplexobj(labelled.unpack(Z)[0]):
             warnings.warn("Expected complex-valued data but found real-valued data. For Hilbert model, use corresponding "
                           "`Hilbert` class.")
-        vals = np.asarray(vals)
-        re = labelled.pack(_part32(vals, False), dims, coords, name, attrs, Z)
-        im = labelled.pack(_part32(vals, True),
-                           dims, coords, name, attrs, Z)
+        re, im = _re_im(Z)
         pr, pi = self.pre_re[i], self.pre_im[i]
         std_c = None
         if self._params["standardize"][i]:
@@ -225,10 +230,7 @@ class ComplexCPCCA(Deferred):
             S = fld.S
             if not (1.0 - self.alpha[i]) < np.finfo(np.float64).eps:     # whitener.py:46-60: alpha >= 1 is the identity
                 n_, m_ = S.shape
-                if n_ < m_:                                          # whitener.py:101-104
-                    warnings.warn(f"The number of samples ({n_}) is smaller than the number of features ({m_}), leading to "
-                                  "an ill-conditioned problem. This may cause unstable results. Consider using PCA to "
-                                  "reduce dimensionality and stabilize the problem by setting `use_pca=True`.")
+                warn_ill_conditioned(n_, m_)
                 T = _hermitian_power(np.ascontiguousarray(S.conj().T) @ S / n_, (self.alpha[i] - 1) / 2)
                 try:
                     Tinv = np.linalg.inv(T)
@@ -269,141 +271,15 @@ class ComplexCPCCA(Deferred):
                          total_squared_covariance=float((np.abs(Cu) ** 2).sum()), norm1=norm1, norm2=norm2)
         return self
 
-    # ------------------------------------------------------------------ accessors
-    def _pre(self, which):
-        return self.pre_re[which - 1]
+    # ------------------------------------------------------------------ the shared surface (cross/_surface.py) reads these
+    def _pres(self):
+        return self.pre_re
 
-    def _mode_array(self, values, name):
-        k = len(values)
-        return labelled.pack(np.asarray(values), ("mode",), {"mode": np.arange(1, k + 1)}, name, dict(self.attrs),
-                             self.pre_re[0].fields[0].like)
+    def _sides(self):
+        return [HostSide(self._Su[i], self.Tinv[i]) for i in (0, 1)]
 
-    def _components(self, normalized):
-        c1, c2 = self.data["components1"], self.data["components2"]
-        if not normalized:                                       # cpcca.py:308-316
-            c1, c2 = c1 * self.data["norm1"].astype(np.float32), c2 * self.data["norm2"].astype(np.float32)
-        return c1, c2
-
-    def _scores(self, normalized):
-        s1, s2 = self.data["scores1"], self.data["scores2"]
-        if normalized:                                           # cpcca.py:318-329
-            s1, s2 = s1 / self.data["norm1"], s2 / self.data["norm2"]
-        return s1, s2
-
-    def _wrap_components(self, c1, c2, name):
-        return (self.pre_re[0].inverse_transform_components(c1, name + "_X", self.attrs),
-                self.pre_re[1].inverse_transform_components(c2, name + "_Y", self.attrs))
-
-    def _wrap_scores(self, s1, s2, name):
-        return (self.pre_re[0].inverse_transform_scores(s1, name + "_X", self.attrs),
-                self.pre_re[1].inverse_transform_scores(s2, name + "_Y", self.attrs))
-
-    def components(self, normalized: bool = True):
-        return self._wrap_components(*self._components(normalized), "components")
-
-    def scores(self, normalized: bool = False):
-        return self._wrap_scores(*self._scores(normalized), "scores")
-
-    def components_amplitude(self, normalized: bool = True):
-        c1, c2 = self._components(normalized)
-        return self._wrap_components(np.abs(c1), np.abs(c2), "components_amplitude")
-
-    def components_phase(self, normalized: bool = True):
-        c1, c2 = self._components(normalized)
-        return self._wrap_components(np.angle(c1), np.angle(c2), "components_phase")
-
-    def scores_amplitude(self, normalized: bool = False):
-        s1, s2 = self._scores(normalized)
-        return self._wrap_scores(np.abs(s1), np.abs(s2), "scores_amplitude")
-
-    def scores_phase(self, normalized: bool = False):
-        s1, s2 = self._scores(normalized)
-        return self._wrap_scores(np.angle(s1), np.angle(s2), "scores_phase")
-
-    def singular_values(self):
-        return self._mode_array(self.data["singular_values"], "singular_values")
-
-    def squared_covariance(self):
-        return self._mode_array(self.data["squared_covariance"], "squared_covariance")
-
-    def total_squared_covariance(self):
-        return self.data["total_squared_covariance"]
-
-    # ---- diagnostics of cpcca.py:342-575 in complex algebra, in the n x m analysis space (a PCA basis has orthonormal
-    # columns, so Frobenius norms of feature-space residuals equal those of their PC-space coordinates)
-    def _rank_one_terms(self):
-        """mode j: the whitened reconstruction r_j q_j^H un-whitened (whitener.inverse_transform_data: . @ T^-1) is
-        r_j b_j^H with b_j = T^-H q_j"""
-        B = [self.data[f"Q{i + 1}"] if self.Tinv[i] is None else self.Tinv[i].conj().T @ self.data[f"Q{i + 1}"] for i in (0, 1)]
-        return self.data["scores1"], self.data["scores2"], B[0], B[1]
-
-    @staticmethod
-    def _deflated_norms(Sx, Sy, R1, R2, B1, B2, M2):
-        """||(Sx - r1 b1^H)^H (Sy - r2 b2^H)||_F^2 per mode without forming Sx^H Sy: with M = Sx^H Sy the product is
-        D = M - g1 b2^H - b1 g2^H + c b1 b2^H (g1 = Sx^H r2, g2 = Sy^H r1, c = r1^H r2) and ||D||^2 expands into inner
-        products of n-vectors (M2 = ||M||_F^2)."""
-        dot = lambda a, b: (a.conj() * b).sum(axis=0)            # column-wise <a, b>
-        G1, G2 = Sx.conj().T @ R2, Sy.conj().T @ R1              # (m1 x k), (m2 x k)
-        a1, a2b = Sx @ B1, Sy @ B2
-        a1g, a2g = Sx @ G1, Sy @ G2
-        c = dot(R1, R2)
-        nb1, nb2, ng1, ng2 = dot(B1, B1).real, dot(B2, B2).real, dot(G1, G1).real, dot(G2, G2).real
-        return (M2 + nb1 * ng2 + ng1 * nb2 + np.abs(c) ** 2 * nb1 * nb2
-                - 2 * dot(a2g, a1).real - 2 * dot(a2b, a1g).real + 2 * (c * dot(a2b, a1)).real
-                + 2 * (dot(B1, G1) * dot(B2, G2)).real - 2 * (c * nb1 * dot(B2, G2)).real - 2 * (c * dot(G1, B1) * nb2).real)
-
-    def squared_covariance_fraction(self):
-        """cpcca.py:418-512: SCF_i = 1 - ||d_X,i^H d_Y,i||_F^2 / ||X^H Y||_F^2 with d the residual of the un-whitened data
-        after its reconstruction by mode i (clipped at 0) -- for every alpha; with alpha = 1 it equals sigma_i^2 / TSC."""
-        Sx, Sy = self._Su
-        n = Sx.shape[0]
-        R1, R2, B1, B2 = self._rank_one_terms()
-        M2 = self.data["total_squared_covariance"] * (n - 1) ** 2
-        scf = 1 - self._deflated_norms(Sx, Sy, R1, R2, B1, B2, M2) / M2
-        return self._mode_array(np.where(scf < 0, 0, scf), "squared_covariance_fraction")
-
-    def _fve_self(self, i):
-        """cpcca.py:514-639: 1 - ||S - r b^H||_F^2 / ||S||_F^2 per mode"""
-        S = self._Su[i]
-        R, B = self._rank_one_terms()[i], self._rank_one_terms()[2 + i]
-        tot = (np.abs(S) ** 2).sum()
-        res = tot - 2 * ((S @ B).conj() * R).sum(axis=0).real + (np.abs(R) ** 2).sum(0) * (np.abs(B) ** 2).sum(0)
-        return 1 - res / tot
-
-    def fraction_variance_X_explained_by_X(self):
-        return self._mode_array(self._fve_self(0), "fraction_variance_X_explained_by_X")
-
-    def fraction_variance_Y_explained_by_Y(self):
-        return self._mode_array(self._fve_self(1), "fraction_variance_Y_explained_by_Y")
-
-    @staticmethod
-    def _corr(A, B):
-        """cpcca.py:910-1022 method='correlation': columns divided by numpy's (real, population) std of a complex array,
-        then A^H B / (n - 1)"""
-        return (A / A.std(axis=0)).conj().T @ (B / B.std(axis=0)) / (A.shape[0] - 1)
-
-    def cross_correlation_coefficients(self):
-        return self._mode_array(np.diag(self._corr(self.data["scores1"], self.data["scores2"])), "cross_correlation_coefficients")
-
-    def _mode_matrix(self, M, name):
-        k = M.shape[0]
-        return labelled.pack(M, ("mode_x", "mode_y"), {"mode_x": np.arange(1, k + 1), "mode_y": np.arange(1, k + 1)}, name,
-                             dict(self.attrs), self.pre_re[0].fields[0].like)
-
-    def correlation_coefficients_X(self):
-        return self._mode_matrix(self._corr(self.data["scores1"], self.data["scores1"]), "correlation_coefficients_X")
-
-    def correlation_coefficients_Y(self):
-        return self._mode_matrix(self._corr(self.data["scores2"], self.data["scores2"]), "correlation_coefficients_Y")
-
-    def covariance_fraction_CD95(self):
-        """mca.py:127-189"""
-        s = self.data["singular_values"]
-        cf = s[0] / np.cumsum(s)
-        if len(s) > 1 and (cf[-2] - cf[-1]) > 0.001:
-            warnings.warn("The curent estimate of CF is sensitive to the number of modes retained. Please increase "
-                          "`n_modes` for a better estimate.")
-        return self._mode_array(s / s.sum(), "covariance_fraction")
+    def _analysis_vectors(self, i):
+        return self.data[f"Q{i + 1}"]
 
     # ------------------------------------------------------------------ transform / inverse
     def transform(self, X=None, Y=None, normalized: bool = False):
@@ -414,11 +290,7 @@ class ComplexCPCCA(Deferred):
         for i, Z in enumerate((X, Y)):
             if Z is None:
                 continue
-            vals, dims, coords, name, attrs = labelled.unpack(Z)
-            vals = np.asarray(vals)
-            re = labelled.pack(_part32(vals, False), dims, coords, name, attrs, Z)
-            im = labelled.pack(_part32(vals, True),
-                               dims, coords, name, attrs, Z)
+            re, im = _re_im(Z)
             An, fields, vs = self.pre_re[i].transform(re)
             Bn, _, _ = self.pre_im[i].transform(im)
             S = self.field[i].project(An, Bn)
@@ -432,7 +304,6 @@ class ComplexCPCCA(Deferred):
             out.append(self.pre_re[i].inverse_transform_scores(S, "scores_" + "XY"[i], self.attrs, fields, vs))
         return out[0] if len(out) == 1 else out
 
-
     def inverse_transform(self, X=None, Y=None):
         """base_model_cross_set.py:376-425 + cpcca.py:254-271: scores (with a 'mode' dimension) back to the fields --
         S conj(Q)^T in the analysis space, un-whitened, out of the PCA basis, then every part un-scaled by its own
@@ -444,25 +315,9 @@ class ComplexCPCCA(Deferred):
             if S is None:
                 continue
             pre = self.pre_re[i]
-            vals, dims, coords, _, _ = labelled.unpack(S)
-            if "mode" not in dims:
-                vals, dims = vals[None], ("mode",) + tuple(dims)
-                coords = dict(coords, mode=np.array([1]))
-            modes = np.asarray(coords["mode"]).astype(int)
-            order = [dims.index("mode")] + [j for j, d in enumerate(dims) if d != "mode"]
-            Sm = np.transpose(vals, order).reshape(len(modes), -1).T.astype(np.complex128)      # (n', k')
-            vs = ~np.isnan(Sm).all(axis=1)
-            Za = Sm[vs] @ self.data[f"Q{i + 1}"][:, modes - 1].conj().T                          # analysis space (n' x m)
+            Sm, modes, vs, fields = parse_scores(S, pre.fields, np.complex128)                   # (n', k')
+            Za = Sm @ self.data[f"Q{i + 1}"][:, modes - 1].conj().T                              # analysis space (n' x m)
             rec = np.asarray(self._back(i, np.ascontiguousarray(Za.conj().T))).conj().T         # (V T^-H Za^H)^H = Za T^-1 V^H
-            f0 = pre.fields[0]
-            sample_shape = tuple(vals.shape[dims.index(d)] for d in f0.sample_dims)
-            fields = []
-            for f in pre.fields:
-                g = object.__new__(type(f))
-                g.__dict__.update(f.__dict__)
-                g.sample_shape = sample_shape
-                g.coords = dict(f.coords, **{d: coords[d] for d in f.sample_dims if d in coords})
-                fields.append(g)
             re = pre.inverse_transform_data(rec.real, "reconstructed_data", fields, vs)
             if self._hilbert:      # un-scale only: inverse(Im) - inverse(0)
                 im = pre.inverse_transform_data(rec.imag, "reconstructed_data", fields, vs)
@@ -525,7 +380,7 @@ class HilbertCPCCA(ComplexCPCCA):
         raise NotImplementedError("Hilbert models do not support the transform method.")
 
 
-class ComplexCPCCARotator:
+class ComplexCPCCARotator(ComplexPairSurface, CrossRotator):
     """Drop-in for xeofs.cross.ComplexCPCCARotator (cross/cpcca_rotator.py:472-534 over :20-420): Varimax
     (power = 1) / Promax rotation of a fitted complex cross model.  The stacked complex feature-space loadings [Qx; Qy] sqrt(s)
     are rotated on the device as one [Re | Im] panel (`rotation.cpromax_panel`); their images in the
@@ -533,168 +388,58 @@ class ComplexCPCCARotator:
 
     _model_name = "Rotated Complex CPCCA"
     _hilbert = False
+    _score_dtype = np.complex64
 
-    def __init__(self, n_modes: int = 10, power: int = 1, max_iter: int | None = None, rtol: float = 1e-8,
-                 compute: bool = True):
-        if max_iter is None:
-            max_iter = 1000 if compute else 100
-        self._params = dict(n_modes=n_modes, power=power, max_iter=max_iter, rtol=rtol, compute=compute)
-        self.attrs = {"model": self._model_name}
-        self.attrs.update(self._params)
-        self.attrs.update({"software": "xeofs_amd", "version": __version__,
-                           "date": datetime.datetime.now().strftime("%Y-%m-%d %H:%M:%S")})
-        self.data, self.model_data = {}, {}
-        self.sorted = False
+    _rotate = staticmethod(rotation.cpromax_panel)
 
-    def get_params(self):
-        return dict(self._params)
-
-    def _rot_mat_inv_trans(self, R):
-        return np.linalg.inv(R).conj().T if self._params["power"] > 1 else R
-
-    def fit(self, model):
-        """cpcca_rotator.py:122-263 (+ the post-compute sort by squared covariance) with complex loadings"""
-        getattr(model, "compute", lambda: None)()      # a deferred fit runs now: ctx / preprocessor / data are read below
-        from .. import rotation
-
-        torch = engine._torch()
-        self.model = model
-        self.ctx = model.ctx
+    def _adopt(self, model):
         self.pre = model.pre_re
-        k = int(self._params["n_modes"])
-        s = np.asarray(model.data["singular_values"], dtype=np.float64)[:k]
-        k = s.size
-        scaling = np.sqrt(s)
-        C1 = np.asarray(model.data["components1"])[:, :k]
-        C2 = np.asarray(model.data["components2"])[:, :k]
-        p1 = C1.shape[0]
-        Xrot, ptot, k, rot_matrix, phi = rotation.cpromax_panel(self.ctx, np.concatenate([C1, C2], axis=0),
-                                                                power=self._params["power"], max_iter=self._params["max_iter"],
-                                                                rtol=self._params["rtol"], col_scale=scaling)
-        Qr = [model.data[f"Q{i + 1}"][:, :k] * scaling @ rot_matrix for i in range(2)]
-        norm1, norm2 = np.linalg.norm(Qr[0], axis=0), np.linalg.norm(Qr[1], axis=0)
-        sqcov = (norm1 * norm2) ** 2
-        idx = np.argsort(sqcov)[::-1]
-        RinvT = self._rot_mat_inv_trans(rot_matrix)
-        sc1 = (np.asarray(model.data["scores1"])[:, :k] / scaling) @ RinvT * norm1
-        sc2 = (np.asarray(model.data["scores2"])[:, :k] / scaling) @ RinvT * norm2
-        # sign rule on the stacked rotated loadings (xarray_utils.py:273-301; numpy's lexicographic complex max / min)
+        return {}
+
+    def _pres(self):
+        return self.pre
+
+    @staticmethod
+    def _model_vectors(model, i):
+        return model.data[f"Q{i + 1}"]
+
+    def _panel_sign(self, Xrot, ptot, k):
+        """numpy's lexicographic complex max / min on the [Re | Im] panel"""
+        torch = engine._torch()
         CH = Xrot.shape[1] // 2
         amax, amin = engine.panel_colargminmax(self.ctx, Xrot, ptot)
         cols = torch.arange(k, device=Xrot.device)
         pick = lambda ix: (Xrot[ix[:k], cols].double().cpu().numpy(), Xrot[ix[:k], cols + CH].double().cpu().numpy())
         (mr, mi), (nr, ni) = pick(amax), pick(amin)
-        sign = np.where(np.hypot(mr, mi) >= np.hypot(nr, ni), 1.0, -1.0)
-        F = []
-        for norm, lo, hi in ((norm1, 0, p1), (norm2, p1, ptot)):
-            M = np.zeros((k, k), dtype=complex)
-            M[idx, np.arange(k)] = sign[idx] / norm[idx]
-            blk = engine.panel_matmul(self.ctx, Xrot[lo:], rotation._dev(rotation._cembed(M, CH), Xrot))[:hi - lo].cpu().numpy()
-            c = np.empty((hi - lo, k), np.complex64)
-            c.real, c.imag = blk[:, :k], blk[:, CH:CH + k]
-            F.append(c)
-        del Xrot
-        self.model_data = dict(singular_values=np.asarray(model.data["singular_values"]), components1=C1, components2=C2)
-        self.data = dict(
-            components1=F[0], components2=F[1],
-            scores1=(sc1 * sign)[:, idx].astype(np.complex64), scores2=(sc2 * sign)[:, idx].astype(np.complex64),
-            squared_covariance=sqcov[idx], total_squared_covariance=model.data["total_squared_covariance"],
-            idx_modes_sorted=idx, norm1=norm1[idx], norm2=norm2[idx], rotation_matrix=rot_matrix, phi_matrix=phi,
-            modes_sign=sign[idx],
-        )
-        self.sorted = True
-        return self
+        return np.where(np.hypot(mr, mi) >= np.hypot(nr, ni), 1.0, -1.0)
 
-    # ------------------------------------------------------------------ transform (cpcca_rotator.py:282-372)
+    def _export(self, Xrot, lo, hi, idx, w):
+        CH, k = Xrot.shape[1] // 2, idx.size
+        M = np.zeros((k, k), dtype=complex)
+        M[idx, np.arange(k)] = w
+        blk = engine.panel_matmul(self.ctx, Xrot[lo:], rotation._dev(rotation._cembed(M, CH), Xrot))[:hi - lo].cpu().numpy()
+        c = np.empty((hi - lo, k), np.complex64)
+        c.real, c.imag = blk[:, :k], blk[:, CH:CH + k]
+        return c
+
+    def _unrotated_scores(self, which, Z, k):
+        un = self.model.transform(**{"XY"[which - 1]: Z})          # unrotated scores: data . back-projected components
+        vals, dims, coords, _, _ = labelled.unpack(un)
+        S = np.asarray(vals).reshape(vals.shape[0], -1).T[:, :k]
+        ok = ~np.isnan(S).all(axis=1)
+
+        def label(proj, name):
+            full = np.full(S.shape, np.nan, dtype=complex)
+            full[ok] = proj
+            return labelled.pack(full.T.reshape((k,) + vals.shape[1:]), dims, dict(coords, mode=np.arange(1, k + 1)), name,
+                                 dict(self.attrs), un)
+
+        return S[ok], label
+
     def transform(self, X=None, Y=None, normalized: bool = False):
         if self._hilbert:
             raise NotImplementedError("Hilbert models do not support the transform method.")
-        if X is None and Y is None:
-            raise ValueError("No data provided. Please provide X and/or Y.")
-        k = self.data["norm1"].size
-        RinvT = self._rot_mat_inv_trans(self.data["rotation_matrix"])
-        scaling = np.sqrt(np.asarray(self.model_data["singular_values"], dtype=np.float64)[:k])
-        outs = []
-        for which, Z in ((1, X), (2, Y)):
-            if Z is None:
-                continue
-            un = self.model.transform(**{"XY"[which - 1]: Z})          # unrotated scores: data . back-projected components
-            vals, dims, coords, _, _ = labelled.unpack(un)
-            kk = vals.shape[0]
-            S = np.asarray(vals).reshape(kk, -1).T[:, :k]
-            ok = ~np.isnan(S).all(axis=1)
-            proj = np.full(S.shape, np.nan, dtype=complex)
-            proj[ok] = (S[ok] / scaling) @ RinvT
-            proj = proj[:, self.data["idx_modes_sorted"]] * self.data["modes_sign"]
-            if not normalized:
-                proj = proj * self.data[f"norm{which}"]
-            coords = dict(coords, mode=np.arange(1, k + 1))
-            outs.append(labelled.pack(proj.T.reshape((k,) + vals.shape[1:]), dims, coords, f"scores{which}", dict(self.attrs), un))
-        return outs[0] if len(outs) == 1 else outs
-
-    # ------------------------------------------------------------------ accessors
-    def _components(self, normalized):
-        q1, q2 = self.data["components1"], self.data["components2"]
-        if not normalized:
-            q1, q2 = q1 * self.data["norm1"].astype(np.float32), q2 * self.data["norm2"].astype(np.float32)
-        return q1, q2
-
-    def _scores(self, normalized):
-        s1, s2 = self.data["scores1"], self.data["scores2"]
-        if normalized:
-            s1, s2 = s1 / self.data["norm1"].astype(np.float32), s2 / self.data["norm2"].astype(np.float32)
-        return s1, s2
-
-    def _wc(self, c1, c2, name):
-        return (self.pre[0].inverse_transform_components(c1, name + "1", self.attrs),
-                self.pre[1].inverse_transform_components(c2, name + "2", self.attrs))
-
-    def _ws(self, s1, s2, name):
-        return (self.pre[0].inverse_transform_scores(s1, name + "1", self.attrs),
-                self.pre[1].inverse_transform_scores(s2, name + "2", self.attrs))
-
-    def components(self, normalized: bool = True):
-        return self._wc(*self._components(normalized), "components")
-
-    def scores(self, normalized: bool = False):
-        return self._ws(*self._scores(normalized), "scores")
-
-    def components_amplitude(self, normalized: bool = True):
-        c1, c2 = self._components(normalized)
-        return self._wc(np.abs(c1), np.abs(c2), "components_amplitude")
-
-    def components_phase(self, normalized: bool = True):
-        c1, c2 = self._components(normalized)
-        return self._wc(np.angle(c1), np.angle(c2), "components_phase")
-
-    def scores_amplitude(self, normalized: bool = False):
-        s1, s2 = self._scores(normalized)
-        return self._ws(np.abs(s1), np.abs(s2), "scores_amplitude")
-
-    def scores_phase(self, normalized: bool = False):
-        s1, s2 = self._scores(normalized)
-        return self._ws(np.angle(s1), np.angle(s2), "scores_phase")
-
-    def _mode_array(self, values, name):
-        k = len(values)
-        return labelled.pack(np.asarray(values), ("mode",), {"mode": np.arange(1, k + 1)}, name, dict(self.attrs),
-                             self.pre[0].fields[0].like)
-
-    def squared_covariance(self):
-        return self._mode_array(self.data["squared_covariance"], "squared_covariance")
-
-    def squared_covariance_fraction(self):
-        return self._mode_array(self.data["squared_covariance"] / self.data["total_squared_covariance"],
-                                "squared_covariance_fraction")
-
-    def rotation_matrix(self):
-        return self.data["rotation_matrix"]
-
-    def phi_matrix(self):
-        return self.data["phi_matrix"]
-
-    def fit_transform(self, *a, **k):
-        raise NotImplementedError("The fit_transform method is not implemented for the rotator classes.")
+        return super().transform(X, Y, normalized)
 
 
 class HilbertCPCCARotator(ComplexCPCCARotator):

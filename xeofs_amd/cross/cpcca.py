@@ -10,13 +10,13 @@ matrices (`eofx_crosscov_rsvd_f32`; C is never formed) -> singular vectors taken
 
 With alpha = 1 and use_pca = False the analysis runs directly on the resident feature-space matrices
 (the SURVEY.md §8 hot path, row R14/R15).  The diagnostics of Swenson (2015) are evaluated through rank-one
-algebra on panel products (A B, A^T R) instead of per-mode reconstructions of the full fields.
+algebra on panel products (A B, A^T R) instead of per-mode reconstructions of the full fields; they and the labelled
+accessors are shared with the complex models (`cross/_surface.py`), which reach the fields through `_Side`.
 """
 
 from __future__ import annotations
 
 import datetime
-import warnings
 
 import numpy as np
 
@@ -24,13 +24,10 @@ from .. import __version__, engine, labelled
 from .._deferred import Deferred
 from ..linalg.decomposer import MAX_SKETCH, sanity_check_n_modes
 from ..pca import ResidentPCA
-from ..preprocessing import Preprocessor
+from ..preprocessing import Preprocessor, parse_scores
+from ._surface import ModelSurface, _pair, covariance_fraction_CD95, warn_ill_conditioned
 
 MAX_DENSE_WHITEN = 8192     # whitening without PCA forms the p x p covariance (as the reference does)
-
-
-def _pair(v):
-    return list(v) if isinstance(v, (list, tuple)) else [v, v]
 
 
 def fractional_matrix_power(C, power):
@@ -185,7 +182,7 @@ class _Side:
                             f"alpha < 1 without PCA needs the {mat.p} x {mat.p} feature covariance; use use_pca=True")
                     self._Zhost = mat.download().astype(np.float64)
                 n, m = self._Zhost.shape
-                self._warn_ill_conditioned(n, m)
+                warn_ill_conditioned(n, m)
                 Cm = self._Zhost.T @ self._Zhost / n
                 self.T = fractional_matrix_power(Cm, (alpha - 1) / 2)
                 try:
@@ -209,13 +206,6 @@ class _Side:
         else:
             self.work = mat if self._Zhost is None else engine.from_dense(ctx, self._Zhost.astype(np.float32))
 
-    @staticmethod
-    def _warn_ill_conditioned(n, m):
-        if n < m:                                               # whitener.py:101-104
-            warnings.warn(f"The number of samples ({n}) is smaller than the number of features ({m}), leading to "
-                          "an ill-conditioned problem. This may cause unstable results. Consider using PCA to "
-                          "reduce dimensionality and stabilize the problem by setting `use_pca=True`.")
-
     def _whiten_on_device(self, alpha):
         """Whitener.fit / transform (preprocessing/whitener.py:86-133) on the resident PC scores: C = Z^T Z / n through the
         float64 Gram kernel, T = C^((alpha - 1) / 2) from its eigen-decomposition (linalg/_numpy/_utils.py:6-33: eigenvalues
@@ -225,7 +215,7 @@ class _Side:
         ctx = self.ctx
         Zd = self._Zdev
         n, m = Zd.shape
-        self._warn_ill_conditioned(n, m)
+        warn_ill_conditioned(n, m)
         Lm = (m + 31) // 32 * 32
         Zp = torch.zeros((self.mat.n_pad, Lm), dtype=torch.float32, device=Zd.device)
         Zp[:n, :m] = Zd
@@ -338,7 +328,7 @@ class _Side:
         self.work = None
 
 
-class CPCCA(Deferred):
+class CPCCA(ModelSurface, Deferred):
     _model_name = "Continuum Power CCA"
 
     def __init__(self, n_modes: int = 2, alpha=0.2, standardize=False, use_coslat=False, use_pca=True,
@@ -521,20 +511,15 @@ class CPCCA(Deferred):
             m.free()
         return t
 
-    # ------------------------------------------------------------------ accessors (base_model_cross_set.py:465-523)
-    def components(self, normalized: bool = True):
-        q1, q2 = self.data["components1"], self.data["components2"]
-        if not normalized:
-            q1, q2 = q1 * self.data["norm1"].astype(q1.dtype), q2 * self.data["norm2"].astype(q2.dtype)
-        return (self.preprocessor1.inverse_transform_components(q1, "components1", self.attrs),
-                self.preprocessor2.inverse_transform_components(q2, "components2", self.attrs))
+    # ------------------------------------------------------------------ the shared surface (cross/_surface.py) reads these
+    def _pres(self):
+        return self.preprocessor1, self.preprocessor2
 
-    def scores(self, normalized: bool = False):
-        s1, s2 = self.data["scores1"], self.data["scores2"]
-        if normalized:
-            s1, s2 = s1 / self.data["norm1"].astype(s1.dtype), s2 / self.data["norm2"].astype(s2.dtype)
-        return (self.preprocessor1.inverse_transform_scores(s1, "scores1", self.attrs),
-                self.preprocessor2.inverse_transform_scores(s2, "scores2", self.attrs))
+    def _sides(self):
+        return self.side
+
+    def _analysis_vectors(self, i):
+        return self._q[i]
 
     def _project(self, which, Z):
         """preprocess -> pca -> whitener -> singular vectors; returns (scores n' x k, fields, valid samples)"""
@@ -584,108 +569,11 @@ class CPCCA(Deferred):
             if S is None:
                 continue
             pre = self.preprocessor1 if which == 1 else self.preprocessor2
-            vals, dims, coords, _, _ = labelled.unpack(S)
-            if "mode" not in dims:
-                vals, dims = vals[None], ("mode",) + tuple(dims)
-                coords = dict(coords, mode=np.array([1]))
-            modes = np.asarray(coords["mode"]).astype(int)
-            order = [dims.index("mode")] + [i for i, d in enumerate(dims) if d != "mode"]
-            Sm = np.transpose(vals, order).reshape(len(modes), -1).T.astype(np.float64)     # (n', k')
-            vs = ~np.isnan(Sm).all(axis=1)
-            Za = Sm[vs] @ self._q[which - 1][:, modes - 1].T                                  # analysis space
+            Sm, modes, vs, fields = parse_scores(S, pre.fields, np.float64)                   # (n', k')
+            Za = Sm @ self._q[which - 1][:, modes - 1].T                                      # analysis space
             rec = self.side[which - 1].data_back(Za)
-            f0 = pre.fields[0]
-            sample_shape = tuple(vals.shape[dims.index(d)] for d in f0.sample_dims)
-            fields = []
-            for f in pre.fields:
-                g = object.__new__(type(f))
-                g.__dict__.update(f.__dict__)
-                g.sample_shape = sample_shape
-                g.coords = dict(f.coords, **{d: coords[d] for d in f.sample_dims if d in coords})
-                fields.append(g)
             outs.append(pre.inverse_transform_data(rec, "reconstructed_data", fields, vs))
         return outs[0] if len(outs) == 1 else outs
-
-    def _mode_array(self, values, name):
-        k = len(values)
-        return labelled.pack(np.asarray(values), ("mode",), {"mode": np.arange(1, k + 1)}, name, dict(self.attrs),
-                             self.preprocessor1.fields[0].like)
-
-    def singular_values(self):
-        return self._mode_array(self.data["singular_values"], "singular_values")
-
-    def squared_covariance(self):
-        return self._mode_array(self.data["squared_covariance"], "squared_covariance")
-
-    def total_squared_covariance(self):
-        return self.data["total_squared_covariance"]
-
-    # ------------------------------------------------------------------ diagnostics (cpcca.py:330-640)
-    @staticmethod
-    def _corr(A, B):
-        """cpcca.py:910-985 method='correlation': columns scaled by their population std, cross-products / (n-1)"""
-        A, B = A.astype(np.float64), B.astype(np.float64)
-        return (A / A.std(axis=0)).T @ (B / B.std(axis=0)) / (A.shape[0] - 1)
-
-    def cross_correlation_coefficients(self):
-        return self._mode_array(np.diag(self._corr(self.data["scores1"], self.data["scores2"])),
-                                "cross_correlation_coefficients")
-
-    def _mode_matrix(self, M, name):
-        k = M.shape[0]
-        return labelled.pack(M, ("mode_x", "mode_y"), {"mode_x": np.arange(1, k + 1), "mode_y": np.arange(1, k + 1)}, name,
-                             dict(self.attrs), self.preprocessor1.fields[0].like)
-
-    def correlation_coefficients_X(self):
-        return self._mode_matrix(self._corr(self.data["scores1"], self.data["scores1"]), "correlation_coefficients_X")
-
-    def correlation_coefficients_Y(self):
-        return self._mode_matrix(self._corr(self.data["scores2"], self.data["scores2"]), "correlation_coefficients_Y")
-
-    def _rank_one_terms(self):
-        """per-mode pieces of the residuals d_i = A_i - r_i b_i^T (b_i = Tinv_i^T q_i), all modes batched into
-        panel products: g1 = A1^T R2, g2 = A2^T R1, a_i = A_i b_i, ..."""
-        R1, R2 = self.data["scores1"].astype(np.float64), self.data["scores2"].astype(np.float64)
-        B = []
-        for i in range(2):
-            Q = self._q[i]
-            B.append(Q if self.side[i].Tinv is None else self.side[i].Tinv.T @ Q)
-        return R1, R2, B[0], B[1]
-
-    def squared_covariance_fraction(self):
-        """cpcca.py:418-497: 1 - ||d_X^T d_Y||_F^2 / ||X^T Y||_F^2 per mode (clipped at 0).
-
-        D = M - b1 g2^T - g1 b2^T + c b1 b2^T with M = A1^T A2; ||D||^2 is expanded into inner products of
-        n-vectors A_i x so that M (and any per-mode reconstruction of the fields) is never formed."""
-        sx, sy = self.side
-        n = sx.n
-        R1, R2, B1, B2 = self._rank_one_terms()
-        G1, G2 = sx.A_tmul(R2), sy.A_tmul(R1)                        # (m1 x k), (m2 x k)
-        a1, a2b = sx.A_mul(B1), sy.A_mul(B2)                         # A1 b1, A2 b2   (n x k)
-        a2g, a1g = sy.A_mul(G2), sx.A_mul(G1)                        # A2 g2, A1 g1   (n x k)
-        c = (R1 * R2).sum(axis=0)
-        nb1, nb2 = (B1 * B1).sum(0), (B2 * B2).sum(0)
-        ng1, ng2 = (G1 * G1).sum(0), (G2 * G2).sum(0)
-        M2 = self.data["total_squared_covariance"] * (n - 1) ** 2
-        b1g1, g2b2 = (B1 * G1).sum(0), (G2 * B2).sum(0)
-        D2 = (M2 + nb1 * ng2 + ng1 * nb2 + c ** 2 * nb1 * nb2 - 2 * (a1 * a2g).sum(0) - 2 * (a1g * a2b).sum(0)
-              + 2 * c * (a1 * a2b).sum(0) + 2 * b1g1 * g2b2 - 2 * c * nb1 * g2b2 - 2 * c * b1g1 * nb2)
-        scf = 1 - D2 / M2
-        return self._mode_array(np.where(scf < 0, 0, scf), "squared_covariance_fraction")
-
-    def _fve_self(self, i):
-        sd = self.side[i]
-        R = self.data[f"scores{i + 1}"].astype(np.float64)
-        B = self._rank_one_terms()[2 + i]
-        tot = sd.A_sumsq()
-        res = tot - 2 * (R * sd.A_mul(B)).sum(0) + (R * R).sum(0) * (B * B).sum(0)
-        return 1 - res / tot
-
-    def fraction_variance_X_explained_by_X(self):
-        return self._mode_array(self._fve_self(0), "fraction_variance_X_explained_by_X")
-
-    def fraction_variance_Y_explained_by_Y(self):
-        return self._mode_array(self._fve_self(1), "fraction_variance_Y_explained_by_Y")
 
     def fraction_variance_Y_explained_by_X(self):
         """cpcca.py:563-640: like the SCF but with (X^T X)^(-1/2) in front (needs X in a reduced space)."""
@@ -768,53 +656,34 @@ def holm_sidak(p):
     return out
 
 
-class MCA(CPCCA):
+class _FixedAlpha(CPCCA):
+    """The children with a hard-coded alpha (mca.py:120-123): the CPCCA constructor without it."""
+    _alpha = None
+
+    def __init__(self, n_modes: int = 2, standardize=False, use_coslat=False, check_nans=True, use_pca=True,
+                 n_pca_modes=0.999, pca_init_rank_reduction=0.3, compute: bool = True, sample_name: str = "sample",
+                 feature_name="feature", solver: str = "auto", random_state=None, solver_kwargs: dict = {}):
+        super().__init__(n_modes=n_modes, alpha=self._alpha, standardize=standardize, use_coslat=use_coslat,
+                         use_pca=use_pca, n_pca_modes=n_pca_modes, pca_init_rank_reduction=pca_init_rank_reduction,
+                         check_nans=check_nans, compute=compute, sample_name=sample_name, feature_name=feature_name,
+                         solver=solver, random_state=random_state, solver_kwargs=solver_kwargs)
+        self._params.pop("alpha")
+
+
+class MCA(_FixedAlpha):
     """cross/mca.py:20-123: CPCCA with alpha = [1, 1]."""
     _model_name = "Maximum Covariance Analysis"
-
-    def __init__(self, n_modes: int = 2, standardize=False, use_coslat=False, check_nans=True, use_pca=True,
-                 n_pca_modes=0.999, pca_init_rank_reduction=0.3, compute: bool = True, sample_name: str = "sample",
-                 feature_name="feature", solver: str = "auto", random_state=None, solver_kwargs: dict = {}):
-        super().__init__(n_modes=n_modes, alpha=[1.0, 1.0], standardize=standardize, use_coslat=use_coslat,
-                         use_pca=use_pca, n_pca_modes=n_pca_modes, pca_init_rank_reduction=pca_init_rank_reduction,
-                         check_nans=check_nans, compute=compute, sample_name=sample_name, feature_name=feature_name,
-                         solver=solver, random_state=random_state, solver_kwargs=solver_kwargs)
-        self._params.pop("alpha")
-
-    def covariance_fraction_CD95(self):
-        """mca.py:127-189 (Cheng & Dunkerton 1995): CF_i = sigma_i / sum_j sigma_j over the retained modes, with the
-        reference's warning when the estimate still moves by more than 1e-3 with the last mode."""
-        s = np.asarray(self.data["singular_values"], dtype=np.float64)
-        cf = s[0] / np.cumsum(s)
-        if len(s) > 1 and (cf[-2] - cf[-1]) > 0.001:
-            warnings.warn("The curent estimate of CF is sensitive to the number of modes retained. Please increase "
-                          "`n_modes` for a better estimate.")
-        return self._mode_array(s / s.sum(), "covariance_fraction")
+    _alpha = [1.0, 1.0]
+    covariance_fraction_CD95 = covariance_fraction_CD95
 
 
-class CCA(CPCCA):
+class CCA(_FixedAlpha):
     """cross/cca.py: CPCCA with alpha = [0, 0]."""
     _model_name = "Canonical Correlation Analysis"
-
-    def __init__(self, n_modes: int = 2, standardize=False, use_coslat=False, check_nans=True, use_pca=True,
-                 n_pca_modes=0.999, pca_init_rank_reduction=0.3, compute: bool = True, sample_name: str = "sample",
-                 feature_name="feature", solver: str = "auto", random_state=None, solver_kwargs: dict = {}):
-        super().__init__(n_modes=n_modes, alpha=[0.0, 0.0], standardize=standardize, use_coslat=use_coslat,
-                         use_pca=use_pca, n_pca_modes=n_pca_modes, pca_init_rank_reduction=pca_init_rank_reduction,
-                         check_nans=check_nans, compute=compute, sample_name=sample_name, feature_name=feature_name,
-                         solver=solver, random_state=random_state, solver_kwargs=solver_kwargs)
-        self._params.pop("alpha")
+    _alpha = [0.0, 0.0]
 
 
-class RDA(CPCCA):
+class RDA(_FixedAlpha):
     """cross/rda.py: CPCCA with alpha = [0, 1]."""
     _model_name = "Redundancy Analysis"
-
-    def __init__(self, n_modes: int = 2, standardize=False, use_coslat=False, check_nans=True, use_pca=True,
-                 n_pca_modes=0.999, pca_init_rank_reduction=0.3, compute: bool = True, sample_name: str = "sample",
-                 feature_name="feature", solver: str = "auto", random_state=None, solver_kwargs: dict = {}):
-        super().__init__(n_modes=n_modes, alpha=[0.0, 1.0], standardize=standardize, use_coslat=use_coslat,
-                         use_pca=use_pca, n_pca_modes=n_pca_modes, pca_init_rank_reduction=pca_init_rank_reduction,
-                         check_nans=check_nans, compute=compute, sample_name=sample_name, feature_name=feature_name,
-                         solver=solver, random_state=random_state, solver_kwargs=solver_kwargs)
-        self._params.pop("alpha")
+    _alpha = [0.0, 1.0]

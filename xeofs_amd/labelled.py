@@ -153,6 +153,18 @@ def pack(values, dims, coords, name, attrs, like):
     return DataArray(values, dims, coords, name, attrs)
 
 
+def mode_array(values, name, attrs, like):
+    """a per-mode vector as a labelled array over `mode` = 1..k"""
+    k = len(values)
+    return pack(np.asarray(values), ("mode",), {"mode": np.arange(1, k + 1)}, name, dict(attrs), like)
+
+
+def mode_matrix(M, name, attrs, like):
+    """a k x k matrix over (`mode_x`, `mode_y`)"""
+    k = M.shape[0]
+    return pack(M, ("mode_x", "mode_y"), {"mode_x": np.arange(1, k + 1), "mode_y": np.arange(1, k + 1)}, name, dict(attrs), like)
+
+
 def concat(objs, dim, coord):
     """Stack equally shaped arrays along a new leading dimension `dim` (xr.concat(..., dim=dim) +
     assign_coords); a list of lists (multi-field outputs) is stacked field by field."""

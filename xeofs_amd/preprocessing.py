@@ -61,6 +61,32 @@ class _Field:
         return np.broadcast_to(w.reshape(shape), self.feature_shape).reshape(-1)
 
 
+def parse_scores(scores, fields, dtype, scalar_mode=False):
+    """Scores handed to an `inverse_transform` (base_model_single_set.py:205-286, base_model_cross_set.py:376-425) ->
+    (S [n', k'] of the valid samples as `dtype`, mode numbers, valid-sample mask, `fields` relabelled with the scores' sample
+    coordinates).  Scores without a 'mode' dimension are one mode: the one a scalar 'mode' coordinate names when
+    `scalar_mode` ("Handle scalar mode in xr.dot", line 276), else mode 1."""
+    vals, dims, coords, _, _ = labelled.unpack(scores)
+    dims = tuple(dims)
+    if "mode" not in dims:
+        m = np.asarray(coords.get("mode", 1) if scalar_mode else 1).reshape(-1)[:1]
+        vals, dims = np.asarray(vals)[None], ("mode",) + dims
+        coords = dict(coords, mode=m)
+    modes = np.asarray(coords["mode"]).astype(int).reshape(-1)
+    order = [dims.index("mode")] + [i for i, d in enumerate(dims) if d != "mode"]
+    S = np.transpose(vals, order).reshape(len(modes), -1).T.astype(dtype)            # (n_samples, k')
+    vs = ~np.isnan(S).all(axis=1)
+    sample_shape = tuple(vals.shape[dims.index(d)] for d in fields[0].sample_dims)
+    relabelled = []
+    for f in fields:
+        g = object.__new__(type(f))
+        g.__dict__.update(f.__dict__)
+        g.sample_shape = sample_shape
+        g.coords = dict(f.coords, **{d: coords[d] for d in f.sample_dims if d in coords})
+        relabelled.append(g)
+    return S[vs], modes, vs, relabelled
+
+
 class Preprocessor:
     def __init__(self, center=True, standardize=False, use_coslat=False, check_nans=True, ctx=None, in_place=False,
                  masked_ok=False):

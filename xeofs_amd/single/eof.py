@@ -14,7 +14,7 @@ import numpy as np
 from .. import __version__, engine, labelled
 from .._deferred import Deferred
 from ..linalg.decomposer import Decomposer
-from ..preprocessing import Preprocessor
+from ..preprocessing import Preprocessor, parse_scores
 
 
 # Iteration rule of the complex models when `solver_kwargs` names none.  The reference's complex branch is a CONVERGED solver
@@ -129,28 +129,10 @@ class EOF(Deferred):
     def _parse_scores(self, scores, normalized, dtype):
         """base_model_single_set.py:205-286: scores with a (possibly scalar) 'mode' coordinate -> (S [n', k'] of the valid
         samples, mode numbers, valid-sample mask, the fields relabelled with the scores' sample coordinates)."""
-        vals, dims, coords, _, _ = labelled.unpack(scores)
-        dims = tuple(dims)
-        if "mode" not in dims:          # a single selected mode: "Handle scalar mode in xr.dot" (line 276)
-            m = np.asarray(coords.get("mode", 1)).reshape(-1)[:1]
-            vals, dims = np.asarray(vals)[None], ("mode",) + dims
-            coords = dict(coords, mode=m)
-        modes = np.asarray(coords["mode"]).astype(int).reshape(-1)
-        order = [dims.index("mode")] + [i for i, d in enumerate(dims) if d != "mode"]
-        S = np.transpose(vals, order).reshape(len(modes), -1).T            # (n_samples, k')
-        vs = ~np.isnan(S).all(axis=1)
-        S = np.ascontiguousarray(S[vs], dtype=dtype)
+        S, modes, vs, fields = parse_scores(scores, self.preprocessor.fields, dtype, scalar_mode=True)
+        S = np.ascontiguousarray(S)
         if normalized:
             S = S * self.data["norms"][modes - 1].astype(S.real.dtype)
-        f0 = self.preprocessor.fields[0]
-        sample_shape = tuple(vals.shape[dims.index(d)] for d in f0.sample_dims)
-        fields = []
-        for f in self.preprocessor.fields:
-            g = object.__new__(type(f))
-            g.__dict__.update(f.__dict__)
-            g.sample_shape = sample_shape
-            g.coords = dict(f.coords, **{d: coords[d] for d in f.sample_dims if d in coords})
-            fields.append(g)
         return S, modes, vs, fields
 
     def inverse_transform(self, scores, normalized: bool = False):
@@ -175,9 +157,7 @@ class EOF(Deferred):
         return self.preprocessor.inverse_transform_scores(S, "scores", self.attrs)
 
     def _mode_array(self, values, name):
-        k = len(values)
-        return labelled.pack(np.asarray(values), ("mode",), {"mode": np.arange(1, k + 1)}, name, dict(self.attrs),
-                             self.preprocessor.fields[0].like)
+        return labelled.mode_array(values, name, self.attrs, self.preprocessor.fields[0].like)
 
     def singular_values(self):
         return self._mode_array(self.data["norms"], "norms")
