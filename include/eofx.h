@@ -379,13 +379,15 @@ int eofx_panel_rinv_f64(eofx_ctx *ctx, const double *G, int L, int l, double *Ri
 /* out[rows_pad x Lo] = P[rows_pad x L] * M[L x Lo]  (M device float64 row-major). */
 int eofx_panel_matmul_f32(eofx_ctx *ctx, const float *P, int64_t rows_pad, int L,
                           const double *M, int Lo, float *out);
-/* per-column max and min over the first `rows` rows: mx[L], mn[L] device float32. */
+/* per-column max and min over the first `rows` rows: mx[L], mn[L] device float32.  L a positive multiple of 4 (the panel is
+ * read in 16-byte quads), else EOFX_ERR_ARG.  A NaN is skipped (fmaxf / fminf). */
 int eofx_panel_colminmax_f32(eofx_ctx *ctx, const float *P, int64_t rows, int L, float *mx,
                              float *mn);
 /* dst[rows x k] (host|device, dense) = P[:, :k] * sign[k] (host doubles or NULL). */
 int eofx_panel_export_f32(eofx_ctx *ctx, const float *P, int64_t rows, int L, int k,
                           const double *sign, float *dst);
-/* P[rows_pad x L] (device) <- src[rows x l] (host|device dense), zero padded.   */
+/* P[rows_pad x L] (device) <- src[rows x l] (host|device dense), zero padded.  L a positive multiple of 4 (the panel is
+ * written in 16-byte quads), else EOFX_ERR_ARG. */
 int eofx_panel_import_f32(eofx_ctx *ctx, const float *src, int64_t rows, int l, float *P,
                           int64_t rows_pad, int L);
 
@@ -564,8 +566,9 @@ int eofx_cmat_mul_f32(eofx_ctx *ctx, const eofx_mat *A, const eofx_mat *B, int c
  *   conj_left = 0:  out = Z   W :  out.re = P1.re - P2.im, out.im = P1.im + P2.re          */
 int eofx_cpanel_combine_f32(eofx_ctx *ctx, const float *P1, const float *P2, int conj_left,
                             int64_t rows_pad, int L, float *out);
-/* row index of the per-column max and min over the first `rows` rows (device int64[L]);
- * used for the lexicographic complex max/min of the sign rule (xarray_utils.py:294-296).     */
+/* row index of the per-column max and min over the first `rows` rows (device int64[L]), ties -> the lowest row;
+ * used for the lexicographic complex max/min of the sign rule (xarray_utils.py:294-296).  A column without a
+ * candidate row (rows == 0, or nothing but NaN) gives row 0.                                   */
 int eofx_panel_colargminmax_f32(eofx_ctx *ctx, const float *P, int64_t rows, int L, int64_t *amax,
                                 int64_t *amin);
 

@@ -2097,6 +2097,8 @@ extern "C" int eofx_panel_matmul_f32(eofx_ctx* ctx, const float* P, int64_t rows
 extern "C" int eofx_panel_colminmax_f32(eofx_ctx* ctx, const float* P, int64_t rows, int L, float* mx,
                                         float* mn) {
   if (!ctx || !P || !mx || !mn) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (L <= 0 || L % 4 || rows < 0)     // (the kernel reads the panel in 16-byte quads)
+    return set_err(ctx, EOFX_ERR_ARG, "colminmax: L=%d must be a positive multiple of 4, rows=%lld non-negative", L, (long long)rows);
   ENTER(ctx);
   CHK(arena_reserve(ctx, (size_t)2 * 1024 * L * sizeof(float) + 4096));
   return launch_colminmax(ctx, P, rows, L, mx, mn);
@@ -2111,6 +2113,8 @@ extern "C" int eofx_panel_export_f32(eofx_ctx* ctx, const float* P, int64_t rows
 extern "C" int eofx_panel_import_f32(eofx_ctx* ctx, const float* src, int64_t rows, int l, float* P,
                                      int64_t rows_pad, int L) {
   if (!ctx || !P || !src || l > L || rows > rows_pad) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (L <= 0 || L % 4 || l < 0 || rows < 0)     // (the kernel writes the panel in 16-byte quads)
+    return set_err(ctx, EOFX_ERR_ARG, "import: L=%d must be a positive multiple of 4, l=%d and rows=%lld non-negative", L, l, (long long)rows);
   ENTER(ctx);
   CHK(arena_reserve(ctx, (size_t)rows * l * sizeof(float) + 8192));
   return import_panel(ctx, src, rows, l, P, rows_pad, L);
@@ -4527,7 +4531,7 @@ extern "C" int eofx_panel_colargminmax_f32(eofx_ctx* ctx, const float* P, int64_
   return panel_colargminmax(ctx, P, rows, L, amax, amin, nullptr);
 }
 static int panel_colargminmax(eofx_ctx* ctx, const float* P, int64_t rows, int L, int64_t* amax, int64_t* amin, const float* rowscale) {
-  if (!ctx || !P || !amax || !amin) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (!ctx || !P || !amax || !amin || L <= 0 || rows < 0) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
   ENTER(ctx);
   const int nparts = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 15) / 16, 2048));
   CHK(arena_reserve(ctx, (size_t)nparts * L * 24 + 8192));

@@ -2799,8 +2799,11 @@ __global__ void colargminmax_final_kernel(const float* __restrict__ pmx, const i
   __syncthreads();
   if (ql == 0 && c < L) {
     for (int q = 1; q < 16; ++q) take(sa[q][cl], sia[q][cl], sb[q][cl], sib[q][cl]);
-    amax[c] = ia;
-    amin[c] = ib;
+    // A column without a candidate -- no rows (a rank of the sharded complex fit whose slice is empty), every row masked through
+    // rowscale, or no value that compares (all NaN) -- leaves the partial indices at -1.  The entry returns row 0 then: rsvd_c64's
+    // sign rule hands these indices to cpanel_pick_kernel, which must stay inside the panel.
+    amax[c] = ia < 0 ? 0 : ia;
+    amin[c] = ib < 0 ? 0 : ib;
   }
 }
 
