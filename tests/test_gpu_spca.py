@@ -1,4 +1,4 @@
-"""GPU tests of sparse PCA by variable projection (csrc/eofx_spca.hpp, engine.spca_*, xeofs_amd.single.SparsePCA).
+"""GPU tests of sparse PCA by variable projection (csrc/eofx_spca.hpp, xeofs_amd.spca, xeofs_amd.single.SparsePCA).
 
 The checker is a float64 numpy restatement of the algorithm (Erichson et al. 2020, variable projection) written from its
 equations: the thin SVD C = U D V^T, B = A = V[:, :k], alpha, beta scaled by D_0^2, nu = 1 / (D_0^2 + beta), kappa = nu
@@ -110,10 +110,10 @@ def rel(a, b):
 
 
 def solve(ctx, C, k, **kw):
-    from xeofs_amd import engine
+    from xeofs_amd import spca
 
-    Ct = engine._dev64(ctx, np.ascontiguousarray(np.asarray(C, np.float64).T))
-    out = engine.spca_solve(ctx, Ct, k, **kw)
+    Ct = spca._dev64(ctx, np.ascontiguousarray(np.asarray(C, np.float64).T))
+    out = spca.spca_solve(ctx, Ct, k, **kw)
     return dict(out, B=out["B"].cpu().numpy(), A=out["A"].cpu().numpy())
 
 
@@ -172,7 +172,7 @@ def test_solver_robust(ctx, check):
 
 
 def test_solver_argument_errors(ctx):
-    from xeofs_amd import engine
+    from xeofs_amd import spca
 
     C = planted(20, 300)
     with pytest.raises(ValueError):
@@ -185,7 +185,7 @@ def test_solver_argument_errors(ctx):
         solve(ctx, C, 3, alpha=float("nan"))
     with pytest.raises(ValueError, match="max_iter"):
         solve(ctx, C, 3, max_iter=0)
-    assert engine.SPCA_KMAX == 64 and engine.SPCA_LMAX == 128
+    assert spca.SPCA_KMAX == 64 and spca.SPCA_LMAX == 128
 
 
 def test_solver_bitwise_repeatable(ctx):

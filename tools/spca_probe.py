@@ -48,7 +48,7 @@ def main():
     import torch
 
     import bench
-    from xeofs_amd import engine
+    from xeofs_amd import engine, spca
     from xeofs_amd.preprocessing import Preprocessor
 
     dev = "cuda:0"
@@ -72,8 +72,8 @@ def main():
 
     da = labelled.DataArray(X, ("time", "x"))
     mat, out["ms_preprocess"] = timed(lambda: pre.fit_transform(da, "time"))
-    Ct, out["ms_qb"] = timed(lambda: engine.spca_compress(ctx, mat, args.k, 10, 1, 1, 0))
-    res, out["ms_solve"] = timed(lambda: engine.spca_solve(ctx, Ct, args.k))
+    Ct, out["ms_qb"] = timed(lambda: spca.spca_compress(ctx, mat, args.k, 10, 1, 1, 0))
+    res, out["ms_solve"] = timed(lambda: spca.spca_solve(ctx, Ct, args.k))
     B = res["B"].to(torch.float32).cpu().numpy()
     _, out["ms_scores"] = timed(lambda: engine.project(ctx, mat, B))
     out["ms_fit_wall"] = 1e3 * (time.perf_counter() - t_all)

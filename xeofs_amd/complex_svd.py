@@ -377,15 +377,8 @@ def complex_rsvd(ctx, A, B, k: int, n_oversamples: int = 10, n_iter="auto", rand
         n_iter = auto_count
     elif adaptive:      # until every wanted value is good to 2e-6 (at most 20 products, and what the Rayleigh-Ritz order allows)
         n_iter = max(2, min(20, KRYLOV_MAX_ORDER // max(l, 1) - 1))
-    if l == r:      # full-width sketch spans everything: identity, not an ill-conditioned square Gaussian
-        omega = np.eye(r, dtype=np.float32)
-    elif omega is not None:                                                       # the caller's draw (one for all ranks)
-        omega = np.asarray(omega.result() if hasattr(omega, "result") else omega, dtype=np.float32)
-        if omega.shape != (r, k + n_oversamples):
-            raise ValueError(f"omega must have shape {(r, k + n_oversamples)}")
-        omega = omega[:, :l]
-    else:
-        omega = engine.sketch_matrix(r, k + n_oversamples, random_state)[:, :l]   # real Gaussian start
+    # real Gaussian start (the caller's draw, one for all ranks, or drawn here); full width: the identity -- the engine's rule
+    omega = engine._sketch(r, k + n_oversamples, omega, random_state, identity_when_full=True, exact_rows=True)[:, :l]
     transposed = n < p      # A_op = Z^H: tall side = features (sharded), small side = samples
 
     def to_feature(P, f=False):

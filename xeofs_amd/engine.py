@@ -1,10 +1,13 @@
-"""Thin Python handles over the C ABI (include/eofx.h): context, resident matrix, and the
-hot-path calls.  numpy arrays are host buffers, torch CUDA tensors are device buffers; the
-library detects which.  No arithmetic happens in this file.
+"""Python handles over the C ABI (include/eofx.h): context, resident matrix, one plain function per entry point, and
+the marshalling those functions share (weights, statistics buffers, layout mode, start matrix, iteration code, output
+factors, the collective-error protocol).  numpy arrays are host buffers, torch CUDA tensors are device buffers; the
+library detects which.  Bindings and marshalling only: nothing here iterates, and no arithmetic happens in this file
+(the one solver written in Python on top of these calls is xeofs_amd/spca.py).
 """
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import numbers
 
@@ -346,9 +349,160 @@ def from_dense(ctx: Context, X) -> ResidentMatrix:
     return ResidentMatrix(ctx, h)
 
 
+# --------------------------------------------------------------------------- #
+# marshalling shared by the entry points below                                  #
+# --------------------------------------------------------------------------- #
 def _layout_mode(keep_raw, in_place, allow_masked):
     return (3 if allow_masked else 2) if in_place else int(bool(keep_raw))
 
+
+@contextlib.contextmanager
+def _layout(ctx: Context, mode: int, sample_raw: bool = False):
+    """the layout mode (eofx_ctx_set_layout) and the sample-raw flag (eofx_ctx_set_sample_raw) of the call inside the block;
+    both are context state of the engine and go back to 0 however the block ends"""
+    ctx.lib.eofx_ctx_set_layout(ctx.handle, int(mode))
+    ctx.lib.eofx_ctx_set_sample_raw(ctx.handle, int(bool(sample_raw)))
+    try:
+        yield
+    finally:
+        ctx.lib.eofx_ctx_set_layout(ctx.handle, 0)
+        ctx.lib.eofx_ctx_set_sample_raw(ctx.handle, 0)
+
+
+@contextlib.contextmanager
+def _collective(ctx: Context):
+    """a call that issues collectives through the communicator attached to the context: an exception raised inside a
+    callback communicator cannot cross the C frames, so the trampoline (`comm_set_callback`) stores it in `ctx._comm_err` and
+    returns an error status.  The slot is cleared on entry and a stored exception is re-raised on exit -- BEFORE the caller
+    looks at the status code, which only says that some collective failed."""
+    ctx._comm_err = None
+    yield
+    if getattr(ctx, "_comm_err", None) is not None:
+        raise ctx._comm_err
+
+
+def _weights(feature_weights, P: int, what: str = "stacked feature"):
+    """feature weights as a float64 C-contiguous host array with one entry per `what`, or None"""
+    if feature_weights is None:
+        return None
+    w = np.ascontiguousarray(feature_weights, dtype=np.float64)
+    if w.shape != (P,):
+        raise ValueError(f"feature_weights must have one entry per {what}")
+    return w
+
+
+class _FitStats:
+    """The statistics a preprocessing entry point returns: the buffers the engine fills and the scalars it sets by
+    reference.  `args`: the seven pointers in the order every such entry takes them."""
+
+    def __init__(self, n: int, P: int, want_stats: bool):
+        self.mean = np.empty(P, np.float64) if want_stats else None
+        self.std = np.empty(P, np.float64) if want_stats else None
+        self.vf = np.empty(P, np.uint8)
+        self.vs = np.empty(n, np.uint8)
+        self.n, self.p, self.tv = C.c_int64(), C.c_int64(), C.c_double()
+        self.args = (ptr(self.mean), ptr(self.std), ptr(self.vf), ptr(self.vs), C.byref(self.n), C.byref(self.p),
+                     C.byref(self.tv))
+
+    def as_dict(self, **extra) -> dict:
+        """the `stats` dict; `extra` adds keys (`fused`) or replaces what the entry does not report itself"""
+        stats = dict(mean=self.mean, std=self.std, valid_feature=self.vf.astype(bool), valid_sample=self.vs.astype(bool),
+                     n=self.n.value, p=self.p.value, total_variance=self.tv.value)
+        stats.update(extra)
+        return stats
+
+
+def _adopt(ctx: Context, handle, X, keep: bool, valid_feature) -> ResidentMatrix:
+    """the matrix an entry point built from the field X.  keep: the matrix reads X where it lies -- a device field is then
+    referenced so that it outlives the matrix (a host field was staged and is owned by the engine).  A masked in-place
+    matrix learns which of its physical columns are the valid features."""
+    mat = ResidentMatrix(ctx, handle)
+    if keep and hasattr(X, "data_ptr"):
+        mat._keepalive = X
+    if mat.masked:
+        mat.set_valid(valid_feature)
+    return mat
+
+
+def _sketch(rows: int, width: int, omega, random_state, *, identity_when_full: bool, exact_rows, resolve_first: bool = False):
+    """The start matrix [rows, width] of a randomized decomposition as a float32 C-contiguous host array -- the one place
+    that knows how it is resolved.  omega: None (drawn from random_state: `sketch_matrix`), an array, or anything with
+    `.result()` (SketchFuture, SketchSlice), which is joined here.
+    identity_when_full: a sketch at least as wide as the matrix is small (width >= rows) spans everything, so the identity
+    [rows, width] replaces an (occasionally ill-conditioned) square Gaussian; `omega` is then neither joined, drawn nor
+    checked -- unless resolve_first (the panel-level drivers of xeofs_amd.sharded resolve before they look at the width: a
+    draw from a shared RandomState advances it all the same).
+    exact_rows: True -- the shape must be (rows, width); False -- further rows may follow (the engine is told the row count
+    and reads the leading `rows`); None -- not checked, the caller slices what it needs."""
+    full = identity_when_full and width >= rows
+    if not full or resolve_first:
+        if hasattr(omega, "result"):
+            omega = omega.result()
+        if omega is None:
+            omega = sketch_matrix(rows, width, random_state)
+        omega = np.ascontiguousarray(omega, dtype=np.float32)
+        if exact_rows is None:
+            fits = True
+        elif exact_rows:
+            fits = omega.shape == (rows, width)
+        else:
+            fits = omega.ndim == 2 and omega.shape[1] == width and omega.shape[0] >= rows
+        if not fits:
+            raise ValueError(f"omega must have shape {(rows, width)}")
+    return np.eye(rows, width, dtype=np.float32) if full else omega
+
+
+def _n_iter_code(n_iter, complex_rule: bool = False) -> int:
+    """n_iter as the engine takes it: a count, or -1 for "auto" (scikit-learn's count).  complex_rule (the complex
+    decompositions): None means "auto" as well, and "converge" is -2 -- until the Ritz values stand still (at most 20)."""
+    if n_iter == "auto" or (complex_rule and n_iter is None):
+        return -1
+    if complex_rule and n_iter == "converge":
+        return -2
+    return int(n_iter)
+
+
+def _factors_out(ctx: Context, n: int, rows_v: int, k: int, dtype=np.float32, device_out: bool = False):
+    """-> (U [n, k], s [k] float32 host, V [rows_v, k]) for the engine to fill: host arrays, or torch tensors on the context's
+    device with device_out (nothing crosses PCIe); dtype float32 or complex64"""
+    if device_out:
+        torch = _torch()
+        tdt = torch.complex64 if np.dtype(dtype) == np.complex64 else torch.float32
+        U = torch.empty((n, k), dtype=tdt, device=f"cuda:{ctx.device}")
+        V = torch.empty((rows_v, k), dtype=tdt, device=f"cuda:{ctx.device}")
+    else:
+        U = _host_out((n, k), dtype)
+        V = _host_out((rows_v, k), dtype)
+    return U, np.empty(k, np.float32), V
+
+
+class _CrossOut:
+    """The outputs of a cross-covariance driver (x, y: the two resident matrices, k modes).  `args`: the seven pointers in
+    the order both entries take them; `tsc`: the total squared covariance, NaN unless the engine is handed it."""
+
+    def __init__(self, x: ResidentMatrix, y: ResidentMatrix, k: int):
+        self.x, self.y = x, y
+        # (at least one row: an empty slice of a sharded field still hands the engine a buffer)
+        self.Q1 = np.empty((max(x.p_phys, 1), k), np.float32)
+        self.Q2 = np.empty((max(y.p_phys, 1), k), np.float32)
+        self.s = np.empty(k, np.float32)
+        self.scores1 = np.empty((x.n, k), np.float32)
+        self.scores2 = np.empty((x.n, k), np.float32)
+        self.norm1 = np.empty(k, np.float32)
+        self.norm2 = np.empty(k, np.float32)
+        self.tsc = C.c_double(float("nan"))
+        self.args = tuple(ptr(a) for a in (self.Q1, self.s, self.Q2, self.scores1, self.scores2, self.norm1, self.norm2))
+
+    def as_dict(self) -> dict:
+        """the result dict; Q1 / Q2 hold the rows of the valid features of their matrix"""
+        rows = lambda mat, Q: mat.compact_rows(Q if Q.shape[0] == mat.p_phys else Q[:mat.p_phys])
+        return dict(Q1=rows(self.x, self.Q1), Q2=rows(self.y, self.Q2), s=self.s, scores1=self.scores1, scores2=self.scores2,
+                    norm1=self.norm1, norm2=self.norm2, total_squared_covariance=self.tsc.value)
+
+
+# --------------------------------------------------------------------------- #
+# preprocessing and decomposition entry points                                  #
+# --------------------------------------------------------------------------- #
 
 def preprocess(ctx: Context, X, center=True, standardize=False, feature_weights=None,
                check_nans=True, want_stats=True, build=True, keep_raw=False, in_place=False, allow_masked=False,
@@ -366,34 +520,15 @@ def preprocess(ctx: Context, X, center=True, standardize=False, feature_weights=
     raw field in the sample-contiguous layout (eofx_ctx_set_sample_raw) and the Hilbert stage saves its transposing copy."""
     X = _f32c(X)
     n, P = X.shape
-    w = None if feature_weights is None else np.ascontiguousarray(feature_weights, dtype=np.float64)
-    if w is not None and w.shape != (P,):
-        raise ValueError("feature_weights must have one entry per stacked feature")
-    mean = np.empty(P, np.float64) if want_stats else None
-    std = np.empty(P, np.float64) if want_stats else None
-    vf = np.empty(P, np.uint8)
-    vs = np.empty(n, np.uint8)
-    n_out, p_out = C.c_int64(), C.c_int64()
-    tv = C.c_double()
+    w = _weights(feature_weights, P)
+    st = _FitStats(n, P, want_stats)
     h = C.c_void_p()
-    ctx.lib.eofx_ctx_set_layout(ctx.handle, _layout_mode(keep_raw, in_place, allow_masked))
-    ctx.lib.eofx_ctx_set_sample_raw(ctx.handle, int(bool(for_hilbert and in_place and build)))
-    try:
+    with _layout(ctx, _layout_mode(keep_raw, in_place, allow_masked), sample_raw=for_hilbert and in_place and build):
         rc = ctx.lib.eofx_preprocess_f32(ctx.handle, ptr(X), n, P, int(center), int(standardize), ptr(w),
-                                         int(check_nans), C.byref(h) if build else None, ptr(mean), ptr(std),
-                                         ptr(vf), ptr(vs), C.byref(n_out), C.byref(p_out), C.byref(tv))
-    finally:
-        ctx.lib.eofx_ctx_set_layout(ctx.handle, 0)
-        ctx.lib.eofx_ctx_set_sample_raw(ctx.handle, 0)
+                                         int(check_nans), C.byref(h) if build else None, *st.args)
     raise_for(rc, ctx.handle)
-    stats = dict(mean=mean, std=std, valid_feature=vf.astype(bool), valid_sample=vs.astype(bool),
-                 n=n_out.value, p=p_out.value, total_variance=tv.value)
-    mat = ResidentMatrix(ctx, h) if build else None
-    if mat is not None and (keep_raw or in_place) and hasattr(X, "data_ptr"):
-        mat._keepalive = X
-    if mat is not None and mat.masked:
-        mat.set_valid(stats["valid_feature"])
-    return mat, stats
+    mat = _adopt(ctx, h, X, keep_raw or in_place, st.vf) if build else None
+    return mat, st.as_dict()
 
 
 def fit(ctx: Context, X, k: int, center=True, standardize=False, feature_weights=None, check_nans=True,
@@ -407,54 +542,22 @@ def fit(ctx: Context, X, k: int, center=True, standardize=False, feature_weights
     X = _f32c(X)
     n, P = X.shape
     k = int(k)
-    w = None if feature_weights is None else np.ascontiguousarray(feature_weights, dtype=np.float64)
-    if w is not None and w.shape != (P,):
-        raise ValueError("feature_weights must have one entry per stacked feature")
-    small = min(n, P)
-    if omega is None:
-        omega = sketch_matrix(small, k + n_oversamples, random_state)
-    elif isinstance(omega, SketchFuture):
-        omega = omega.result()
-    omega = np.ascontiguousarray(omega, dtype=np.float32)
-    if omega.ndim != 2 or omega.shape[1] != k + n_oversamples or omega.shape[0] < small:
-        raise ValueError(f"omega must have shape {(small, k + n_oversamples)}")
-    mean = np.empty(P, np.float64) if want_stats else None
-    std = np.empty(P, np.float64) if want_stats else None
-    vf = np.empty(P, np.uint8)
-    vs = np.empty(n, np.uint8)
-    n_out, p_out = C.c_int64(), C.c_int64()
-    tv = C.c_double()
+    w = _weights(feature_weights, P)
+    omega = _sketch(min(n, P), k + n_oversamples, omega, random_state, identity_when_full=False, exact_rows=False)
+    st = _FitStats(n, P, want_stats)
     fused = C.c_int()
     h = C.c_void_p()
-    if device_out:
-        torch = _torch()
-        U = torch.empty((n, k), dtype=torch.float32, device=f"cuda:{ctx.device}")
-        V = torch.empty((P, k), dtype=torch.float32, device=f"cuda:{ctx.device}")
-    else:
-        U = _host_out((n, k))
-        V = _host_out((P, k))
-    s = np.empty(k, np.float32)
-    it = -1 if n_iter == "auto" else int(n_iter)
-    ctx.lib.eofx_ctx_set_layout(ctx.handle, _layout_mode(False, in_place, allow_masked))
-    try:
+    U, s, V = _factors_out(ctx, n, P, k, np.float32, device_out)
+    with _layout(ctx, _layout_mode(False, in_place, allow_masked)):
         rc = ctx.lib.eofx_fit_f32(ctx.handle, ptr(X), n, P, int(center), int(standardize), ptr(w), int(check_nans), k,
-                                  int(n_oversamples), it, ptr(omega), omega.shape[0], int(flip), C.byref(h), ptr(mean),
-                                  ptr(std), ptr(vf), ptr(vs), C.byref(n_out), C.byref(p_out), C.byref(tv), ptr(U), ptr(s),
-                                  ptr(V), C.byref(fused))
-    finally:
-        ctx.lib.eofx_ctx_set_layout(ctx.handle, 0)
+                                  int(n_oversamples), _n_iter_code(n_iter), ptr(omega), omega.shape[0], int(flip),
+                                  C.byref(h), *st.args, ptr(U), ptr(s), ptr(V), C.byref(fused))
     raise_for(rc, ctx.handle)
-    mat = ResidentMatrix(ctx, h)
-    if hasattr(X, "data_ptr"):
-        mat._keepalive = X
-    stats = dict(mean=mean, std=std, valid_feature=vf.astype(bool), valid_sample=vs.astype(bool),
-                 n=n_out.value, p=p_out.value, total_variance=tv.value, fused=bool(fused.value))
-    if mat.masked:
-        mat.set_valid(stats["valid_feature"])
+    mat = _adopt(ctx, h, X, True, st.vf)
     if mat.n != n or mat.p_phys != P:     # the factors were written densely with the compacted shape
         U = U.reshape(-1)[: mat.n * k].reshape(mat.n, k)
         V = V.reshape(-1)[: mat.p_phys * k].reshape(mat.p_phys, k)
-    return mat, stats, U, s, mat.compact_rows(V)
+    return mat, st.as_dict(fused=bool(fused.value)), U, s, mat.compact_rows(V)
 
 
 # ---- communicator of the native feature-sharded fit (include/eofx.h: eofx_fit_sharded_f32) -------------------------------
@@ -535,51 +638,23 @@ def fit_sharded(ctx: Context, X, k: int, p_total: int, center=True, standardize=
     X = _f32c(X)
     n, P = X.shape
     k = int(k)
-    w = None if feature_weights is None else np.ascontiguousarray(feature_weights, dtype=np.float64)
-    if w is not None and w.shape != (P,):
-        raise ValueError("feature_weights must have one entry per stacked feature of the slice")
-    if omega is None:
-        omega = sketch_matrix(n, k + n_oversamples, random_state)
-    elif hasattr(omega, "result"):
-        omega = omega.result()
-    omega = np.ascontiguousarray(omega, dtype=np.float32)
-    if omega.ndim != 2 or omega.shape[1] != k + n_oversamples or omega.shape[0] < n:
-        raise ValueError(f"omega must have shape {(n, k + n_oversamples)}")
-    mean = np.empty(P, np.float64) if want_stats else None
-    std = np.empty(P, np.float64) if want_stats else None
-    vf = np.empty(P, np.uint8)
-    tv = C.c_double()
+    w = _weights(feature_weights, P, what="stacked feature of the slice")
+    omega = _sketch(n, k + n_oversamples, omega, random_state, identity_when_full=False, exact_rows=False)
+    st = _FitStats(n, P, want_stats)
     h = C.c_void_p()
-    if device_out:
-        torch = _torch()
-        U = torch.empty((n, k), dtype=torch.float32, device=f"cuda:{ctx.device}")
-        V = torch.empty((P, k), dtype=torch.float32, device=f"cuda:{ctx.device}")
-    else:
-        U = _host_out((n, k))
-        V = _host_out((P, k))
-    s = np.empty(k, np.float32)
-    it = -1 if n_iter == "auto" else int(n_iter)
-    ctx._comm_err = None
-    ctx.lib.eofx_ctx_set_layout(ctx.handle, _layout_mode(False, True, allow_masked))
-    try:
+    U, s, V = _factors_out(ctx, n, P, k, np.float32, device_out)
+    # (on the way out the layout is reset first, then an exception a callback communicator stored is re-raised)
+    with _collective(ctx), _layout(ctx, _layout_mode(False, True, allow_masked)):
         rc = ctx.lib.eofx_fit_sharded_f32(ctx.handle, ptr(X), n, P, int(p_total), int(center), int(standardize), ptr(w), k,
-                                          int(n_oversamples), it, ptr(omega), omega.shape[0], int(flip), C.byref(h),
-                                          ptr(mean), ptr(std), ptr(vf), C.byref(tv), ptr(U), ptr(s), ptr(V))
-    finally:
-        ctx.lib.eofx_ctx_set_layout(ctx.handle, 0)
-    if getattr(ctx, "_comm_err", None) is not None:
-        raise ctx._comm_err
-    if rc == 1:
+                                          int(n_oversamples), _n_iter_code(n_iter), ptr(omega), omega.shape[0], int(flip),
+                                          C.byref(h), ptr(st.mean), ptr(st.std), ptr(st.vf), C.byref(st.tv), ptr(U), ptr(s),
+                                          ptr(V))
+    if rc == 1:       # the ranks' vote for the panel-level driver; only now is any other status an error
         return None
     raise_for(rc, ctx.handle)
-    mat = ResidentMatrix(ctx, h)
-    if hasattr(X, "data_ptr"):
-        mat._keepalive = X
-    stats = dict(mean=mean, std=std, valid_feature=vf.astype(bool), valid_sample=np.ones(n, bool), n=n,
-                 p=mat.p, total_variance=tv.value, fused=True)
-    if mat.masked:
-        mat.set_valid(stats["valid_feature"])
-    return mat, stats, U, s, mat.compact_rows(V)
+    mat = _adopt(ctx, h, X, True, st.vf)
+    # the sharded entry drops no sample and reports no counts: every sample is valid, p is the slice's valid features
+    return mat, st.as_dict(valid_sample=np.ones(n, bool), n=n, p=mat.p, fused=True), U, s, mat.compact_rows(V)
 
 
 def fit_first(ctx: Context, X, Zn, l: int, center=True, standardize=False, feature_weights=None, check_nans=True,
@@ -591,37 +666,22 @@ def fit_first(ctx: Context, X, Zn, l: int, center=True, standardize=False, featu
     torch = _torch()
     X = _f32c(X)
     n, P = X.shape
-    w = None if feature_weights is None else np.ascontiguousarray(feature_weights, dtype=np.float64)
-    if w is not None and w.shape != (P,):
-        raise ValueError("feature_weights must have one entry per stacked feature")
+    w = _weights(feature_weights, P)
     L = Zn.shape[1]
     Yp = torch.empty(((P + 511) // 512 * 512, L), dtype=torch.float32, device=Zn.device)
-    mean = np.empty(P, np.float64) if want_stats else None
-    std = np.empty(P, np.float64) if want_stats else None
-    vf = np.empty(P, np.uint8)
-    vs = np.empty(n, np.uint8)
-    n_out, p_out = C.c_int64(), C.c_int64()
-    tv = C.c_double()
+    st = _FitStats(n, P, want_stats)
     fused = C.c_int()
     h = C.c_void_p()
-    ctx.lib.eofx_ctx_set_layout(ctx.handle, 2)
-    try:
+    with _layout(ctx, 2):
         rc = ctx.lib.eofx_fit_first_f32(ctx.handle, ptr(X), n, P, int(center), int(standardize), ptr(w), int(check_nans),
-                                        ptr(Zn), L, int(l), ptr(Yp), C.byref(h), ptr(mean), ptr(std), ptr(vf), ptr(vs),
-                                        C.byref(n_out), C.byref(p_out), C.byref(tv), C.byref(fused))
-    finally:
-        ctx.lib.eofx_ctx_set_layout(ctx.handle, 0)
+                                        ptr(Zn), L, int(l), ptr(Yp), C.byref(h), *st.args, C.byref(fused))
     raise_for(rc, ctx.handle)
-    mat = ResidentMatrix(ctx, h)
-    if hasattr(X, "data_ptr"):
-        mat._keepalive = X
-    stats = dict(mean=mean, std=std, valid_feature=vf.astype(bool), valid_sample=vs.astype(bool),
-                 n=n_out.value, p=p_out.value, total_variance=tv.value, fused=bool(fused.value))
-    if n_out.value != n:
+    mat = _adopt(ctx, h, X, True, st.vf)
+    if st.n.value != n:
         Yp = None
     elif mat.p_pad != Yp.shape[0]:
         Yp = Yp[: mat.p_pad].contiguous()
-    return mat, stats, Yp
+    return mat, st.as_dict(fused=bool(fused.value)), Yp
 
 
 def fit_info(ctx: Context):
@@ -649,19 +709,11 @@ def apply(ctx: Context, X, mean, std, feature_weights, valid_feature, check_nans
     vs = np.empty(n, np.uint8)
     n_out = C.c_int64()
     h = C.c_void_p()
-    ctx.lib.eofx_ctx_set_layout(ctx.handle, _layout_mode(False, in_place, allow_masked))
-    try:
+    with _layout(ctx, _layout_mode(False, in_place, allow_masked)):
         rc = ctx.lib.eofx_apply_f32(ctx.handle, ptr(X), n, P, ptr(mean), ptr(std), ptr(w), ptr(vf),
                                     int(check_nans), C.byref(h), ptr(vs), C.byref(n_out))
-    finally:
-        ctx.lib.eofx_ctx_set_layout(ctx.handle, 0)
     raise_for(rc, ctx.handle)
-    mat = ResidentMatrix(ctx, h)
-    if in_place and hasattr(X, "data_ptr"):
-        mat._keepalive = X
-    if mat.masked:
-        mat.set_valid(vf)
-    return mat, vs.astype(bool)
+    return _adopt(ctx, h, X, in_place, vf), vs.astype(bool)
 
 
 def rsvd(ctx: Context, mat: ResidentMatrix, k: int, n_oversamples: int = 10, n_iter: int | str = "auto",
@@ -669,24 +721,12 @@ def rsvd(ctx: Context, mat: ResidentMatrix, k: int, n_oversamples: int = 10, n_i
     """randomized SVD of the resident matrix -> (U[n,k], s[k], V[p,k]) float32 host arrays
     (or torch device tensors for U and V with `device_out=True`: nothing crosses PCIe)."""
     k = int(k)
-    small = min(mat.n, mat.p)
-    if omega is None:
-        omega = sketch_matrix(small, k + n_oversamples, random_state)
-    omega = np.ascontiguousarray(omega, dtype=np.float32)
-    if omega.shape != (small, k + n_oversamples):
-        raise ValueError(f"omega must have shape {(small, k + n_oversamples)}")
+    # (a full-width sketch becomes the identity inside the engine, eofx_rsvd_f32: the draw is still made and checked here)
+    omega = _sketch(min(mat.n, mat.p), k + n_oversamples, omega, random_state, identity_when_full=False, exact_rows=True)
     if mat.masked and mat.p < mat.n:
         raise NotImplementedError("masked in-place matrix with fewer valid features than samples")   # the engine never builds one
-    if device_out:
-        torch = _torch()
-        U = torch.empty((mat.n, k), dtype=torch.float32, device=f"cuda:{ctx.device}")
-        V = torch.empty((mat.p_phys, k), dtype=torch.float32, device=f"cuda:{ctx.device}")
-    else:
-        U = _host_out((mat.n, k))
-        V = _host_out((mat.p_phys, k))
-    s = np.empty(k, np.float32)
-    it = -1 if n_iter == "auto" else int(n_iter)
-    rc = ctx.lib.eofx_rsvd_f32(ctx.handle, mat.handle, k, int(n_oversamples), it, ptr(omega), int(flip),
+    U, s, V = _factors_out(ctx, mat.n, mat.p_phys, k, np.float32, device_out)
+    rc = ctx.lib.eofx_rsvd_f32(ctx.handle, mat.handle, k, int(n_oversamples), _n_iter_code(n_iter), ptr(omega), int(flip),
                                ptr(U), ptr(s), ptr(V))
     raise_for(rc, ctx.handle)
     return U, s, mat.compact_rows(V)
@@ -732,27 +772,13 @@ def crosscov_rsvd(ctx: Context, x: ResidentMatrix, y: ResidentMatrix, k: int, n_
         raise ValueError(f"Both data matrices must have the same number of samples but found {x.n} in the first and "
                          f"{y.n} in the second.")
 
-    def sketch():
-        om = omega.result() if hasattr(omega, "result") else omega     # a SketchFuture is joined as late as possible
-        if om is None:
-            om = sketch_matrix(small, k + n_oversamples, random_state)
-        om = np.ascontiguousarray(om, dtype=np.float32)
-        if om.shape != (small, k + n_oversamples):
-            raise ValueError(f"omega must have shape {(small, k + n_oversamples)}")
+    def sketch():       # (called by the engine: a SketchFuture is joined as late as possible)
+        om = _sketch(small, k + n_oversamples, omega, random_state, identity_when_full=False, exact_rows=True)
         # masked in-place matrices keep their all-NaN grid points as zero columns: the sketch gets zero rows there, the
-        # singular vectors come back with zero rows there (compacted below)
+        # singular vectors come back with zero rows there (compacted in the result)
         return np.ascontiguousarray(small_mat.scatter_rows(om))
 
-    n = x.n
-    Q1 = np.empty((x.p_phys, k), np.float32)
-    Q2 = np.empty((y.p_phys, k), np.float32)
-    s = np.empty(k, np.float32)
-    s1 = np.empty((n, k), np.float32)
-    s2 = np.empty((n, k), np.float32)
-    n1 = np.empty(k, np.float32)
-    n2 = np.empty(k, np.float32)
-    tsc = C.c_double(float("nan"))
-    it = -1 if n_iter == "auto" else int(n_iter)
+    out = _CrossOut(x, y, k)
     # the engine asks for the sketch when it first needs it (eofx_crosscov_rsvd_lazy_f32): with the total squared
     # covariance wanted, the Gram matrices are queued before that and a SketchFuture finishes beside them
     held = {}
@@ -766,24 +792,20 @@ def crosscov_rsvd(ctx: Context, x: ResidentMatrix, y: ResidentMatrix, k: int, n_
             return None
 
     cb = _lib.SKETCH_FN(provide)
-    rc = ctx.lib.eofx_crosscov_rsvd_lazy_f32(ctx.handle, x.handle, y.handle, k, int(n_oversamples), it, cb, None,
-                                             int(flip), ptr(Q1), ptr(s), ptr(Q2), ptr(s1), ptr(s2), ptr(n1), ptr(n2),
-                                             C.byref(tsc) if want_tsc else None)
+    rc = ctx.lib.eofx_crosscov_rsvd_lazy_f32(ctx.handle, x.handle, y.handle, k, int(n_oversamples), _n_iter_code(n_iter), cb,
+                                             None, int(flip), *out.args, C.byref(out.tsc) if want_tsc else None)
     if "err" in held:
         raise held["err"]
     raise_for(rc, ctx.handle)
-    return dict(Q1=x.compact_rows(Q1), Q2=y.compact_rows(Q2), s=s, scores1=s1, scores2=s2, norm1=n1, norm2=n2,
-                total_squared_covariance=tsc.value)
+    return out.as_dict()
 
 
 def comm_allreduce_host(ctx: Context, values, op: str = "sum") -> np.ndarray:
     """all-reduce of a small host vector of doubles over the communicator attached to the context
     (eofx_ctx_comm_allreduce_f64): the global facts a sharded model needs between engine calls"""
     buf = np.ascontiguousarray(np.atleast_1d(values), dtype=np.float64).copy()
-    ctx._comm_err = None
-    rc = ctx.lib.eofx_ctx_comm_allreduce_f64(ctx.handle, ptr(buf), buf.size, {"sum": 0, "max": 1, "min": 2}[op])
-    if getattr(ctx, "_comm_err", None) is not None:
-        raise ctx._comm_err
+    with _collective(ctx):
+        rc = ctx.lib.eofx_ctx_comm_allreduce_f64(ctx.handle, ptr(buf), buf.size, {"sum": 0, "max": 1, "min": 2}[op])
     raise_for(rc, ctx.handle)
     return buf
 
@@ -807,37 +829,18 @@ def crosscov_rsvd_sharded(ctx: Context, x: ResidentMatrix, y: ResidentMatrix, k:
         raise ValueError("sketch wider than rank not supported on the cross path")
     on_x = int(p1_total) < int(p2_total)            # the sketch lives on the narrower field's feature axis
     sm, off = (x, int(p1_offset)) if on_x else (y, int(p2_offset))
-    om = omega.result() if hasattr(omega, "result") else omega
-    if l_req == small:      # full-width sketch: the identity (see eofx_rsvd_f32)
-        om = np.eye(small, dtype=np.float32)
-    elif om is None:
-        om = sketch_matrix(small, l_req, random_state)
-    om = np.asarray(om, dtype=np.float32)
-    if om.shape != (small, l_req):
-        raise ValueError(f"omega must have shape {(small, l_req)}")
+    # (this entry takes the rows of the slice, so the identity of a full-width sketch is written here: see eofx_rsvd_f32)
+    om = _sketch(small, l_req, omega, random_state, identity_when_full=True, exact_rows=True)
     rows = np.ascontiguousarray(sm.scatter_rows(np.ascontiguousarray(om[off:off + sm.p])), dtype=np.float32)
     if rows.shape[0] == 0:
         rows = np.zeros((1, l_req), np.float32)
-    n = x.n
-    Q1 = np.empty((max(x.p_phys, 1), k), np.float32)
-    Q2 = np.empty((max(y.p_phys, 1), k), np.float32)
-    s = np.empty(k, np.float32)
-    s1 = np.empty((n, k), np.float32)
-    s2 = np.empty((n, k), np.float32)
-    n1 = np.empty(k, np.float32)
-    n2 = np.empty(k, np.float32)
-    tsc = C.c_double(float("nan"))
-    it = -1 if n_iter == "auto" else int(n_iter)
-    ctx._comm_err = None
-    rc = ctx.lib.eofx_crosscov_rsvd_sharded_f32(ctx.handle, x.handle, y.handle, int(p1_total), int(p1_offset), int(p2_total),
-                                                int(p2_offset), k, int(n_oversamples), it, ptr(rows), int(flip), ptr(Q1),
-                                                ptr(s), ptr(Q2), ptr(s1), ptr(s2), ptr(n1), ptr(n2),
-                                                C.byref(tsc) if want_tsc else None)
-    if getattr(ctx, "_comm_err", None) is not None:
-        raise ctx._comm_err
+    out = _CrossOut(x, y, k)
+    with _collective(ctx):
+        rc = ctx.lib.eofx_crosscov_rsvd_sharded_f32(ctx.handle, x.handle, y.handle, int(p1_total), int(p1_offset),
+                                                    int(p2_total), int(p2_offset), k, int(n_oversamples), _n_iter_code(n_iter),
+                                                    ptr(rows), int(flip), *out.args, C.byref(out.tsc) if want_tsc else None)
     raise_for(rc, ctx.handle)
-    return dict(Q1=x.compact_rows(Q1[:x.p_phys]), Q2=y.compact_rows(Q2[:y.p_phys]), s=s, scores1=s1, scores2=s2, norm1=n1,
-                norm2=n2, total_squared_covariance=tsc.value)
+    return out.as_dict()
 
 
 def host_eigh(A: np.ndarray):
@@ -1127,32 +1130,22 @@ def sample_norms(ctx: Context, mat: ResidentMatrix) -> np.ndarray:
     return out
 
 
-def _c64_arguments(ctx: Context, A: ResidentMatrix, k: int, n_oversamples: int, n_iter, random_state, omega, device_out: bool):
-    """the start matrix, the iteration rule and the output buffers shared by the two complex decompositions"""
-    r = min(A.n, A.p)
+def _c64_arguments(ctx: Context, A: ResidentMatrix, k: int, n_oversamples: int, n_iter, random_state, omega, device_out: bool,
+                   p_total=None):
+    """the start matrix, the iteration code and the output buffers (omega, it, U, s, V) of the complex decompositions.
+    p_total: A is this rank's slice of a field with `p_total` valid features over all ranks (n < p_total: the start matrix
+    lives on the replicated sample side -- one draw, identical on every rank)."""
+    if p_total is None:
+        r, rows_v = min(A.n, A.p), A.p_phys
+    else:
+        if not A.n < int(p_total):
+            raise ValueError("the sharded complex decomposition needs more features over all ranks than samples")
+        r, rows_v = A.n, max(A.p_phys, 1)
     if k > r:
         raise ValueError(f"n_modes must be less than or equal to the rank of the dataset (rank = {r}).")
-    l = min(k + n_oversamples, r)
-    if l == r:      # full-width sketch spans everything: identity, not an ill-conditioned square Gaussian
-        omega = np.zeros((r, k + n_oversamples), np.float32)
-        omega[np.arange(l), np.arange(l)] = 1.0
-    elif omega is None:
-        omega = np.ascontiguousarray(sketch_matrix(r, k + n_oversamples, random_state), dtype=np.float32)
-    else:
-        omega = np.ascontiguousarray(omega, dtype=np.float32)
-        if omega.shape != (r, k + n_oversamples):
-            raise ValueError(f"omega must have shape {(r, k + n_oversamples)}")
-    # "auto": scikit-learn's count, as the real branch; "converge": until the Ritz values stand still (at most 20 iterations)
-    it = -1 if n_iter in ("auto", None) else -2 if n_iter == "converge" else int(n_iter)
-    if device_out:
-        torch = _torch()
-        dev = f"cuda:{ctx.device}"
-        U = torch.empty((A.n, k), dtype=torch.complex64, device=dev)
-        V = torch.empty((A.p_phys, k), dtype=torch.complex64, device=dev)
-    else:
-        U = _host_out((A.n, k), np.complex64)
-        V = _host_out((A.p_phys, k), np.complex64)
-    return omega, it, U, np.empty(k, np.float32), V
+    omega = _sketch(r, k + n_oversamples, omega, random_state, identity_when_full=True, exact_rows=True)
+    U, s, V = _factors_out(ctx, A.n, rows_v, k, np.complex64, device_out)
+    return omega, _n_iter_code(n_iter, complex_rule=True), U, s, V
 
 
 def rsvd_c64(ctx: Context, A: ResidentMatrix, B: ResidentMatrix, k: int, n_oversamples: int = 10, n_iter="auto",
@@ -1170,38 +1163,6 @@ def rsvd_c64(ctx: Context, A: ResidentMatrix, B: ResidentMatrix, k: int, n_overs
     return U, s, A.compact_rows(V)       # (masked real part: the rows of the valid features)
 
 
-def _c64_sharded_arguments(ctx: Context, A: ResidentMatrix, k: int, p_total: int, n_oversamples: int, n_iter, random_state,
-                           omega, device_out: bool):
-    """as `_c64_arguments` for a slice of a field with `p_total` valid features over all ranks (n < p_total: the start matrix
-    lives on the replicated sample side -- one draw, identical on every rank)"""
-    n = A.n
-    if not n < int(p_total):
-        raise ValueError("the sharded complex decomposition needs more features over all ranks than samples")
-    if k > n:
-        raise ValueError(f"n_modes must be less than or equal to the rank of the dataset (rank = {n}).")
-    l = min(k + n_oversamples, n)
-    if l == n:
-        omega = np.zeros((n, k + n_oversamples), np.float32)
-        omega[np.arange(l), np.arange(l)] = 1.0
-    elif omega is None:
-        omega = np.ascontiguousarray(sketch_matrix(n, k + n_oversamples, random_state), dtype=np.float32)
-    else:
-        omega = np.ascontiguousarray(omega.result() if hasattr(omega, "result") else omega, dtype=np.float32)
-        if omega.shape != (n, k + n_oversamples):
-            raise ValueError(f"omega must have shape {(n, k + n_oversamples)}")
-    it = -1 if n_iter in ("auto", None) else -2 if n_iter == "converge" else int(n_iter)
-    rows_v = max(A.p_phys, 1)
-    if device_out:
-        torch = _torch()
-        dev = f"cuda:{ctx.device}"
-        U = torch.empty((n, k), dtype=torch.complex64, device=dev)
-        V = torch.empty((rows_v, k), dtype=torch.complex64, device=dev)
-    else:
-        U = _host_out((n, k), np.complex64)
-        V = _host_out((rows_v, k), np.complex64)
-    return omega, it, U, np.empty(k, np.float32), V
-
-
 def rsvd_sharded_c64(ctx: Context, A: ResidentMatrix, B: ResidentMatrix, k: int, p_total: int, n_oversamples: int = 10,
                      n_iter="auto", random_state=None, flip: bool = True, omega=None, device_out: bool = False):
     """`rsvd_c64` on this rank's slice of the feature axis (eofx_rsvd_sharded_c64; collectives through the communicator
@@ -1209,12 +1170,10 @@ def rsvd_sharded_c64(ctx: Context, A: ResidentMatrix, B: ResidentMatrix, k: int,
     k = int(k)
     if B.masked or (A.masked and B.p_phys != A.p_phys):
         raise NotImplementedError("masked in-place real part: the imaginary part must be a written matrix over the same physical columns")
-    omega, it, U, s, V = _c64_sharded_arguments(ctx, A, k, p_total, n_oversamples, n_iter, random_state, omega, device_out)
-    ctx._comm_err = None
-    rc = ctx.lib.eofx_rsvd_sharded_c64(ctx.handle, A.handle, B.handle, int(p_total), k, int(n_oversamples), it, ptr(omega),
-                                       int(flip), ptr(U), ptr(s), ptr(V))
-    if getattr(ctx, "_comm_err", None) is not None:
-        raise ctx._comm_err
+    omega, it, U, s, V = _c64_arguments(ctx, A, k, n_oversamples, n_iter, random_state, omega, device_out, p_total=p_total)
+    with _collective(ctx):
+        rc = ctx.lib.eofx_rsvd_sharded_c64(ctx.handle, A.handle, B.handle, int(p_total), k, int(n_oversamples), it, ptr(omega),
+                                           int(flip), ptr(U), ptr(s), ptr(V))
     raise_for(rc, ctx.handle)
     return U, s, A.compact_rows(V[:A.p_phys])
 
@@ -1226,12 +1185,11 @@ def rsvd_hilbert_sharded_c64(ctx: Context, A: ResidentMatrix, k: int, p_total: i
     feature-sharded -- every pass streams the rank's REAL slice once, the Hilbert operator acts on the replicated sample-side
     panel.  Reference: single/eof.py:546-555 -> linalg/decomposer.py:149-160."""
     k = int(k)
-    omega, it, U, s, V = _c64_sharded_arguments(ctx, A, k, p_total, n_oversamples, n_iter, random_state, omega, device_out)
-    ctx._comm_err = None
-    rc = ctx.lib.eofx_rsvd_hilbert_sharded_c64(ctx.handle, A.handle, int(p_total), int(padding == "exp"), float(decay_factor), k,
-                                               int(n_oversamples), it, ptr(omega), int(flip), ptr(U), ptr(s), ptr(V))
-    if getattr(ctx, "_comm_err", None) is not None:
-        raise ctx._comm_err
+    omega, it, U, s, V = _c64_arguments(ctx, A, k, n_oversamples, n_iter, random_state, omega, device_out, p_total=p_total)
+    with _collective(ctx):
+        rc = ctx.lib.eofx_rsvd_hilbert_sharded_c64(ctx.handle, A.handle, int(p_total), int(padding == "exp"),
+                                                   float(decay_factor), k, int(n_oversamples), it, ptr(omega), int(flip), ptr(U),
+                                                   ptr(s), ptr(V))
     raise_for(rc, ctx.handle)
     return U, s, A.compact_rows(V[:A.p_phys])
 
@@ -1364,269 +1322,3 @@ def gwpca(ctx: Context, mat: ResidentMatrix, xy: np.ndarray, k: int, bandwidth: 
             agg[key] += st[key]
         agg["chunks"] += 1
     return comps, ev, tv, agg
-
-
-# --------------------------------------------------------------------------- #
-# sparse PCA by variable projection (eofx_spca_*_f64, csrc/eofx_spca.hpp)       #
-# --------------------------------------------------------------------------- #
-SPCA_KMAX = 64            # the loop kernels' limits (modes, columns of V); wider shapes take the general route
-SPCA_LMAX = 128
-SPCA_REGULARIZERS = {"l1": 0, "l0": 1}
-SPCA_GAMMA = 0.1          # outlier threshold of the robust route (compute_spca's default; the model never sets it)
-
-
-def _dev64(ctx: Context, a):
-    """a float64 C-contiguous device tensor of a numpy array / tensor"""
-    torch = _torch()
-    return torch.as_tensor(np.asarray(a) if not hasattr(a, "data_ptr") else a, dtype=torch.float64,
-                           device=f"cuda:{ctx.device}").contiguous()
-
-
-def spca_gram(ctx: Context, X, Y):
-    """X^T Y [a x b] (float64 device tensor) of two float64 device tensors of the same rows, summed in a fixed order"""
-    torch = _torch()
-    rows, a = X.shape
-    b = Y.shape[1]
-    out = torch.empty((a, b), dtype=torch.float64, device=X.device)
-    raise_for(ctx.lib.eofx_spca_gram_f64(ctx.handle, ptr(X), X.stride(0), a, ptr(Y), Y.stride(0) if Y.shape[0] > 1 else 0, b,
-                                         rows, ptr(out)), ctx.handle)
-    return out
-
-
-def spca_sum(ctx: Context, X, absolute: bool = False) -> float:
-    """sum of the entries (or of their absolute values) of a float64 device tensor in a fixed order"""
-    torch = _torch()
-    v = (X.abs() if absolute else X).reshape(-1, 1).contiguous()
-    one = torch.ones((1, 1), dtype=torch.float64, device=X.device)
-    return float(spca_gram(ctx, v, one).item())
-
-
-def spca_rowmul(ctx: Context, X, M):
-    """X [rows x a] M [a x b] -> [rows x b] float64 device tensor (M: host or device)"""
-    torch = _torch()
-    M = _dev64(ctx, M)
-    rows, a = X.shape
-    out = torch.empty((rows, M.shape[1]), dtype=torch.float64, device=X.device)
-    raise_for(ctx.lib.eofx_spca_rowmul_f64(ctx.handle, ptr(X), X.stride(0), a, ptr(M), M.shape[1], rows, ptr(out),
-                                           out.stride(0)), ctx.handle)
-    return out
-
-
-def spca_prox(ctx: Context, X, Y, s: float, regularizer: str, kappa: float, out=None):
-    """prox(X + s Y, kappa) elementwise (Y None: prox(X)); soft threshold for "l1", hard threshold for "l0" """
-    torch = _torch()
-    if out is None:
-        out = torch.empty_like(X)
-    raise_for(ctx.lib.eofx_spca_prox_f64(ctx.handle, ptr(X), ptr(Y), float(s), X.numel(), SPCA_REGULARIZERS[regularizer],
-                                         float(kappa), ptr(out)), ctx.handle)
-    return out
-
-
-def spca_orth(ctx: Context, T):
-    """-> (Q, R) with T = Q R, Q [rows x c] orthonormal (float64 device), R [c x c] host, rows >= c.  CholeskyQR2 on the
-    fixed-order Gram matrices; a (numerically) rank-deficient T takes the library's Householder QR instead."""
-    torch = _torch()
-    c = T.shape[1]
-    Q, R = T, np.eye(c)
-    for _ in range(2):
-        G = spca_gram(ctx, Q, Q).cpu().numpy()
-        try:
-            L = np.linalg.cholesky(G)
-        except np.linalg.LinAlgError:
-            L = None
-        d = None if L is None else np.abs(np.diag(L))
-        if L is None or not np.all(np.isfinite(L)) or d.min() <= 1e-6 * d.max():
-            Qh, Rh = torch.linalg.qr(T, mode="reduced")
-            return Qh.contiguous(), Rh.cpu().numpy()
-        Rs = L.T
-        Q = spca_rowmul(ctx, Q, np.linalg.inv(Rs))
-        R = Rs @ R
-    return Q, R
-
-
-def spca_svd(ctx: Context, Ct):
-    """thin SVD C = U diag(D) V^T of C given as Ct = C^T [p x m] (float64 device) -> (V [p x r] float64 device, D [r] host),
-    r = min(m, p), V's columns signed by the engine's rule (positive where |max| >= |min|)"""
-    p, m = Ct.shape
-    if m <= p:
-        Q, R = spca_orth(ctx, Ct)                   # C^T = Q R, R = U_R S W^T  ->  V = Q U_R
-        UR, D, _ = np.linalg.svd(R)
-        V = spca_rowmul(ctx, Q, UR)
-    else:
-        _, R = spca_orth(ctx, Ct.T.contiguous())    # C = Q R, R = U_R S W^T  ->  V = W
-        _, D, WT = np.linalg.svd(R)
-        V = _dev64(ctx, WT.T)
-    sign = (V.amax(dim=0).abs() >= V.amin(dim=0).abs()).to(V.dtype) * 2.0 - 1.0
-    return (V * sign).contiguous(), np.asarray(D, dtype=np.float64)
-
-
-def _spca_objective(D2, Qa, P, a2, b2, s1, s2):
-    r = (((Qa - P) ** 2).sum(axis=1) + 1.0 - (Qa ** 2).sum(axis=1)) @ D2
-    return 0.5 * r + a2 * s1 + 0.5 * b2 * s2
-
-
-def spca_solve(ctx: Context, Ct, k: int, alpha: float = 1e-3, beta: float = 1e-3, regularizer: str = "l1",
-               max_iter: int = 500, tol: float = 1e-6, check: bool = True, robust: bool = False):
-    """Variable projection on C given as Ct = C^T [p x m] (float64 device): compute_spca (_sparse_pca.py:383-563).
-    -> dict(B [p x k], A [p x k] (float64 device), dtilde [k], objective [n_iter], n_iter, route, ms)
-    route "kernel": the device loop (eofx_spca_loop_f64, k <= 64 and r <= 128); "general": the same iteration as fixed-order
-    products, the prox kernel and a host SVD of the small M; "robust": the robust variant on C itself."""
-    import time
-
-    torch = _torch()
-    if regularizer not in SPCA_REGULARIZERS:
-        raise ValueError(f'regularizer must be one of ("l1", "l0"), not {regularizer}.')
-    if robust and regularizer == "l0":
-        raise NotImplementedError("l0 regularization is not supported for robust sparse pca")
-    p, m = Ct.shape
-    k = int(k)
-    if k > p:
-        raise ValueError(f"n_components must be less than the number of columns of X ({p})")
-    t0 = time.perf_counter()
-    V, D = spca_svd(ctx, Ct)
-    r = V.shape[1]
-    if k > r:
-        raise ValueError(f"n_modes ({k}) exceeds the rank bound min(rows, columns) = {r} of the decomposed matrix")
-    torch.cuda.synchronize(ctx.device)
-    ms_setup = 1e3 * (time.perf_counter() - t0)
-    t0 = time.perf_counter()
-    if robust:
-        out = _spca_robust(ctx, Ct, V, D, k, alpha, beta, max_iter, tol, check)
-    elif k <= SPCA_KMAX and r <= SPCA_LMAX:
-        B = torch.empty((p, k), dtype=torch.float64, device=V.device)
-        Qa = np.empty((r, k))
-        dt = np.empty(k)
-        obj = np.empty(int(max_iter))
-        it = C.c_int()
-        raise_for(ctx.lib.eofx_spca_loop_f64(ctx.handle, ptr(V), p, r, ptr(D), k, float(alpha), float(beta),
-                                             SPCA_REGULARIZERS[regularizer], int(max_iter), float(tol), int(bool(check)),
-                                             ptr(B), ptr(Qa), ptr(dt), ptr(obj), C.byref(it)), ctx.handle)
-        out = dict(B=B, A=spca_rowmul(ctx, V, Qa), dtilde=dt, objective=obj[:it.value].copy(), n_iter=it.value, route="kernel")
-    else:
-        out = _spca_general(ctx, V, D, k, alpha, beta, regularizer, max_iter, tol, check)
-    torch.cuda.synchronize(ctx.device)
-    out["ms"] = dict(setup=ms_setup, loop=1e3 * (time.perf_counter() - t0))
-    return out
-
-
-def _spca_scaled(D, alpha, beta):
-    d0 = float(D[0]) ** 2
-    if not d0 > 0.0:
-        raise ValueError("the decomposed matrix is zero")
-    a2, b2 = alpha * d0, beta * d0
-    nu = 1.0 / (d0 + b2)
-    return a2, b2, nu, nu * a2
-
-
-def _spca_general(ctx, V, D, k, alpha, beta, regularizer, max_iter, tol, check):
-    """the iteration of the loop kernels for shapes beyond their limits: fixed-order products on the device, the small
-    polar factor on the host (LAPACK)"""
-    a2, b2, nu, kappa = _spca_scaled(D, alpha, beta)
-    D2 = D ** 2
-    B = V[:, :k].contiguous()
-    P = spca_gram(ctx, V, B).cpu().numpy()
-    obj = []
-    for it in range(int(max_iter)):
-        U, dt, WT = np.linalg.svd(D2[:, None] * P, full_matrices=False)
-        Qa = U @ WT
-        G = spca_rowmul(ctx, V, D2[:, None] * (Qa - P))
-        B = spca_prox(ctx, B, G - b2 * B, nu, regularizer, kappa)
-        P = spca_gram(ctx, V, B).cpu().numpy()
-        obj.append(_spca_objective(D2, Qa, P, a2, b2, spca_sum(ctx, B, True), spca_sum(ctx, B * B)))
-        if check and it > 0 and abs(obj[-2] - obj[-1]) / obj[-1] < tol:
-            break
-    return dict(B=B, A=spca_rowmul(ctx, V, Qa), dtilde=dt, objective=np.array(obj), n_iter=len(obj), route="general")
-
-
-def _spca_robust(ctx, Ct, V, D, k, alpha, beta, max_iter, tol, check):
-    """robust variant (_sparse_pca.py:497-550) with the outlier matrix S kept as S^T [p x m] on the device; the polar
-    factor of the tall Z through its k x k Gram matrix"""
-    a2, b2, nu, kappa = _spca_scaled(D, alpha, beta)
-    g = SPCA_GAMMA
-    B = V[:, :k].contiguous()
-    St = None
-    obj = []
-    for it in range(int(max_iter)):
-        XSt = Ct if St is None else Ct - St
-        XB = spca_gram(ctx, Ct, B)                               # C B        [m x k]
-        Z = spca_rowmul(ctx, XSt, XB)                            # (C - S)^T C B   [p x k]
-        w, E = np.linalg.eigh(spca_gram(ctx, Z, Z).cpu().numpy())
-        w, E = w[::-1], E[:, ::-1]
-        dt = np.sqrt(np.clip(w, 0.0, None))
-        inv = np.where(dt > dt[0] * 1e-12, 1.0 / np.where(dt > 0, dt, 1.0), 0.0) if dt[0] > 0 else np.zeros_like(dt)
-        A = spca_rowmul(ctx, Z, (E * inv) @ E.T)                 # polar(Z) = Z E S^-1 E^T
-        Rt = XSt - spca_rowmul(ctx, A, XB.T)                     # (C - S - C B A^T)^T
-        G = spca_rowmul(ctx, Ct, spca_gram(ctx, Rt, A)) - b2 * B  # C^T (R A) - beta B
-        B = spca_prox(ctx, B, G, nu, "l1", kappa)
-        Rt = Ct - spca_rowmul(ctx, A, spca_gram(ctx, Ct, B).T)
-        St = spca_prox(ctx, Rt, None, 0.0, "l1", g)
-        Rt = Rt - St
-        obj.append(0.5 * spca_sum(ctx, Rt * Rt) + a2 * spca_sum(ctx, B, True) + 0.5 * b2 * spca_sum(ctx, B * B)
-                   + g * spca_sum(ctx, St, True))
-        if check and it > 0 and abs(obj[-2] - obj[-1]) / obj[-1] < tol:
-            break
-    return dict(B=B, A=A, dtilde=dt, objective=np.array(obj), n_iter=len(obj), route="robust")
-
-
-def _spca_ops_resident(ctx: Context, mat: ResidentMatrix, rows=None):
-    """(mul, tmul) of the rows `rows` (a range, None = all) of a resident matrix on float64 device tensors through the
-    f32 panel products: mul(Z [p x c]) = X_b Z, tmul(Q [n_b x c]) = X_b^T Q"""
-    torch = _torch()
-    r0, r1 = (0, mat.n) if rows is None else rows
-
-    def mul(Z):
-        c = Z.shape[1]
-        Yp = torch.zeros((mat.p_pad, panel_width(c)), dtype=torch.float32, device=Z.device)
-        Yp[:mat.p, :c] = Z
-        return panel_mul(ctx, mat, Yp)[r0:r1, :c].to(torch.float64).contiguous()
-
-    def tmul(Q):
-        c = Q.shape[1]
-        Zn = torch.zeros((mat.n_pad, panel_width(c)), dtype=torch.float32, device=Q.device)
-        Zn[r0:r1, :c] = Q
-        return panel_tmul(ctx, mat, Zn)[:mat.p, :c].to(torch.float64).contiguous()
-
-    return mul, tmul
-
-
-def _spca_orth_cols(ctx, Y):
-    """an orthonormal basis of Y's column space as scipy's economic QR gives it: [rows x min(rows, c)]"""
-    rows, c = Y.shape
-    if rows <= c:
-        return _dev64(ctx, np.eye(rows))
-    return spca_orth(ctx, Y)[0]
-
-
-def _spca_qb(ctx, mul, tmul, p, l, n_subspace, omega):
-    """_compute_rqb (_sparse_pca.py:170-218) -> K^T = X^T Q [p x min(rows, l)] (float64 device)"""
-    Q = _spca_orth_cols(ctx, mul(omega))
-    for _ in range(int(n_subspace)):
-        Z = _spca_orth_cols(ctx, tmul(Q))
-        Q = _spca_orth_cols(ctx, mul(Z))
-    return tmul(Q)
-
-
-def spca_compress(ctx: Context, mat: ResidentMatrix, k: int, oversample: int = 10, n_subspace: int = 1, n_blocks: int = 1,
-                  random_state=None):
-    """compute_rqb (_sparse_pca.py:221-333) on the resident matrix -> C^T [p x m_c] (float64 device) of the compressed
-    matrix C = Q^T X.  The sketch Omega = standard_normal((p, k + oversample)) is engine.sketch_matrix's draw (an integer
-    seed re-seeds at every draw, as check_random_state does).  n_blocks > 1: a QB per block of sample rows through the
-    full-matrix products on row-sliced / zero-padded panels, then a QB of the stacked block outputs (fixed-order float64
-    products)."""
-    l = int(k) + int(oversample)
-    p = mat.p
-    if int(n_blocks) <= 1:
-        mul, tmul = _spca_ops_resident(ctx, mat)
-        return _spca_qb(ctx, mul, tmul, p, l, n_subspace, _dev64(ctx, sketch_matrix(p, l, random_state)))
-    torch = _torch()
-    bounds = np.array_split(np.arange(mat.n), int(n_blocks))
-    Kt = []
-    for b in bounds:
-        if b.size == 0:
-            continue
-        mul, tmul = _spca_ops_resident(ctx, mat, (int(b[0]), int(b[-1]) + 1))
-        Kt.append(_spca_qb(ctx, mul, tmul, p, l, n_subspace, _dev64(ctx, sketch_matrix(p, l, random_state))))
-    Kt = torch.cat(Kt, dim=1).contiguous()                      # K^T [p x sum of the block ranks]
-    mul = lambda Z: spca_gram(ctx, Kt, Z)                        # K Z
-    tmul = lambda Q: spca_rowmul(ctx, Kt, Q)                     # K^T Q
-    return _spca_qb(ctx, mul, tmul, p, l, n_subspace, _dev64(ctx, sketch_matrix(p, l, random_state)))

@@ -17,6 +17,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .engine import _sketch
+
 
 class Comm:
     """Collectives over torch.distributed (nccl == RCCL on ROCm; gloo on CPU)."""
@@ -246,20 +248,14 @@ def rsvd_auto_iters(k, n, p):
 def _resolve_sketch(k, r, n_oversamples, omega, random_state):
     """sketch width policy shared by the drivers: l = min(k + n_oversamples, rank); a full-width sketch
     spans everything, so the identity replaces an (occasionally ill-conditioned) square Gaussian"""
-    from .engine import sketch_matrix
-
     if k > r:
         raise ValueError(f"n_modes must be less than or equal to the rank of the dataset (rank = {r}).")
     l_req = k + n_oversamples
     l = min(l_req, r)
-    if omega is None:
-        omega = sketch_matrix(r, l_req, random_state)
-    elif hasattr(omega, "result"):          # an engine.SketchFuture: joined here
-        omega = omega.result()
-    omega = np.ascontiguousarray(omega[:, :l], dtype=np.float32)
-    if l == r:
-        omega = np.eye(r, dtype=np.float32)
-    return omega, l
+    # the caller's matrix (or an engine.SketchFuture) is resolved even where the identity replaces it, and taken as it comes:
+    # the drivers slice the rows and columns they need
+    omega = _sketch(r, l_req, omega, random_state, identity_when_full=True, exact_rows=None, resolve_first=True)
+    return np.ascontiguousarray(omega[:, :l]), l
 
 
 def _orth_tall(tall_total: int, L: int, prec_power: str = "f16x3") -> bool:

@@ -3,7 +3,7 @@ variable projection [Erichson et al. 2020], minimising 1/2 |X - X B A^T|^2 + alp
 
 The randomized route compresses the preprocessed field to C = Q^T X (compute_rqb) with the engine's panel products; the
 exact route decomposes X itself.  Either way the iteration runs on the device in float64 from the thin SVD of C
-(engine.spca_solve, csrc/eofx_spca.hpp): for k <= 64 modes and at most 128 singular vectors each iteration is one streaming
+(spca.spca_solve, csrc/eofx_spca.hpp): for k <= 64 modes and at most 128 singular vectors each iteration is one streaming
 pass over V and B plus a single-workgroup step, and the host reads a finished flag once per 16 iterations.
 
 Deliberate deviations from the reference:
@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .. import engine, labelled
+from .. import engine, labelled, spca
 from .eof import EOF
 
 VALID_SOLVERS = ("auto", "full", "randomized")
@@ -53,7 +53,7 @@ class SparsePCA(EOF):
             raise TypeError("This method does not support complex data.")
         if prm["solver"] not in VALID_SOLVERS:
             raise ValueError(f"Unrecognized solver '{prm['solver']}'. Valid options are 'auto', 'full', and 'randomized'.")
-        if prm["regularizer"] not in engine.SPCA_REGULARIZERS:
+        if prm["regularizer"] not in spca.SPCA_REGULARIZERS:
             raise ValueError(f'regularizer must be one of ("l1", "l0"), not {prm["regularizer"]}.')
         if prm["robust"] and prm["regularizer"] == "l0":
             raise NotImplementedError("l0 regularization is not supported for robust sparse pca")
@@ -82,13 +82,13 @@ class SparsePCA(EOF):
             raise ValueError(f"n_components must be less than the number of columns of X ({p})")
         exact = self.use_exact(n, p)
         if exact:
-            Ct = engine._dev64(self.ctx, mat.download()).T.contiguous()        # X^T [p x n]
+            Ct = spca._dev64(self.ctx, mat.download()).T.contiguous()        # X^T [p x n]
         else:
-            Ct = engine.spca_compress(self.ctx, mat, k, prm["oversample"], prm["n_subspace"], prm["n_blocks"],
-                                      prm["random_state"])
+            Ct = spca.spca_compress(self.ctx, mat, k, prm["oversample"], prm["n_subspace"], prm["n_blocks"],
+                                    prm["random_state"])
         m_c = Ct.shape[1]
-        res = engine.spca_solve(self.ctx, Ct, k, prm["alpha"], prm["beta"], prm["regularizer"], prm["max_iter"], prm["tol"],
-                                check=bool(prm["compute"]), robust=bool(prm["robust"]))
+        res = spca.spca_solve(self.ctx, Ct, k, prm["alpha"], prm["beta"], prm["regularizer"], prm["max_iter"], prm["tol"],
+                              check=bool(prm["compute"]), robust=bool(prm["robust"]))
         del Ct
         ev = explained_variance(res["dtilde"], n, m_c, k, prm["oversample"], exact)
         B = res["B"].to(dtype=engine._torch().float32).cpu().numpy()
