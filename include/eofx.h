@@ -505,6 +505,14 @@ int eofx_spca_rowmul_f64(eofx_ctx *ctx, const double *X, int64_t ldx, int a, con
  * hard threshold, zero where x^2 < 2 kappa (l0)                                                                       */
 int eofx_spca_prox_f64(eofx_ctx *ctx, const double *X, const double *Y, double s, int64_t count, int regularizer, double kappa,
                        double *out);
+/* ---- lag-summed covariance of optimal persistence analysis (xeofs/single/opa.py:104-171, csrc/eofx_lagcov.hpp) -------
+ * M [p x p] (device, row-major, float64) = sum_{tau < ntau} w[tau] sum_{t < n - tau} S[t, i] S[t + tau, j] for the float32
+ * device panel S [n x p] with row stride ld >= p and the float64 weights w [ntau] (host|device).  The reference's
+ * ntau products of shifted windows are ONE filter along the samples, Y[t] = sum_tau w[tau] S[t + tau] (rows past n count
+ * as zero), and ONE cross-product M = S^T Y on the fp64 matrix cores; Y stays in LDS for ntau <= 65 and is written once
+ * beyond.  Float64 arithmetic, no atomics, fixed summation order.  EOFX_ERR_ARG unless n >= 2, 1 <= ntau <= n - 1 (the
+ * largest lag leaves two samples) and p >= 1; EOFX_ERR_SHAPE for p > 1024.                                             */
+int eofx_lagcov_f64(eofx_ctx *ctx, const float *S, int64_t n, int p, int64_t ld, const double *w, int ntau, double *M);
 /* Gram matrix of a resident matrix (float32, device): side 0 = sample space G[n_pad x n_pad] = X X^T,
  * side 1 = feature space G[p_pad x p_pad] = X^T X (rows/columns beyond n / p are zero).  Used for
  * (a) the total squared covariance sum(|X^T Y|^2) = <X X^T, Y Y^T> (cross/cpcca.py:991-1000) when X and

@@ -11,6 +11,7 @@
 #include "eofx_lag.hpp"
 #include "eofx_gw.hpp"
 #include "eofx_spca.hpp"
+#include "eofx_lagcov.hpp"
 #ifndef EOFX_AXB_DMA_DEFAULT
 #define EOFX_AXB_DMA_DEFAULT 1
 #endif
@@ -6754,5 +6755,51 @@ extern "C" int eofx_spca_prox_f64(eofx_ctx* ctx, const double* X, const double* 
   hipLaunchKernelGGL(spca_prox_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, X, Y, s, count, regularizer,
                      kappa, out);
   KCHK();
+  return EOFX_OK;
+}
+
+// ---- lag-summed covariance of optimal persistence analysis (csrc/eofx_lagcov.hpp) --------------------------------------
+extern "C" int eofx_lagcov_f64(eofx_ctx* ctx, const float* S, int64_t n, int p, int64_t ld, const double* w, int ntau, double* M) {
+  if (!ctx || !S || !w || !M) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (n < 2 || ld < p) return set_err(ctx, EOFX_ERR_ARG, "n must be >= 2 and ld >= p (n = %lld, p = %d, ld = %lld)", (long long)n, p, (long long)ld);
+  if (p < 1) return set_err(ctx, EOFX_ERR_ARG, "p must be >= 1, got %d", p);
+  if (p > LAGCOV_PMAX) return set_err(ctx, EOFX_ERR_SHAPE, "the lag covariance kernels take p <= %d, got %d", LAGCOV_PMAX, p);
+  if (ntau < 1 || (int64_t)ntau > n - 1)
+    return set_err(ctx, EOFX_ERR_ARG, "ntau must be in [1, n - 1 = %lld] (the largest lag leaves two samples), got %d", (long long)(n - 1), ntau);
+  if (!is_device_ptr(S) || !is_device_ptr(M)) return set_err(ctx, EOFX_ERR_ARG, "S and M must be device buffers");
+  ENTER(ctx);
+  const bool fused = ntau <= LAGCOV_FUSE_NTAU;
+  const int nb = (p + 63) / 64, ny = nb * ((nb + 3) / 4);
+  const int64_t ntiles = (n + LAGCOV_R - 1) / LAGCOV_R;
+  const int G = (int)std::min<int64_t>(ntiles, std::max(1, LAGCOV_WGS / ny));      // a function of the shape alone
+  const size_t nw = (size_t)ntau + 2 * LAGCOV_PADW, pp = (size_t)p * p;
+  CHK(arena_reserve(ctx, (nw + pp * G + (fused ? 0 : (size_t)n * p)) * 8 + 3 * 256));
+  ArenaScope scope(ctx);
+  ARENA(double, wpad, nw);
+  ARENA(double, part, pp * G);
+  double* Y = nullptr;
+  HIPCHK(hipMemsetAsync(wpad, 0, nw * 8, ctx->stream));
+  HIPCHK(hipMemcpyAsync(wpad + LAGCOV_PADW, w, (size_t)ntau * 8, is_device_ptr(w) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                        ctx->stream));
+  if (fused) {
+    const size_t lds = LAGCOV_LDS_Y + LAGCOV_LDS_S;
+    HIPCHK(hipFuncSetAttribute((const void*)lagcov_cross_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(lagcov_cross_kernel<true>, dim3((unsigned)G, (unsigned)ny), dim3(256), lds, ctx->stream, S, n, p, ld,
+                       (const double*)wpad, ntau, (const double*)nullptr, part);
+  } else {
+    Y = arena_alloc<double>(ctx, (size_t)n * p);
+    if (!Y) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (Y)");
+    const int64_t threads = (n + LAGCOV_WIN - 1) / LAGCOV_WIN * p;
+    hipLaunchKernelGGL(lagcov_fir_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, S, n, p, ld,
+                       (const double*)wpad, ntau, Y);
+    KCHK();
+    hipLaunchKernelGGL(lagcov_cross_kernel<false>, dim3((unsigned)G, (unsigned)ny), dim3(256), LAGCOV_LDS_Y, ctx->stream, S, n, p,
+                       ld, (const double*)wpad, ntau, (const double*)Y, part);
+  }
+  KCHK();
+  hipLaunchKernelGGL(f64_reduce_kernel, dim3((unsigned)((pp + 63) / 64)), dim3(256), 0, ctx->stream, (const double*)part, M,
+                     (int64_t)pp, G);
+  KCHK();
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // (w may be a pageable host buffer; the arena is handed back)
   return EOFX_OK;
 }

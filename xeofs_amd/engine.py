@@ -1322,3 +1322,31 @@ def gwpca(ctx: Context, mat: ResidentMatrix, xy: np.ndarray, k: int, bandwidth: 
             agg[key] += st[key]
         agg["chunks"] += 1
     return comps, ev, tv, agg
+
+
+# --------------------------------------------------------------------------- #
+# lag-summed covariance of optimal persistence analysis (eofx_lagcov_f64, csrc/eofx_lagcov.hpp)   #
+# --------------------------------------------------------------------------- #
+LAGCOV_PMAX = 1024        # columns the kernels take
+LAGCOV_FUSE_NTAU = 65     # up to here the filtered panel stays in LDS; beyond, it is written once
+
+
+def lagcov(ctx: Context, S, w):
+    """M [p x p] = sum_tau w[tau] S[:n - tau]^T S[tau:] (float64 device tensor) of a float32 panel S [n x p] -- a host
+    array or a device tensor, whose row stride may exceed p -- and the weights w [ntau] of the lags 0 .. ntau - 1
+    (opa.py:104-171 as one filter along the samples and one cross-product)"""
+    torch = _torch()
+    dev = f"cuda:{ctx.device}"
+    if not hasattr(S, "data_ptr"):
+        S = torch.from_numpy(_f32c(S)).to(dev)
+    if S.dim() != 2:
+        raise ValueError(f"S must be a matrix, got {S.dim()} dimensions")
+    if S.dtype != torch.float32 or S.stride(1) != 1 or S.stride(0) < S.shape[1]:
+        S = S.to(torch.float32).contiguous()
+    n, p = S.shape
+    w = np.ascontiguousarray(w.detach().cpu().numpy() if hasattr(w, "detach") else w, dtype=np.float64)
+    if w.ndim != 1:
+        raise ValueError(f"w must be a vector of lag weights, got shape {w.shape}")
+    M = torch.empty((p, p), dtype=torch.float64, device=S.device)
+    raise_for(ctx.lib.eofx_lagcov_f64(ctx.handle, ptr(S), n, p, S.stride(0), ptr(w), w.size, ptr(M)), ctx.handle)
+    return M
