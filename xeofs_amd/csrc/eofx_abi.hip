@@ -1599,6 +1599,7 @@ static int run_colstats(eofx_ctx* ctx, const float* Xd, int64_t n, int64_t P, in
   ARENA(double, sq_p, (size_t)RS * P);
   ARENA(float, mn_p, (size_t)RS * P);
   ARENA(float, mx_p, (size_t)RS * P);
+  ARENA(float, csh, (size_t)round_up(P, 4));   // provisional shift of the sums (colstats_shift_kernel)
   // the Hilbert stage follows (eofx_ctx_set_sample_raw) and its one-kernel route takes this length two features at a time:
   // the pass also writes the raw field in the sample-contiguous layout (instead of a separate transposing copy behind the statistics pass)
   if (vec4 && !row_map && ctx->want_rawT && ctx->keep_raw == 2 && !ctx->pending_rawT && round_up(n, ATB_BM) <= 8192 && rps % 64 == 0) {
@@ -1610,19 +1611,21 @@ static int run_colstats(eofx_ctx* ctx, const float* Xd, int64_t n, int64_t P, in
       ctx->pending_rawT = nullptr;
     }
   }
+  hipLaunchKernelGGL(colstats_shift_kernel, dim3(gxs), dim3(256), 0, ctx->stream, Xd, n, P, ld, row_map, csh);
+  KCHK();
   if (vec4 && ctx->pending_rawT && !row_map && ctx->want_rawT)
-    hipLaunchKernelGGL(colstats_tr_kernel, dim3((unsigned)((P + 63) / 64), (int)RS), dim3(256), 0, ctx->stream, Xd, n, P, ld, rps, cnt_p,
+    hipLaunchKernelGGL(colstats_tr_kernel, dim3((unsigned)((P + 63) / 64), (int)RS), dim3(256), 0, ctx->stream, Xd, n, P, ld, rps, csh, cnt_p,
                        sum_p, sq_p, mn_p, mx_p, ctx->pending_rawT, round_up(n, ATB_BM));
   else if (vec4)
     hipLaunchKernelGGL(colstats4_kernel, dim3(gx, (int)RS), dim3(256), 0, ctx->stream, Xd, n, P, ld, row_map, rps,
-                       cnt_p, sum_p, sq_p, mn_p, mx_p);
+                       csh, cnt_p, sum_p, sq_p, mn_p, mx_p);
   else
     hipLaunchKernelGGL(colstats_kernel, dim3(gx, (int)RS), dim3(256), 0, ctx->stream, Xd, n, P, ld, row_map, rps,
-                       cnt_p, sum_p, sq_p, mn_p, mx_p);
+                       csh, cnt_p, sum_p, sq_p, mn_p, mx_p);
   KCHK();
   HIPCHK(hipMemsetAsync(ps.absmax, 0, sizeof(unsigned), ctx->stream));
   hipLaunchKernelGGL(colstats_finalize_kernel, dim3(gxs), dim3(256), 0, ctx->stream, cnt_p, sum_p, sq_p, mn_p, mx_p,
-                     (int)RS, P, center, standardize, w_dev, (double)1.1920928955078125e-07, ps.cnt,
+                     csh, (int)RS, P, center, standardize, w_dev, (double)1.1920928955078125e-07, ps.cnt,
                      ps.mean, ps.stdv, ps.shift, ps.scale, ps.m2, ps.absmax, ps.vmin, ps.vmax);
   KCHK();
   return EOFX_OK;
@@ -1660,7 +1663,7 @@ static size_t colstats_scratch(int64_t n, int64_t P) {
   const int64_t gx = std::max<int64_t>(1, (P / 4 + 255) / 256);   // the four-features-per-thread kernel: fewer workgroups, more row splits
   int64_t RS = std::max<int64_t>(1, (2048 + gx - 1) / gx);      // (fewer than four features: gx was 0 -- a division by zero, round 5)
   RS = std::min<int64_t>(RS, std::max<int64_t>(1, n / 64));
-  return (size_t)(RS + 1) * P * 32 + (size_t)P * 64 + (size_t)n * 16 + (1 << 20);
+  return (size_t)(RS + 1) * P * 32 + (size_t)P * 72 + (size_t)n * 16 + (1 << 20);
 }
 
 // shared tail of preprocess/apply: NaN policy, maps, allocation, apply kernel

@@ -1955,16 +1955,37 @@ __global__ __launch_bounds__(256) void panel_import_kernel(const float* __restri
 
 // ---------------------------------------------------------------------------------
 // Fused preprocessor (Scaler + Sanitizer), HBM-bound.
-//   colstats : NaN-aware count / sum / sum of squares per feature in float64,
+//   colstats : NaN-aware count / sum / sum of squares (about a provisional shift) per feature in float64,
 //              one thread per feature column, rows split over gridDim.y.
 //   finalize : combine row-splits in fixed order -> mean, std, shift, scale, variance term.
 //   rowcount : valid-feature count per sample (only launched when samples are missing).
 //   apply    : gather valid rows/cols, (x - shift) * scale, write X and X^T zero padded.
 // ---------------------------------------------------------------------------------
+// The sums are taken about a provisional per-feature shift c (colstats_shift_kernel: the first finite value among nine
+// probe rows, 0 if there is none): s = sum (x - c), q = sum (x - c)^2, and colstats_finalize_kernel forms
+// mean = c + s / k, M2 = q - s^2 / k.  Summed about 0, M2 = q - s mu loses |mean|^2 / var times the rounding of the sums
+// -- 1e-3 of std for a float32 field whose offset is 1e6 standard deviations; about c the sums hold only the spread.
+__global__ __launch_bounds__(256) void colstats_shift_kernel(const float* __restrict__ X, int64_t n, int64_t P, int64_t ld,
+                                                              const int64_t* __restrict__ row_map, float* __restrict__ cshift) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= P) return;
+  float s = 0.f;
+  for (int t = 0; t < 9; ++t) {
+    const int64_t r = t == 8 ? n - 1 : (n * t) / 8;
+    const float v = X[(row_map ? row_map[r] : r) * ld + c];
+    if (fabsf(v) < INFINITY) {     // (false for NaN)
+      s = v;
+      break;
+    }
+  }
+  cshift[c] = s;
+}
+
 __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__ X, int64_t n,
                                                         int64_t P, int64_t ld,
                                                         const int64_t* __restrict__ row_map,
                                                         int64_t rows_per_split,
+                                                        const float* __restrict__ cshift,
                                                         int* __restrict__ cnt,
                                                         double* __restrict__ sum,
                                                         double* __restrict__ sumsq,
@@ -1976,6 +1997,7 @@ __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__
   const int64_t r1 = (r0 + rows_per_split < n) ? r0 + rows_per_split : n;
   int k = 0;
   double s = 0.0, q = 0.0;
+  const double cs = (double)cshift[c];
   float lo = INFINITY, hi = -INFINITY;   // fminf/fmaxf skip NaN
   // row_map (bootstrap resampling: source row of every logical row) is wave-uniform -> scalar loads
   int64_t r = r0;
@@ -1991,7 +2013,7 @@ __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__
       lo = fminf(lo, v[u]);
       hi = fmaxf(hi, v[u]);
       if (v[u] == v[u]) {
-        const double d = (double)v[u];
+        const double d = (double)v[u] - cs;
         ++k;
         s += d;
         q += d * d;
@@ -2004,7 +2026,7 @@ __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__
     lo = fminf(lo, v);
     hi = fmaxf(hi, v);
     if (v == v) {
-      const double d = (double)v;
+      const double d = (double)v - cs;
       ++k;
       s += d;
       q += d * d;
@@ -2022,7 +2044,7 @@ __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__
 // row instead of 256 B).  P % 4 == 0, ld % 4 == 0, X 16-byte aligned.  Rows are summed in the same order per split.
 __global__ __launch_bounds__(256) void colstats4_kernel(const float* __restrict__ X, int64_t n, int64_t P, int64_t ld,
                                                          const int64_t* __restrict__ row_map, int64_t rows_per_split,
-                                                         int* __restrict__ cnt, double* __restrict__ sum,
+                                                         const float* __restrict__ cshift, int* __restrict__ cnt, double* __restrict__ sum,
                                                          double* __restrict__ sumsq, float* __restrict__ vmin,
                                                          float* __restrict__ vmax) {
   const int64_t c = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
@@ -2032,13 +2054,15 @@ __global__ __launch_bounds__(256) void colstats4_kernel(const float* __restrict_
   int k[4] = {0, 0, 0, 0};
   double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
   float lo[4] = {INFINITY, INFINITY, INFINITY, INFINITY}, hi[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  const f32x4 cs4 = *reinterpret_cast<const f32x4*>(cshift + c);
+  const double cs[4] = {(double)cs4[0], (double)cs4[1], (double)cs4[2], (double)cs4[3]};
   auto take = [&](const f32x4& v) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       lo[e] = fminf(lo[e], v[e]);      // fminf / fmaxf skip NaN
       hi[e] = fmaxf(hi[e], v[e]);
       if (v[e] == v[e]) {
-        const double d = (double)v[e];
+        const double d = (double)v[e] - cs[e];
         ++k[e];
         s[e] += d;
         q[e] += d * d;
@@ -2079,7 +2103,8 @@ __global__ __launch_bounds__(256) void colstats4_kernel(const float* __restrict_
 // Xt [P][n_pad].  At the end the 16 row groups of a feature meet in LDS in a fixed order: one partial per (split, feature),
 // as colstats4_kernel leaves them.  P % 4 == 0, rows_per_split % 64 == 0.  The values written are the RAW ones.
 __global__ __launch_bounds__(256) void colstats_tr_kernel(const float* __restrict__ X, int64_t n, int64_t P, int64_t ld,
-                                                           int64_t rows_per_split, int* __restrict__ cnt, double* __restrict__ sum,
+                                                           int64_t rows_per_split, const float* __restrict__ cshift,
+                                                           int* __restrict__ cnt, double* __restrict__ sum,
                                                            double* __restrict__ sumsq, float* __restrict__ vmin,
                                                            float* __restrict__ vmax, float* __restrict__ Xt, int64_t n_pad) {
   __shared__ float T[64][65];
@@ -2093,6 +2118,8 @@ __global__ __launch_bounds__(256) void colstats_tr_kernel(const float* __restric
   int k[4] = {0, 0, 0, 0};
   double s[4] = {0.0, 0.0, 0.0, 0.0}, qq[4] = {0.0, 0.0, 0.0, 0.0};
   float lo[4] = {INFINITY, INFINITY, INFINITY, INFINITY}, hi[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  const f32x4 cs4 = live ? *reinterpret_cast<const f32x4*>(cshift + cb) : f32x4{0.f, 0.f, 0.f, 0.f};
+  const double cs[4] = {(double)cs4[0], (double)cs4[1], (double)cs4[2], (double)cs4[3]};
   for (int64_t r0 = rs0; r0 < rs1; r0 += 64) {
     f32x4 v[4];
 #pragma unroll
@@ -2111,7 +2138,7 @@ __global__ __launch_bounds__(256) void colstats_tr_kernel(const float* __restric
           lo[e] = fminf(lo[e], x);      // fminf / fmaxf skip NaN
           hi[e] = fmaxf(hi[e], x);
           if (x == x) {
-            const double d = (double)x;
+            const double d = (double)x - cs[e];
             ++k[e];
             s[e] += d;
             qq[e] += d * d;
@@ -2181,7 +2208,7 @@ __global__ __launch_bounds__(256) void colstats_tr_kernel(const float* __restric
 __global__ __launch_bounds__(256) void colstats_finalize_kernel(
     const int* __restrict__ cnt_p, const double* __restrict__ sum_p,
     const double* __restrict__ sumsq_p, const float* __restrict__ vmin_p,
-    const float* __restrict__ vmax_p, int splits, int64_t P, int center, int standardize,
+    const float* __restrict__ vmax_p, const float* __restrict__ cshift, int splits, int64_t P, int center, int standardize,
     const double* __restrict__ weights, double eps, int* __restrict__ cnt, double* __restrict__ mean,
     double* __restrict__ stdv, double* __restrict__ shift, double* __restrict__ scale,
     double* __restrict__ m2, unsigned* __restrict__ absmax, float* __restrict__ vmin_out = nullptr,
@@ -2206,8 +2233,9 @@ __global__ __launch_bounds__(256) void colstats_finalize_kernel(
   }
   double mu = NAN, sd = NAN, M2 = 0.0;
   if (k > 0) {
-    mu = s / k;
-    M2 = q - s * mu;
+    const double ds = s / k;           // the sums are about cshift: mean - cshift
+    mu = (double)cshift[c] + ds;
+    M2 = q - s * ds;
     if (M2 < 0.0) M2 = 0.0;
     sd = sqrt(M2 / k);
     if (sd < eps) sd = eps;
