@@ -212,9 +212,9 @@ class NumpyComplexOps:
         return self.torch.from_numpy(a.T @ a)
 
     def right_mul(self, P, M):
-        from xeofs_amd.complex_svd import _embed_right
+        from xeofs_amd.cpanel import embed
 
-        return self.torch.from_numpy((P.numpy().astype(np.float64) @ _embed_right(M)).astype(np.float32))
+        return self.torch.from_numpy((P.numpy().astype(np.float64) @ embed(M, 32)).astype(np.float32))
 
     def matmul_real(self, P, E):
         return self.torch.from_numpy((P.numpy().astype(np.float64) @ np.asarray(E, dtype=np.float64)).astype(np.float32))

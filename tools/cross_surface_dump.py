@@ -1,7 +1,8 @@
 """Every array the public surface of the cross models and their rotators returns, on fixed synthetic fields, into one
 .npz -- to compare two checkouts bit for bit (`cross_surface_dump.py OUT.npz`, then `--compare A.npz B.npz`).
 Fits CPCCA over alpha x use_pca, MCA / CCA / RDA, ComplexCPCCA / ComplexMCA, HilbertMCA with and without padding, and a
-rotator (power 1 and 2) on one model of each kind; EOF / ComplexEOF ride along for `inverse_transform`."""
+rotator (power 1 and 2) on one model of each kind; EOF / ComplexEOF ride along for `inverse_transform`; then the panel-level
+complex drivers (`panel_level`)."""
 import os
 import sys
 import warnings
@@ -24,6 +25,52 @@ def compare(a, b):
             if A[k].dtype != B[k].dtype or not np.array_equal(A[k], B[k], equal_nan=A[k].dtype.kind in "fc")]
     print(f"cross_surface_dump: {len(A.files)} / {len(B.files)} arrays, {len(bad)} differ" + (": " + ", ".join(bad) if bad else ""))
     return 1 if bad else 0
+
+
+def panel_level(record, rng):
+    """The drivers under the complex models that work on [Re | Im] panels (xeofs_amd/cpanel.py) and that the models above reach
+    only at one width and orientation: the Python panel route of the complex decomposition at both orientations, both panel
+    widths and with more modes than rank (the null-mode repair), the complex PCA pre-reduction with either side small, and
+    the complex rotation with its finishing step at 32 and 64 columns per half."""
+    from xeofs_amd import engine, rotation
+    from xeofs_amd.complex_svd import complex_rsvd
+    from xeofs_amd.cpca import ComplexResidentPCA
+
+    ctx = engine.default_context()
+
+    def resident(n, p, rank, noise):
+        def c(*shape):
+            return rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
+        Z = (c(n, rank) * (5.0 * 0.8 ** np.arange(rank))) @ c(rank, p) + noise * c(n, p)
+        Z = Z - Z.mean(axis=0)
+        return [engine.from_dense(ctx, np.ascontiguousarray(part, dtype=np.float32)) for part in (Z.real, Z.imag)]
+
+    for n, p, k, over, rank, noise in ((60, 700, 5, 10, 6, 0.3), (700, 60, 5, 10, 6, 0.3), (60, 700, 30, 10, 6, 0.3),
+                                       (60, 700, 20, None, 8, 0.0)):
+        A, B = resident(n, p, rank, noise)
+        kw = {} if over is None else dict(n_oversamples=over)
+        U, s, V = complex_rsvd(ctx, A, B, k, random_state=11, **kw)
+        record(f"complex_rsvd.{n}x{p}.k{k}", (U, s, V))
+        if not noise:
+            print(f"cross_surface_dump: complex_rsvd {n}x{p} k={k}: {int((s <= 3e-6 * s[0]).sum())} null modes repaired")
+        A.free()
+        B.free()
+    for n, p in ((50, 400), (400, 50)):
+        A, B = resident(n, p, 6, 0.3)
+        pca = ComplexResidentPCA(ctx).fit(A, B)
+        Q = rng.standard_normal((pca.m, 4)) + 1j * rng.standard_normal((pca.m, 4))
+        record(f"ComplexResidentPCA.{n}x{p}", (pca.scores(), pca.s, pca.singular_values_all, pca.transform(A, B),
+                                               pca.back_project(Q), pca.components()))
+        A.free()
+        B.free()
+    for m in (3, 40):
+        p = 333
+        load = (rng.standard_normal((p, m)) + 1j * rng.standard_normal((p, m))) * (rng.random_sample((p, m)) < 0.2)
+        load = load + 0.05 * (rng.standard_normal((p, m)) + 1j * rng.standard_normal((p, m)))
+        for power in (1, 2):
+            Xrot, p_, m_, rot_mat, phi = rotation.cpromax_panel(ctx, load, power=power, col_scale=np.linspace(2.0, 1.0, m))
+            record(f"cpromax_panel.m{m}.p{power}",
+                   (Xrot[:p].cpu().numpy(), rot_mat, phi) + rotation.cfinish_on_device(ctx, Xrot, p_, m_))
 
 
 def main(out_path):
@@ -126,6 +173,7 @@ def main(out_path):
     surface("EOF", S.EOF(n_modes=3, random_state=7).fit(X, "time"), (Xn,))
     surface("ComplexEOF", S.ComplexEOF(n_modes=3, random_state=7).fit(Zx, "time"))
     surface("HilbertEOF", S.HilbertEOF(n_modes=3, random_state=7).fit(X, "time"))
+    panel_level(record, rng)
     np.savez(out_path, **out)
     print(f"cross_surface_dump: wrote {len(out)} arrays to {out_path}")
     return 0

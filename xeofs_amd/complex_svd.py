@@ -4,7 +4,7 @@ reference hands to scipy's svds(lobpcg)).
 
 Every pass over the data is one launch of the streaming kernel in its two-matrix form
 (`eofx_cmat_mul_f32`; other precisions than the default: one launch per part + a recombination
-kernel) on a 64-wide real panel holding [Re | Im] of a complex panel of up to 32 columns.  Orthonormalisation is a complex
+kernel) on a 64-wide [Re | Im] panel (`cpanel`) of up to 32 complex columns.  Orthonormalisation is a complex
 Cholesky-free QR from the Hermitian Gram matrix (one 64x64 float64 Gram of the real panel gives
 all four blocks); the l x l Hermitian eigen-problems are solved on the host in float64.
 
@@ -18,30 +18,11 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import engine
+from . import cpanel, engine
 
 HALF = 32          # complex panels are [Re(32 cols) | Im(32 cols)]; sketches of 33 .. 64 columns: [Re(64) | Im(64)]
 LP = 2 * HALF
 MAX_HALF = 64
-
-
-def _embed_right(M, half=HALF):
-    """real (2 half) x (2 half) matrix E with [Pr|Pi] @ E = [Re(P M) | Im(P M)] for complex M (l x m, padded)."""
-    E = np.zeros((2 * half, 2 * half))
-    l, m = M.shape
-    E[:l, :m] = M.real
-    E[half:half + l, :m] = -M.imag
-    E[:l, half:half + m] = M.imag
-    E[half:half + l, half:half + m] = M.real
-    return E
-
-
-def _hermitian_gram(G, l, half=HALF):
-    """complex l x l Gram P^H P from the real Gram of [Pr|Pi]."""
-    rr, ri = G[:l, :l], G[:l, half:half + l]
-    ir, ii = G[half:half + l, :l], G[half:half + l, half:half + l]
-    H = (rr + ii) + 1j * (ri - ir)
-    return 0.5 * (H + H.conj().T)
 
 
 class ComplexOps:
@@ -84,7 +65,7 @@ class ComplexOps:
 
     def right_mul(self, P, M):
         torch = engine._torch()
-        return engine.panel_matmul(self.ctx, P, torch.as_tensor(_embed_right(M, self.half), device=P.device))
+        return engine.panel_matmul(self.ctx, P, torch.as_tensor(cpanel.embed(M, self.half), device=P.device))
 
     def matmul_real(self, P, E):             # P [rows x L] (any multiple of 64 columns) times the real matrix E [L x Lo]
         torch = engine._torch()
@@ -156,15 +137,9 @@ def _block_krylov(ops, comm, Z0, q, l, half, small, tall, fwd, bwd, gram, orth, 
             G = comm.sum_(G)
         return G.detach().cpu().numpy() if torch.is_tensor(G) else np.asarray(G)
 
-    def cblock(G, r0, c0):                       # complex l x l block of a real Gram matrix at (r0, c0)
-        rr, ri = G[r0:r0 + l, c0:c0 + l], G[r0:r0 + l, c0 + half:c0 + half + l]
-        ir, ii = G[r0 + half:r0 + half + l, c0:c0 + l], G[r0 + half:r0 + half + l, c0 + half:c0 + half + l]
-        return (rr + ii) + 1j * (ri - ir)
-
     def cholqr(P, side, dref=None, tolref=0.0):
         """Cholesky-QR with the dependency rules of eofx_rsvd_c64 -> (Q, R, live columns)"""
-        Hm = cblock(real_gram(P, side), 0, 0)
-        Hm = 0.5 * (Hm + Hm.conj().T)
+        Hm = cpanel.block(real_gram(P, side), l, half, hermitian=True)
         d0 = Hm.diagonal().real.copy()
         A = Hm.copy()
         dead = np.zeros(l, bool)
@@ -186,7 +161,7 @@ def _block_krylov(ops, comm, Z0, q, l, half, small, tall, fwd, bwd, gram, orth, 
         return ops.right_mul(P, T), R, int(live.sum()), d0
 
     def embed_stack(blocks):                     # real (len(blocks) lp) x lp matrix applying complex l x l blocks on the right
-        return np.concatenate([_embed_right(c, half) for c in blocks], axis=0)
+        return np.concatenate([cpanel.embed(c, half) for c in blocks], axis=0)
 
     def assemble(nbr, nWr, last=None):
         """H = K^H M K over the first nbr blocks from the products of the first nWr ones (+ the last diagonal block)"""
@@ -195,7 +170,7 @@ def _block_krylov(ops, comm, Z0, q, l, half, small, tall, fwd, bwd, gram, orth, 
         raw = {}
         for i in range(nWr):
             for j in range(nbr):
-                cb = cblock(G, j * lp, (nbr + i) * lp)
+                cb = cpanel.block(G, l, half, j * lp, (nbr + i) * lp)
                 raw[(j, i)] = cb if Rf[i] is None else cb @ Rf[i]
         if last is not None:
             raw[(nbr - 1, nbr - 1)] = last
@@ -233,18 +208,18 @@ def _block_krylov(ops, comm, Z0, q, l, half, small, tall, fwd, bwd, gram, orth, 
         nbk = len(K)
         Kc = torch.cat(K, dim=1)
         G = real_gram(torch.cat([Kc, Wb], dim=1), small)
-        c = [cblock(G, b * lp, nbk * lp) for b in range(nbk)]
+        c = [cpanel.block(G, l, half, b * lp, nbk * lp) for b in range(nbk)]
         if it == 0 and not orth_tall and q > 1:
             H00 = c[0] if Rf[0] is None else c[0] @ Rf[0]
             wv = np.linalg.eigvalsh(0.5 * (H00 + H00.conj().T))
             orth_rest = not (wv[0] > 0.0) or np.sqrt(wv[-1] / wv[0]) > 30.0
         V1 = ops.matmul_real(torch.cat([Kc, Wb], dim=1), np.concatenate([-embed_stack(c), np.eye(lp)], axis=0))
-        Gv = cblock(real_gram(V1, small), 0, 0)
+        Gv = cpanel.block(real_gram(V1, small), l, half)
         dref = Gv.diagonal().real + sum((np.abs(cb) ** 2).sum(axis=0) for cb in c)
         Zn, _, live, _ = cholqr(V1, small, dref, 1e-10)
         if live > 0:
             G2 = real_gram(torch.cat([Kc, Zn], dim=1), small)
-            c2 = [cblock(G2, b * lp, nbk * lp) for b in range(nbk)]
+            c2 = [cpanel.block(G2, l, half, b * lp, nbk * lp) for b in range(nbk)]
             V2 = ops.matmul_real(torch.cat([Kc, Zn], dim=1), np.concatenate([-embed_stack(c2), np.eye(lp)], axis=0))
             Zn, _, live, _ = cholqr(V2, small, np.ones(l), 0.25)
         if live == 0:
@@ -279,8 +254,7 @@ def _block_krylov(ops, comm, Z0, q, l, half, small, tall, fwd, bwd, gram, orth, 
     Hqq = None
     if not exhausted:
         Y = fwd(K[-1])
-        Gq = cblock(real_gram(Y, tall), 0, 0)
-        Hqq = 0.5 * (Gq + Gq.conj().T)
+        Hqq = cpanel.block(real_gram(Y, tall), l, half, hermitian=True)
         if orth_rest:
             Y, R, _, _ = cholqr(Y, tall)
             Rf.append(R)
@@ -312,7 +286,7 @@ def _fix_null_small(P, rows, k, first, half):
     is not) -- the host algorithm of the engine entry (csrc/eofx_abi.hip, rsvd_c64_impl); values and the tall side are untouched."""
     torch = engine._torch()
     h = P.detach().cpu().numpy() if torch.is_tensor(P) else np.asarray(P)
-    Z = h[:rows, :k].astype(np.complex128) + 1j * h[:rows, half:half + k].astype(np.complex128)
+    Z = cpanel.unpack(h, rows, k, half, np.complex128)
 
     def project_out(v, upto):
         for _ in range(2):
@@ -339,9 +313,7 @@ def _fix_null_small(P, rows, k, first, half):
             nn = 0.0
         nrm = float(np.linalg.norm(v))
         Z[:, j] = v / nrm if nrm > 0.0 else 0.0
-    out = h.copy()
-    out[:rows, first:k] = Z[:, first:k].real.astype(np.float32)
-    out[:rows, half + first:half + k] = Z[:, first:k].imag.astype(np.float32)
+    out = cpanel.pack(Z[:, first:k], half, out=h.copy(), c0=first)
     if torch.is_tensor(P):
         return torch.as_tensor(out, device=P.device)
     return out
@@ -391,7 +363,7 @@ def complex_rsvd(ctx, A, B, k: int, n_oversamples: int = 10, n_iter="auto", rand
         G = ops.gram_real(P)
         if side == "p":
             G = comm.sum_(G)
-        return _hermitian_gram(G.detach().cpu().numpy(), l, half)
+        return cpanel.block(G.detach().cpu().numpy(), l, half, hermitian=True)
 
     def orth(P, side):
         """Q = P (V diag(w^-1/2)), P^H P = V diag(w) V^H; dependent directions -> zero columns"""
@@ -454,21 +426,14 @@ def complex_rsvd(ctx, A, B, k: int, n_oversamples: int = 10, n_iter="auto", rand
     if flip:
         # VT = conj(V)^T; numpy's max/min of complex arrays are lexicographic (real part, then imag),
         # ties on the real part are measure-zero.  Global over the feature shards.
-        torch = engine._torch()
         amax, amin = ops.argminmax(Vp, p_loc)
-        cols = torch.arange(k)
-        cand = []
-        for idx in (amax[:k].cpu(), amin[:k].cpu()):
-            if p_loc > 0:
-                vr = Vp[idx, cols].detach().cpu().numpy().astype(np.float64)
-                vi = Vp[idx, cols + half].detach().cpu().numpy().astype(np.float64)
-            else:
-                vr, vi = np.full(k, np.nan), np.zeros(k)
-            cand.append((vr, -vi))          # conj flips the imaginary part
-        (mr, mi), (nr, ni) = cand
+        if p_loc > 0:
+            cand = cpanel.lex_extrema(Vp, amax, amin, k, half, conj=True)
+        else:                               # an empty shard takes no part in the gather: NaN real parts
+            cand = np.full(k, np.nan), np.zeros(k), np.full(k, np.nan), np.zeros(k)
         if comm.world > 1:
-            mr, mi, nr, ni = _global_lex_extrema(comm, mr, mi, nr, ni)
-        sign = np.where(np.hypot(mr, mi) >= np.hypot(nr, ni), 1.0, -1.0)
+            cand = _global_lex_extrema(comm, *cand)
+        sign = cpanel.lex_sign(*cand)
     sg = np.concatenate([sign, np.ones(half - k), sign, np.ones(half - k)])
 
     def export(P, rows):
@@ -476,11 +441,7 @@ def complex_rsvd(ctx, A, B, k: int, n_oversamples: int = 10, n_iter="auto", rand
         (the 64-wide panel of a 1M-row factor is 265 MB; its k complex columns are 166 MB at k = 20)"""
         torch = engine._torch()
         if not torch.is_tensor(P) or rows == 0:
-            full = ops.export(P, rows, sg)
-            out = np.empty((rows, k), dtype=np.complex64)
-            out.real = full[:, :k]
-            out.imag = full[:, half:half + k]
-            return out
+            return cpanel.unpack(ops.export(P, rows, sg), rows, k, half, np.complex64)
         sgt = torch.as_tensor(sign, dtype=torch.float32, device=P.device)
         z = torch.stack((P[:rows, :k] * sgt, P[:rows, half:half + k] * sgt), dim=-1)     # [rows, k, 2]
         out = engine._host_out((rows, k), np.complex64)

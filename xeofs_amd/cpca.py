@@ -11,8 +11,8 @@ Same exact route as the real `xeofs_amd.pca.ResidentPCA`, with Hermitian algebra
   3. P = Z^H E_m (two wide products on the parts + recombination) and a Rayleigh-Ritz step on P^H P (float64 Gram of
      the real [Re | Im] panel, m x m Hermitian eigh): singular values / vectors accurate to float32 rounding.
 
-A complex panel of m columns is a real [rows_pad, 2 Lh] panel, Lh = round_up(m, 32): columns [0, m) real parts,
-[Lh, Lh + m) imaginary parts.  V stays resident; scores U s live on the host (n x m complex128).
+Complex panels are the [Re | Im] real panels of `cpanel`, Lh = round_up(m, 32) columns per half.  V stays resident; scores
+U s live on the host (n x m complex128).
 With more samples than features the Gram matrix is Z^H Z (features x features) and the roles of the two sides swap.
 """
 
@@ -22,27 +22,8 @@ import warnings
 
 import numpy as np
 
-from . import engine
+from . import cpanel, engine
 from .pca import ResidentPCA, _round32
-
-
-def embed_right(M, Lh_in, Lh_out):
-    """real (2 Lh_in x 2 Lh_out) matrix E with [Pr | Pi] @ E = [Re(P M) | Im(P M)] for a complex M (l x m)"""
-    l, m = M.shape
-    E = np.zeros((2 * Lh_in, 2 * Lh_out))
-    E[:l, :m] = M.real
-    E[Lh_in:Lh_in + l, :m] = -M.imag
-    E[:l, Lh_out:Lh_out + m] = M.imag
-    E[Lh_in:Lh_in + l, Lh_out:Lh_out + m] = M.real
-    return E
-
-
-def hermitian_from_real_gram(G, Lh, m):
-    """complex m x m Gram P^H P from the real (2 Lh x 2 Lh) Gram of [Pr | Pi]"""
-    rr, ri = G[:m, :m], G[:m, Lh:Lh + m]
-    ir, ii = G[Lh:Lh + m, :m], G[Lh:Lh + m, Lh:Lh + m]
-    H = (rr + ii) + 1j * (ri - ir)
-    return 0.5 * (H + H.conj().T)
 
 
 def _eigh_desc(H):
@@ -97,30 +78,26 @@ class ComplexResidentPCA(ResidentPCA):
         dev = f"cuda:{ctx.device}"
         Es = torch.zeros((A.n_pad if side == 0 else A.p_pad, 2 * Lh), dtype=torch.float32, device=dev)
         Em = np.ascontiguousarray(E[:, :m])      # (BLAS needs plain strides: a sliced / reversed view multiplies 100x slower)
-        Es[:r, :m] = torch.as_tensor(Em.real, dtype=torch.float32)
-        Es[:r, Lh:Lh + m] = torch.as_tensor(Em.imag, dtype=torch.float32)
+        cpanel.pack(Em, Lh, out=Es)
         pr = ctx.precision[1]
         if side == 0:      # tall side = features: P = Z^H E_m
             P = engine.cpanel_combine(ctx, engine.panel_tmul(ctx, A, Es, prec=pr), engine.panel_tmul(ctx, B, Es, prec=pr), True)
         else:              # tall side = samples:  P = Z E_m
             P = engine.cpanel_combine(ctx, engine.panel_mul(ctx, A, Es, prec=pr), engine.panel_mul(ctx, B, Es, prec=pr), False)
-        H = hermitian_from_real_gram(engine.panel_gram(ctx, P).cpu().numpy(), Lh, m)
+        H = cpanel.block(engine.panel_gram(ctx, P).cpu().numpy(), m, Lh, hermitian=True)
         th, W = _eigh_desc(torch.as_tensor(H, device=dev) if m >= 512 else H)
         th, W = np.clip(th, 0.0, None), np.ascontiguousarray(W)
         s = np.sqrt(th)
         tiny = th[0] * 1e-14 if m else 0.0
         inv = np.where(th > tiny, 1.0 / np.sqrt(np.maximum(th, 1e-300)), 0.0)
-        Tall = engine.panel_matmul(ctx, P, torch.as_tensor(embed_right(W * inv, Lh, Lh), device=P.device))   # rows_pad x 2 Lh
+        Tall = engine.panel_matmul(ctx, P, torch.as_tensor(cpanel.embed(W * inv, Lh), device=P.device))   # rows_pad x 2 Lh
         del P
         Small = Em @ W                                          # r x m complex128, orthonormal
         if side == 0:
             self.Vp, self.U = Tall, Small                       # V: p_pad x 2 Lh panel, U: n x m
         else:                                                   # features are the small side: V = E_m W, U = the tall side
-            Vp = torch.zeros((A.p_pad, 2 * Lh), dtype=torch.float32, device=dev)
-            Vp[:p, :m] = torch.as_tensor(Small.real, dtype=torch.float32)
-            Vp[:p, Lh:Lh + m] = torch.as_tensor(Small.imag, dtype=torch.float32)
-            t = Tall[:n].double().cpu().numpy()
-            self.Vp, self.U = Vp, t[:, :m] + 1j * t[:, Lh:Lh + m]
+            Vp = cpanel.pack(Small, Lh, out=torch.zeros((A.p_pad, 2 * Lh), dtype=torch.float32, device=dev))
+            self.Vp, self.U = Vp, cpanel.unpack(Tall, n, m, Lh, np.complex128)
         self.s = s
         self.m, self.Lh, self.n, self.p, self.p_pad = m, Lh, n, p, A.p_pad
         self.singular_values_all = np.sqrt(lam)
@@ -137,8 +114,7 @@ class ComplexResidentPCA(ResidentPCA):
         pr = self.ctx.precision[1]
         out = engine.cpanel_combine(self.ctx, engine.panel_mul(self.ctx, A_new, self.Vp, prec=pr),
                                     engine.panel_mul(self.ctx, B_new, self.Vp, prec=pr), False)
-        o = out[:A_new.n].double().cpu().numpy()
-        return o[:, :self.m] + 1j * o[:, self.Lh:self.Lh + self.m]
+        return cpanel.unpack(out, A_new.n, self.m, self.Lh, np.complex128)
 
     def back_project(self, Q):
         """V Q (p x k complex64): components from PC space back to feature space (pca.py:158-168)"""
@@ -146,14 +122,8 @@ class ComplexResidentPCA(ResidentPCA):
         Q = np.asarray(Q, dtype=np.complex128)
         k = Q.shape[1]
         Lk = _round32(k)
-        out = engine.panel_matmul(self.ctx, self.Vp, torch.as_tensor(embed_right(Q, self.Lh, Lk), device=self.Vp.device))
-        o = out[:self.p].cpu().numpy()
-        res = np.empty((self.p, k), np.complex64)
-        res.real, res.imag = o[:, :k], o[:, Lk:Lk + k]
-        return res
+        out = engine.panel_matmul(self.ctx, self.Vp, torch.as_tensor(cpanel.embed(Q, self.Lh, Lk), device=self.Vp.device))
+        return cpanel.unpack(out, self.p, k, Lk, np.complex64)
 
     def components(self):
-        o = self.Vp[:self.p].cpu().numpy()
-        res = np.empty((self.p, self.m), np.complex64)
-        res.real, res.imag = o[:, :self.m], o[:, self.Lh:self.Lh + self.m]
-        return res
+        return cpanel.unpack(self.Vp, self.p, self.m, self.Lh, np.complex64)

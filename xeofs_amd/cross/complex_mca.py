@@ -29,7 +29,7 @@ import warnings
 
 import numpy as np
 
-from .. import __version__, engine, labelled, rotation
+from .. import __version__, cpanel, engine, labelled, rotation
 from .._deferred import Deferred
 from ..cpca import ComplexResidentPCA
 from ..linalg.decomposer import sanity_check_n_modes
@@ -405,22 +405,11 @@ class ComplexCPCCARotator(ComplexPairSurface, CrossRotator):
 
     def _panel_sign(self, Xrot, ptot, k):
         """numpy's lexicographic complex max / min on the [Re | Im] panel"""
-        torch = engine._torch()
-        CH = Xrot.shape[1] // 2
         amax, amin = engine.panel_colargminmax(self.ctx, Xrot, ptot)
-        cols = torch.arange(k, device=Xrot.device)
-        pick = lambda ix: (Xrot[ix[:k], cols].double().cpu().numpy(), Xrot[ix[:k], cols + CH].double().cpu().numpy())
-        (mr, mi), (nr, ni) = pick(amax), pick(amin)
-        return np.where(np.hypot(mr, mi) >= np.hypot(nr, ni), 1.0, -1.0)
+        return cpanel.lex_sign(*cpanel.lex_extrema(Xrot, amax, amin, k, Xrot.shape[1] // 2))
 
     def _export(self, Xrot, lo, hi, idx, w):
-        CH, k = Xrot.shape[1] // 2, idx.size
-        M = np.zeros((k, k), dtype=complex)
-        M[idx, np.arange(k)] = w
-        blk = engine.panel_matmul(self.ctx, Xrot[lo:], rotation._dev(rotation._cembed(M, CH), Xrot))[:hi - lo].cpu().numpy()
-        c = np.empty((hi - lo, k), np.complex64)
-        c.real, c.imag = blk[:, :k], blk[:, CH:CH + k]
-        return c
+        return cpanel.permute_export(self.ctx, Xrot[lo:], hi - lo, idx, w, Xrot.shape[1] // 2)
 
     def _unrotated_scores(self, which, Z, k):
         un = self.model.transform(**{"XY"[which - 1]: Z})          # unrotated scores: data . back-projected components

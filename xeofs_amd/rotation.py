@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import engine
+from . import cpanel, engine
 
 MAX_ROT_MODES = 256
 FUSED_ROT_MODES = 64      # widest panel of the single-workgroup step kernel (wider ones: its column-blocked variant)
@@ -128,7 +128,7 @@ def finish_on_device(ctx, Xrot, p, m):
 # complex loadings (the rotation of ComplexEOF / HilbertEOF models, xeofs/single/eof_rotator.py:294-400; `_promax` /
 # `_varimax` "also work for complex numbers", _rotation.py:16,105)
 # ---------------------------------------------------------------------------------------------------------------------
-CH = 32            # complex panels of the fused step: [Re (32 columns) | Im (32 columns)]
+CH = 32            # complex columns per half of the fused step's [Re | Im] panel (`cpanel`)
 MAX_CROT_MODES = 128
 
 
@@ -137,32 +137,14 @@ def _cwidth(m):
     return CH if m <= CH else (64 if m <= 64 else 128)
 
 
-def _cembed(M, ch=CH):
-    """real (2 ch) x (2 ch) matrix E with [Pr | Pi] @ E = [Re(P M) | Im(P M)] for a complex m x m' matrix M"""
-    l, m = M.shape
-    E = np.zeros((2 * ch, 2 * ch))
-    E[:l, :m] = M.real
-    E[ch:ch + l, :m] = -M.imag
-    E[:l, ch:ch + m] = M.imag
-    E[ch:ch + l, ch:ch + m] = M.real
-    return E
-
-
-def _cblocks(G, m, ch=CH):
-    """X^H T (complex m x m) from the real product [Xr | Xi]^T [Tr | Ti]"""
-    rr, ri = G[:m, :m], G[:m, ch:ch + m]
-    ir, ii = G[ch:ch + m, :m], G[ch:ch + m, ch:ch + m]
-    return (rr + ii) + 1j * (ri - ir)
-
-
 def _crot_step(ctx, X, R, auxh, mode, power, ch, m):
     """One step of the complex loop on the [Re | Im] panel X: the complex m x m matrix X^H (b (|b|^2 - aux)) (mode 2) or
     b^H ((b / aux) (|b| / aux)^(power-1)) (mode 3), b = X R -- modes 2 / 3 of `eofx_panel_rot_step_f64` with R in its real
     embedding, for 32, 64 or 128 columns per half."""
     aux = np.zeros(2 * ch) if mode == 2 else np.ones(2 * ch)
     aux[:m] = aux[ch:ch + m] = auxh
-    G = engine.panel_rot_step(ctx, X, _dev(_cembed(R, ch), X), _dev(aux, X), mode, float(power))
-    return _cblocks(G.cpu().numpy(), m, ch)
+    G = engine.panel_rot_step(ctx, X, _dev(cpanel.embed(R, ch), X), _dev(aux, X), mode, float(power))
+    return cpanel.block(G.cpu().numpy(), m, ch)
 
 
 def cpromax_panel(ctx, loadings: np.ndarray, power: int = 1, max_iter: int = 1000, rtol: float = 1e-8, col_scale=None):
@@ -177,16 +159,11 @@ def cpromax_panel(ctx, loadings: np.ndarray, power: int = 1, max_iter: int = 100
     if m > MAX_CROT_MODES:
         raise NotImplementedError(f"rotation of more than {MAX_CROT_MODES} complex modes is not supported by this build")
     ch = _cwidth(m)
-    L = 2 * ch
-    rows_pad = (p + 511) // 512 * 512
-    host = np.zeros((p, L), np.float32)
-    host[:, :m], host[:, ch:ch + m] = loadings.real, loadings.imag
-    Lp = engine.panel_import(ctx, host, rows_pad, L)
-    del host
+    Lp = engine.panel_import(ctx, cpanel.pack(loadings, ch), (p + 511) // 512 * 512, 2 * ch)
     if col_scale is not None:
-        Lp = engine.panel_matmul(ctx, Lp, _dev(_cembed(np.diag(np.asarray(col_scale, dtype=np.float64)).astype(complex), ch), Lp))
+        Lp = engine.panel_matmul(ctx, Lp, _dev(cpanel.embed(np.diag(np.asarray(col_scale, dtype=np.float64)).astype(complex), ch), Lp))
     Xn = engine.panel_row_normalize(ctx, Lp)                       # Kaiser: rows / (sqrt(sum |x|^2) + eps)
-    S = _cblocks(engine.panel_gram(ctx, Xn).cpu().numpy(), m, ch)  # X^H X
+    S = cpanel.block(engine.panel_gram(ctx, Xn).cpu().numpy(), m, ch)   # X^H X
     S = 0.5 * (S + S.conj().T)
     R = np.eye(m, dtype=complex)
     alpha = 1.0 / p
@@ -205,7 +182,7 @@ def cpromax_panel(ctx, loadings: np.ndarray, power: int = 1, max_iter: int = 100
     rot_mat = R
     phi = np.eye(m, dtype=complex)
     if power != 1:
-        B = engine.panel_matmul(ctx, Xn, _dev(_cembed(R, ch), Xn)) # X R (normalised, rotated)
+        B = engine.panel_matmul(ctx, Xn, _dev(cpanel.embed(R, ch), Xn))   # X R (normalised, rotated)
         cmax = engine.cpanel_colabsmax(ctx, B, p).cpu().numpy()[:m].astype(np.float64)
         XtP = _crot_step(ctx, Xn, R, cmax, 3, float(power), ch, m)
         XtX = R.conj().T @ S @ R
@@ -218,7 +195,7 @@ def cpromax_panel(ctx, loadings: np.ndarray, power: int = 1, max_iter: int = 100
         rot_mat = R @ Lm
         L_inv = np.linalg.inv(Lm)
         phi = L_inv @ L_inv.conj().T
-    Xrot = engine.panel_matmul(ctx, Lp, _dev(_cembed(rot_mat, ch), Lp))   # (h Xn) rot_mat = loadings rot_mat
+    Xrot = engine.panel_matmul(ctx, Lp, _dev(cpanel.embed(rot_mat, ch), Lp))   # (h Xn) rot_mat = loadings rot_mat
     return Xrot, p, m, rot_mat, phi
 
 
@@ -226,19 +203,11 @@ def cfinish_on_device(ctx, Xrot, p, m):
     """`finish_on_device` for a complex [Re | Im] panel: explained variance = column sums of |x|^2, order, unit-norm
     components, the reference's +-1 sign from numpy's lexicographic complex max / min (real part decides; ties on it are
     measure-zero).  -> (components [p, m] complex64 host, expvar (unsorted), idx, sign (unsorted))."""
-    torch = engine._torch()
-    CH = Xrot.shape[1] // 2
+    ch = Xrot.shape[1] // 2
     Gd = np.diag(engine.panel_gram(ctx, Xrot).cpu().numpy())
-    expvar = (Gd[:m] + Gd[CH:CH + m]).copy()
+    expvar = (Gd[:m] + Gd[ch:ch + m]).copy()
     idx = np.argsort(expvar)[::-1]
     amax, amin = engine.panel_colargminmax(ctx, Xrot, p)
-    cols = torch.arange(m, device=Xrot.device)
-    pick = lambda ix: (Xrot[ix[:m], cols].double().cpu().numpy(), Xrot[ix[:m], cols + CH].double().cpu().numpy())
-    (mr, mi), (nr, ni) = pick(amax), pick(amin)
-    sign = np.where(np.hypot(mr, mi) >= np.hypot(nr, ni), 1.0, -1.0)
-    M = np.zeros((m, m), dtype=complex)                   # column j of the output = column idx[j], scaled and signed
-    M[idx, np.arange(m)] = sign[idx] / np.sqrt(expvar[idx])
-    out = engine.panel_matmul(ctx, Xrot, _dev(_cembed(M, CH), Xrot))[:p].cpu().numpy()
-    comps = np.empty((p, m), np.complex64)
-    comps.real, comps.imag = out[:, :m], out[:, CH:CH + m]
+    sign = cpanel.lex_sign(*cpanel.lex_extrema(Xrot, amax, amin, m, ch))
+    comps = cpanel.permute_export(ctx, Xrot, p, idx, sign[idx] / np.sqrt(expvar[idx]), ch)
     return comps, expvar, idx, sign
