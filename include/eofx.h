@@ -513,6 +513,16 @@ int eofx_spca_prox_f64(eofx_ctx *ctx, const double *X, const double *Y, double s
  * beyond.  Float64 arithmetic, no atomics, fixed summation order.  EOFX_ERR_ARG unless n >= 2, 1 <= ntau <= n - 1 (the
  * largest lag leaves two samples) and p >= 1; EOFX_ERR_SHAPE for p > 1024.                                             */
 int eofx_lagcov_f64(eofx_ctx *ctx, const float *S, int64_t n, int p, int64_t ld, const double *w, int ntau, double *M);
+/* ---- PC-space product of principal oscillation pattern analysis (xeofs/single/pop.py:185-198, csrc/eofx_pcmul.hpp) ---
+ * Y [rows x b] = X [rows x a] M [a x b]: X a device panel of float32 or float64 (x_dtype) with row stride ldx >= a, M
+ * float64 row-major (host|device), Y a device panel of float64 or float32 (y_dtype) with row stride ldy >= b.  Accumulated
+ * in float64 on the fp64 matrix cores, every output summed over k ascending in a fixed order without atomics, and rounded
+ * once.  rows == 0 is a no-op.  EOFX_ERR_ARG unless a >= 1, b >= 1, rows >= 0, ldx >= a, ldy >= b and both types are one
+ * of the two codes; EOFX_ERR_SHAPE for a > 1024 or b > 2048.                                                           */
+#define EOFX_PCMUL_F32 0
+#define EOFX_PCMUL_F64 1
+int eofx_pcmul_f64(eofx_ctx *ctx, const void *X, int x_dtype, int64_t rows, int a, int64_t ldx, const double *M, int b, void *Y,
+                   int y_dtype, int64_t ldy);
 /* Gram matrix of a resident matrix (float32, device): side 0 = sample space G[n_pad x n_pad] = X X^T,
  * side 1 = feature space G[p_pad x p_pad] = X^T X (rows/columns beyond n / p are zero).  Used for
  * (a) the total squared covariance sum(|X^T Y|^2) = <X X^T, Y Y^T> (cross/cpcca.py:991-1000) when X and

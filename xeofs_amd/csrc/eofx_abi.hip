@@ -12,6 +12,7 @@
 #include "eofx_gw.hpp"
 #include "eofx_spca.hpp"
 #include "eofx_lagcov.hpp"
+#include "eofx_pcmul.hpp"
 #ifndef EOFX_AXB_DMA_DEFAULT
 #define EOFX_AXB_DMA_DEFAULT 1
 #endif
@@ -6804,5 +6805,49 @@ extern "C" int eofx_lagcov_f64(eofx_ctx* ctx, const float* S, int64_t n, int p, 
                      (int64_t)pp, G);
   KCHK();
   HIPCHK(hipStreamSynchronize(ctx->stream));       // (w may be a pageable host buffer; the arena is handed back)
+  return EOFX_OK;
+}
+
+// ---- PC-space product of principal oscillation pattern analysis (csrc/eofx_pcmul.hpp) ----------------------------------
+template <class TX, class TY>
+static void launch_pcmul(eofx_ctx* ctx, const void* X, int64_t rows, int a, int64_t ldx, const double* M, int b, void* Y, int64_t ldy) {
+  const dim3 grid((unsigned)((rows + PCMUL_R - 1) / PCMUL_R), (unsigned)((b + PCMUL_C - 1) / PCMUL_C));      // a function of the shape alone
+  hipLaunchKernelGGL((pcmul_kernel<TX, TY>), grid, dim3(256), 0, ctx->stream, (const TX*)X, rows, a, ldx, M, b, (TY*)Y, ldy);
+}
+
+extern "C" int eofx_pcmul_f64(eofx_ctx* ctx, const void* X, int x_dtype, int64_t rows, int a, int64_t ldx, const double* M, int b,
+                              void* Y, int y_dtype, int64_t ldy) {
+  if (!ctx) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if ((x_dtype != EOFX_PCMUL_F32 && x_dtype != EOFX_PCMUL_F64) || (y_dtype != EOFX_PCMUL_F32 && y_dtype != EOFX_PCMUL_F64))
+    return set_err(ctx, EOFX_ERR_ARG, "x_dtype and y_dtype must be EOFX_PCMUL_F32 or EOFX_PCMUL_F64, got %d and %d", x_dtype, y_dtype);
+  if (a < 1 || b < 1 || rows < 0) return set_err(ctx, EOFX_ERR_ARG, "a and b must be >= 1 and rows >= 0 (a = %d, b = %d, rows = %lld)", a, b, (long long)rows);
+  if (a > PCMUL_AMAX || b > PCMUL_BMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the PC-space product takes a <= %d and b <= %d, got a = %d, b = %d", PCMUL_AMAX, PCMUL_BMAX, a, b);
+  if (ldx < a || ldy < b)
+    return set_err(ctx, EOFX_ERR_ARG, "ldx >= a and ldy >= b are required (a = %d, ldx = %lld, b = %d, ldy = %lld)", a, (long long)ldx, b, (long long)ldy);
+  if ((rows + PCMUL_R - 1) / PCMUL_R > (int64_t)INT32_MAX) return set_err(ctx, EOFX_ERR_SHAPE, "too many rows for one launch: %lld", (long long)rows);
+  if (rows == 0) return EOFX_OK;                   // (an empty panel has no buffer to name)
+  if (!X || !M || !Y) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (!is_device_ptr(X) || !is_device_ptr(Y)) return set_err(ctx, EOFX_ERR_ARG, "X and Y must be device buffers");
+  ENTER(ctx);
+  const bool host_m = !is_device_ptr(M);
+  ArenaScope scope(ctx);
+  const double* Md = M;
+  if (host_m) {
+    const size_t ab = (size_t)a * b;
+    CHK(arena_reserve(ctx, ab * 8 + 256));
+    ARENA(double, Mc, ab);
+    HIPCHK(hipMemcpyAsync(Mc, M, ab * 8, hipMemcpyHostToDevice, ctx->stream));
+    Md = Mc;
+  }
+  if (x_dtype == EOFX_PCMUL_F32) {
+    if (y_dtype == EOFX_PCMUL_F32) launch_pcmul<float, float>(ctx, X, rows, a, ldx, Md, b, Y, ldy);
+    else launch_pcmul<float, double>(ctx, X, rows, a, ldx, Md, b, Y, ldy);
+  } else {
+    if (y_dtype == EOFX_PCMUL_F32) launch_pcmul<double, float>(ctx, X, rows, a, ldx, Md, b, Y, ldy);
+    else launch_pcmul<double, double>(ctx, X, rows, a, ldx, Md, b, Y, ldy);
+  }
+  KCHK();
+  if (host_m) HIPCHK(hipStreamSynchronize(ctx->stream));       // (M may be a pageable host buffer; the arena is handed back)
   return EOFX_OK;
 }

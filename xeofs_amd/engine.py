@@ -1351,3 +1351,48 @@ def lagcov(ctx: Context, S, w):
     M = torch.empty((p, p), dtype=torch.float64, device=S.device)
     raise_for(ctx.lib.eofx_lagcov_f64(ctx.handle, ptr(S), n, p, S.stride(0), ptr(w), w.size, ptr(M)), ctx.handle)
     return M
+
+
+# --------------------------------------------------------------------------- #
+# PC-space product of principal oscillation pattern analysis (eofx_pcmul_f64, csrc/eofx_pcmul.hpp)   #
+# --------------------------------------------------------------------------- #
+PCMUL_AMAX = 1024         # inner length the kernel takes (the PCA modes)
+PCMUL_BMAX = 2048         # columns of the small matrix
+
+
+def pcmul(ctx: Context, X, M, out_dtype=None, out=None):
+    """Y [rows x b] = X [rows x a] M [a x b], accumulated in float64 on the matrix cores and rounded once to `out_dtype`
+    (torch.float64, the default, or torch.float32) -- a device tensor.  X: a float32 or float64 panel, a host array or a
+    device tensor whose row stride may exceed a; M: float64, a host array or a device tensor; `out`: a device tensor
+    [rows x b] to write, whose row stride may exceed b."""
+    torch = _torch()
+    dev = f"cuda:{ctx.device}"
+    if not hasattr(X, "data_ptr"):
+        X = np.asarray(X)
+        X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64 if X.dtype == np.float64 else np.float32)).to(dev)
+    if X.dim() != 2:
+        raise ValueError(f"X must be a matrix, got {X.dim()} dimensions")
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.to(torch.float32)
+    rows, a = X.shape
+    if rows and (X.stride(1) != 1 or X.stride(0) < a):
+        X = X.contiguous()
+    if hasattr(M, "data_ptr"):
+        M = M.to(torch.float64).contiguous()
+    else:
+        M = np.ascontiguousarray(M, dtype=np.float64)
+    if M.ndim != 2 or M.shape[0] != a:
+        raise ValueError(f"M must be a matrix of {a} rows, got shape {tuple(M.shape)}")
+    b = M.shape[1]
+    if out is None:
+        out_dtype = torch.float64 if out_dtype is None else out_dtype
+        if out_dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
+        out = torch.empty((rows, b), dtype=out_dtype, device=X.device)
+    elif (not hasattr(out, "data_ptr") or tuple(out.shape) != (rows, b) or out.dtype not in (torch.float32, torch.float64)
+          or (rows and (out.stride(1) != 1 or out.stride(0) < b))):
+        raise ValueError(f"out must be a float32 or float64 device tensor of shape ({rows}, {b}) with unit column stride")
+    code = {torch.float32: 0, torch.float64: 1}      # EOFX_PCMUL_F32 | EOFX_PCMUL_F64
+    raise_for(ctx.lib.eofx_pcmul_f64(ctx.handle, ptr(X), code[X.dtype], rows, a, X.stride(0) if rows else a, ptr(M), b, ptr(out),
+                                     code[out.dtype], out.stride(0) if rows else b), ctx.handle)
+    return out

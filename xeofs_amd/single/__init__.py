@@ -2,5 +2,6 @@ from .eeof import ExtendedEOF  # noqa: F401
 from .eof import EOF, ComplexEOF, HilbertEOF  # noqa: F401
 from .gwpca import GWPCA  # noqa: F401
 from .opa import OPA  # noqa: F401
+from .pop import POP  # noqa: F401
 from .sparse_pca import SparsePCA  # noqa: F401
 from .eof_rotator import ComplexEOFRotator, EOFRotator, HilbertEOFRotator  # noqa: F401
