@@ -523,6 +523,18 @@ int eofx_lagcov_f64(eofx_ctx *ctx, const float *S, int64_t n, int p, int64_t ld,
 #define EOFX_PCMUL_F64 1
 int eofx_pcmul_f64(eofx_ctx *ctx, const void *X, int x_dtype, int64_t rows, int a, int64_t ldx, const double *M, int b, void *Y,
                    int y_dtype, int64_t ldy);
+/* ---- block cross-covariance of multi-view canonical correlation analysis (xeofs/multi/cca.py:480-494, csrc/eofx_viewcov.hpp)
+ * C [p x p] float64 (device, row stride ldc >= p) of a float32 device panel Z [n x p] (row stride ld >= p), the m views side by
+ * side with view v the columns off[v] .. off[v + 1] - 1 (off: m + 1 ints, host|device, off[0] = 0 < ... < off[m] = p):
+ *   C[i, j] = 1 / (n - 1) sum_t (Z[t, i] - mean[i]) (Z[t, j] - mean[j])  for i, j in different views,
+ *   C[i, j] = +0.0 inside a view, or the same sum when keep_diag != 0.
+ * mean: p float64 on the device, or NULL for no centring.  Converted and centred in float64, the products on the fp64 matrix
+ * cores; only tiles on or above the diagonal that hold a wanted output are computed, and each writes its mirror image, so C
+ * equals its transpose bit for bit.  No atomics; the grid and the summation order are functions of (n, p, off, keep_diag)
+ * alone.  EOFX_ERR_ARG unless n >= 2, p >= 1, m >= 1, ld >= p, ldc >= p and off is as described; EOFX_ERR_SHAPE for p > 4096
+ * or m > 64.                                                                                                           */
+int eofx_viewcov_f64(eofx_ctx *ctx, const float *Z, int64_t n, int p, int64_t ld, const double *mean, const int *off, int m,
+                     int keep_diag, double *C, int64_t ldc);
 /* Gram matrix of a resident matrix (float32, device): side 0 = sample space G[n_pad x n_pad] = X X^T,
  * side 1 = feature space G[p_pad x p_pad] = X^T X (rows/columns beyond n / p are zero).  Used for
  * (a) the total squared covariance sum(|X^T Y|^2) = <X X^T, Y Y^T> (cross/cpcca.py:991-1000) when X and

@@ -120,6 +120,7 @@ SIGNATURES = {
     "eofx_spca_prox_f64": (_int, [_vp, _vp, _vp, C.c_double, _i64, _int, C.c_double, _vp]),
     "eofx_lagcov_f64": (_int, [_vp, _vp, _i64, _int, _i64, _vp, _int, _vp]),
     "eofx_pcmul_f64": (_int, [_vp, _vp, _int, _i64, _int, _i64, _vp, _int, _vp, _int, _i64]),
+    "eofx_viewcov_f64": (_int, [_vp, _vp, _i64, _int, _i64, _vp, _vp, _int, _int, _vp, _i64]),
     "eofx_resample_f32": (_int, [_vp, _vp, _vp, _i64, _int, C.POINTER(_vp), _vp, _pd]),
     "eofx_mat_gram_f32": (_int, [_vp, _vp, _int, _vp]),
     "eofx_mat_cross_gram_f32": (_int, [_vp, _vp, _vp, _int, _vp]),

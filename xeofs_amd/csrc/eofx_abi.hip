@@ -13,6 +13,7 @@
 #include "eofx_spca.hpp"
 #include "eofx_lagcov.hpp"
 #include "eofx_pcmul.hpp"
+#include "eofx_viewcov.hpp"
 #ifndef EOFX_AXB_DMA_DEFAULT
 #define EOFX_AXB_DMA_DEFAULT 1
 #endif
@@ -6849,5 +6850,80 @@ extern "C" int eofx_pcmul_f64(eofx_ctx* ctx, const void* X, int x_dtype, int64_t
   }
   KCHK();
   if (host_m) HIPCHK(hipStreamSynchronize(ctx->stream));       // (M may be a pageable host buffer; the arena is handed back)
+  return EOFX_OK;
+}
+
+// ---- block cross-covariance of multi-view canonical correlation analysis (csrc/eofx_viewcov.hpp) -----------------------
+extern "C" int eofx_viewcov_f64(eofx_ctx* ctx, const float* Z, int64_t n, int p, int64_t ld, const double* mean, const int* off, int m,
+                                int keep_diag, double* C, int64_t ldc) {
+  if (!ctx || !Z || !off || !C) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (n < 2 || p < 1 || ld < p || ldc < p)
+    return set_err(ctx, EOFX_ERR_ARG, "n >= 2, p >= 1, ld >= p and ldc >= p are required (n = %lld, p = %d, ld = %lld, ldc = %lld)",
+                   (long long)n, p, (long long)ld, (long long)ldc);
+  if (m < 1) return set_err(ctx, EOFX_ERR_ARG, "m must be >= 1, got %d", m);
+  if (p > VIEWCOV_PMAX || m > VIEWCOV_MMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the view covariance kernel takes p <= %d and m <= %d, got p = %d, m = %d", VIEWCOV_PMAX,
+                   VIEWCOV_MMAX, p, m);
+  if (!is_device_ptr(Z) || !is_device_ptr(C) || (mean && !is_device_ptr(mean)))
+    return set_err(ctx, EOFX_ERR_ARG, "Z, mean and C must be device buffers");
+  ENTER(ctx);
+  std::vector<int> offh((size_t)m + 1);
+  if (is_device_ptr(off)) {
+    HIPCHK(hipMemcpyAsync(offh.data(), off, offh.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  } else {
+    std::copy(off, off + m + 1, offh.begin());
+  }
+  if (offh[0] != 0 || offh[m] != p) return set_err(ctx, EOFX_ERR_ARG, "off must run from 0 to p = %d, got %d .. %d", p, offh[0], offh[m]);
+  for (int v = 0; v < m; ++v)
+    if (offh[v + 1] <= offh[v]) return set_err(ctx, EOFX_ERR_ARG, "off must be strictly increasing (off[%d] = %d, off[%d] = %d)", v, offh[v], v + 1, offh[v + 1]);
+  // the view of every column, and the tiles on or above the diagonal that hold a wanted output
+  std::vector<int> host((size_t)p);
+  for (int v = 0; v < m; ++v) std::fill(host.begin() + offh[v], host.begin() + offh[v + 1], v);
+  const int nb = (p + VIEWCOV_T - 1) / VIEWCOV_T;
+  auto one_view = [&](int b) { return host[(size_t)b * VIEWCOV_T] == host[(size_t)std::min(p, (b + 1) * VIEWCOV_T) - 1]; };
+  int ntiles = 0;
+  for (int bi = 0; bi < nb; ++bi)
+    for (int bj = bi; bj < nb; ++bj) {
+      if (!keep_diag && one_view(bi) && one_view(bj) && host[(size_t)bi * VIEWCOV_T] == host[(size_t)bj * VIEWCOV_T]) continue;
+      host.push_back(bi);
+      host.push_back(bj);
+      ++ntiles;
+    }
+  // the split of the samples: a function of (n, the tile list) alone
+  const int64_t nslabs = (n + VIEWCOV_K - 1) / VIEWCOV_K;
+  int64_t G = ntiles ? std::min<int64_t>(VIEWCOV_WGS / ntiles, nslabs / VIEWCOV_SPLIT_SLABS) : 1;
+  G = std::max<int64_t>(G, 1);
+  const int64_t chunk = (nslabs + G - 1) / G;
+  G = (nslabs + chunk - 1) / chunk;                // (no empty split)
+  const bool split = G > 1;
+  const size_t npart = split ? (size_t)ntiles * G * VIEWCOV_TT : 0;
+  CHK(arena_reserve(ctx, host.size() * sizeof(int) + npart * 8 + 2 * 256));
+  ArenaScope scope(ctx);
+  ARENA(int, dev, host.size());
+  double* part = nullptr;
+  if (split) {
+    part = arena_alloc<double>(ctx, npart);
+    if (!part) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (part)");
+  }
+  HIPCHK(hipMemcpyAsync(dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  const int* view = dev;
+  const int* tiles = dev + p;
+  hipLaunchKernelGGL(viewcov_zero_kernel, dim3((unsigned)((p + 255) / 256), (unsigned)p), dim3(256), 0, ctx->stream, C, p, ldc);
+  KCHK();
+  if (ntiles) {
+    if (split) {
+      hipLaunchKernelGGL(viewcov_kernel<true>, dim3((unsigned)ntiles, (unsigned)G), dim3(256), 0, ctx->stream, Z, n, p, ld, mean, view,
+                         tiles, keep_diag ? 1 : 0, chunk, C, ldc, part);
+      KCHK();
+      hipLaunchKernelGGL(viewcov_finish_kernel, dim3((unsigned)(VIEWCOV_TT / 256), (unsigned)ntiles), dim3(256), 0, ctx->stream,
+                         (const double*)part, (int)G, n, p, view, tiles, keep_diag ? 1 : 0, C, ldc);
+    } else {
+      hipLaunchKernelGGL(viewcov_kernel<false>, dim3((unsigned)ntiles, 1u), dim3(256), 0, ctx->stream, Z, n, p, ld, mean, view, tiles,
+                         keep_diag ? 1 : 0, nslabs, C, ldc, (double*)nullptr);
+    }
+    KCHK();
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // (the staged lists are a pageable host buffer; the arena is handed back)
   return EOFX_OK;
 }

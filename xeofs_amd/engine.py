@@ -1396,3 +1396,49 @@ def pcmul(ctx: Context, X, M, out_dtype=None, out=None):
     raise_for(ctx.lib.eofx_pcmul_f64(ctx.handle, ptr(X), code[X.dtype], rows, a, X.stride(0) if rows else a, ptr(M), b, ptr(out),
                                      code[out.dtype], out.stride(0) if rows else b), ctx.handle)
     return out
+
+
+# --------------------------------------------------------------------------- #
+# block cross-covariance of multi-view CCA (eofx_viewcov_f64, csrc/eofx_viewcov.hpp)                 #
+# --------------------------------------------------------------------------- #
+VIEWCOV_PMAX = 4096       # columns the kernel takes (the views side by side)
+VIEWCOV_MMAX = 64         # views
+
+
+def viewcov(ctx: Context, Z, offsets, center=True, keep_diag=False, out=None):
+    """C [p x p] (float64 device tensor) of a float32 panel Z [n x p] -- a host array or a device tensor, whose row stride may
+    exceed p -- holding m views side by side, view v the columns offsets[v] .. offsets[v + 1] - 1: the covariance (ddof = 1)
+    of columns in different views, +0.0 inside a view unless `keep_diag` (multi/cca.py:480-494 without the diagonal blocks
+    it subtracts).  `center`: about the float64 column mean, computed on the device; else the raw second moment over
+    n - 1.  Only the tiles on or above the diagonal are computed; C equals its transpose bit for bit.  `out`: a float64
+    device tensor [p x p] to write, whose row stride may exceed p."""
+    torch = _torch()
+    dev = f"cuda:{ctx.device}"
+    if not hasattr(Z, "data_ptr"):
+        Z = np.asarray(Z)
+        if Z.ndim != 2:
+            raise ValueError(f"Z must be a matrix, got {Z.ndim} dimensions")
+        Z = torch.from_numpy(_f32c(Z)).to(dev)
+    if Z.dim() != 2:
+        raise ValueError(f"Z must be a matrix, got {Z.dim()} dimensions")
+    n, p = Z.shape
+    off = np.asarray(offsets).reshape(-1)
+    m = off.size - 1
+    if n < 2:
+        raise ValueError(f"the covariance needs n >= 2 samples, got n = {n}")
+    if p > VIEWCOV_PMAX or m > VIEWCOV_MMAX:
+        raise ValueError(f"the view covariance kernel takes p <= {VIEWCOV_PMAX} and m <= {VIEWCOV_MMAX}, got p = {p}, m = {m}")
+    if m < 1 or off[0] != 0 or off[-1] != p or np.any(np.diff(off) <= 0) or np.any(off != np.floor(off)):
+        raise ValueError(f"offsets must be integers strictly increasing from 0 to p = {p}, got {off.tolist()}")
+    off = np.ascontiguousarray(off, dtype=np.int32)
+    if Z.dtype != torch.float32 or Z.stride(1) != 1 or Z.stride(0) < p:
+        Z = Z.to(torch.float32).contiguous()
+    mean = torch.sum(Z, dim=0, dtype=torch.float64).div_(n).contiguous() if center else None
+    if out is None:
+        out = torch.empty((p, p), dtype=torch.float64, device=Z.device)
+    elif (not hasattr(out, "data_ptr") or tuple(out.shape) != (p, p) or out.dtype != torch.float64 or out.stride(1) != 1
+          or out.stride(0) < p):
+        raise ValueError(f"out must be a float64 device tensor of shape ({p}, {p}) with unit column stride")
+    raise_for(ctx.lib.eofx_viewcov_f64(ctx.handle, ptr(Z), n, p, Z.stride(0), ptr(mean), ptr(off), m, int(bool(keep_diag)),
+                                       ptr(out), out.stride(0)), ctx.handle)
+    return out
