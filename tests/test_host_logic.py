@@ -171,3 +171,107 @@ def test_near_diagonal_matrix_powers(scale, accepted):
     assert near_diagonal_powers(torch.as_tensor(Cz), powers) is None
     Cz[5, 5] = np.nan
     assert near_diagonal_powers(torch.as_tensor(Cz), powers) is None
+
+
+# ------------------------------------------------------------------------------------------------ labelled helpers
+class NoArray:
+    """data that cannot be materialised: a dtype and a shape, and `__array__` raises"""
+
+    def __init__(self, dtype, shape=(4, 3)):
+        self.dtype, self.shape, self.ndim = np.dtype(dtype), shape, len(shape)
+
+    def __array__(self, *args, **kwargs):
+        raise AssertionError("is_complex must not materialise the data")
+
+
+@pytest.mark.parametrize("dtype,expected", [(np.float32, False), (np.float64, False), (np.complex64, True),
+                                            (np.complex128, True)])
+def test_first_array_and_is_complex(dtype, expected):
+    """`labelled.first_array` / `labelled.is_complex` over everything a model may be handed; the first array decides"""
+    import torch
+
+    from xeofs_amd import labelled
+
+    a = np.ones((4, 3), dtype)
+    other = np.ones((4, 3), np.complex64 if not expected else np.float32)        # a later array never decides
+    da = labelled.DataArray(a, dims=("time", "x"))
+    da_other = labelled.DataArray(other, dims=("time", "x"))
+    ds = labelled.Dataset({"first": da, "second": da_other})
+    t = torch.from_numpy(a)
+    assert labelled.first_array(a) is a and labelled.first_array(da) is da and labelled.first_array(t) is t
+    assert labelled.first_array([da, da_other]) is da and labelled.first_array((a, other)) is a
+    assert labelled.first_array(ds).name == "first" and labelled.first_array(ds).values is a
+    for X in (a, da, ds, [da, da_other], (da, da_other), [a, other], t, labelled.DataArray(t, dims=("time", "x"))):
+        assert labelled.is_complex(X) is expected, type(X)
+    # nothing is converted or copied: data that raise on __array__ still get an answer
+    lazy = labelled.DataArray(a, dims=("time", "x"))
+    lazy.values = NoArray(dtype)
+    for X in (lazy, [lazy, da_other], (lazy,)):
+        assert labelled.is_complex(X) is expected
+
+
+def _labelled_complex(shape, dims, coords=None):
+    from xeofs_amd import labelled
+
+    rng = np.random.default_rng(3)
+    Z = (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
+    return labelled.DataArray(Z, dims=dims, coords=coords)
+
+
+@pytest.mark.parametrize("model,message", [("OPA", "This method does not support complex data."),
+                                           ("POP", "This method does not support complex data."),
+                                           ("SparsePCA", "This method does not support complex data."),
+                                           ("GWPCA", "GWPCA does not support complex data."),
+                                           ("CCA", "This method does not support complex data.")])
+def test_complex_input_is_rejected_before_any_context(model, message, monkeypatch):
+    """the five real-only models refuse a complex host input with their own message before `engine.default_context()` is
+    touched"""
+    import re
+
+    import xeofs_amd as xe
+    from xeofs_amd import engine
+
+    def no_context(*args, **kwargs):
+        raise AssertionError("the complex check must come before any device work")
+
+    monkeypatch.setattr(engine, "default_context", no_context)
+    monkeypatch.setattr(engine, "Context", no_context)
+    Z = _labelled_complex((20, 6), ("time", "x"))
+    match = "^" + re.escape(message) + "$"
+    if model == "GWPCA":
+        G = _labelled_complex((4, 5, 3), ("lat", "lon", "var"), {"lat": np.arange(4.0), "lon": np.arange(5.0)})
+        with pytest.raises(TypeError, match=match):
+            xe.single.GWPCA(n_modes=2, bandwidth=500.0).fit(G, dim=("lat", "lon"))
+    elif model == "CCA":
+        real = xe.DataArray(np.ones((20, 6), np.float32), dims=("time", "x"))
+        for views in ([Z, real], [real, Z]):
+            with pytest.raises(TypeError, match=match):
+                xe.multi.CCA().fit(views, dim="time")
+    else:
+        kw = dict(OPA=dict(n_modes=2, tau_max=3, n_pca_modes=4), POP=dict(n_pca_modes=4), SparsePCA=dict(n_modes=2))[model]
+        m = getattr(xe.single, model)(**kw)
+        for X in (Z, [Z], xe.Dataset({"z": Z})):
+            with pytest.raises(TypeError, match=match):
+                m.fit(X, dim="time")
+        assert m.ctx is None
+
+
+def test_complex_join():
+    """`labelled.complex_join`: re + 1j (im - im_offset) with the labels of the real part, entry by entry for lists"""
+    from xeofs_amd import labelled
+
+    rng = np.random.default_rng(5)
+    re, im, off = (labelled.DataArray(rng.standard_normal((5, 3)), dims=("time", "x"), coords={"x": [10, 20, 30]},
+                                      name="reconstructed_data", attrs={"k": 1}) for _ in range(3))
+    out = labelled.complex_join(re, im)
+    assert np.array_equal(out.values, re.values + 1j * im.values) and out.values.dtype == np.complex128
+    assert out.dims == re.dims and out.name == re.name and out.attrs == re.attrs
+    assert np.array_equal(out.coords["x"], re.coords["x"])
+    assert np.array_equal(labelled.complex_join(re, im, off).values, re.values + 1j * (im.values - off.values))
+    outs = labelled.complex_join([re, im], [im, off])
+    assert isinstance(outs, list) and len(outs) == 2
+    assert np.array_equal(outs[0].values, re.values + 1j * im.values)
+    assert np.array_equal(outs[1].values, im.values + 1j * off.values)
+    outs = labelled.complex_join([re, im], [im, off], [off, re])
+    assert np.array_equal(outs[0].values, re.values + 1j * (im.values - off.values))
+    assert np.array_equal(outs[1].values, im.values + 1j * (off.values - re.values))

@@ -325,16 +325,7 @@ class ComplexCPCCA(ComplexPairSurface, ModelSurface, Deferred):
             else:
                 im = self.pre_im[i].inverse_transform_data(rec.imag, "reconstructed_data", fields, vs)
                 zero = None
-
-            def join(a, b, z):
-                va, d_, c_, nm, at = labelled.unpack(a)
-                vb = labelled.unpack(b)[0] - (labelled.unpack(z)[0] if z is not None else 0.0)
-                return labelled.pack(va + 1j * vb, d_, c_, nm, at, a)
-
-            if isinstance(re, list):
-                outs.append([join(a, b, z) for a, b, z in zip(re, im, zero or [None] * len(re))])
-            else:
-                outs.append(join(re, im, zero))
+            outs.append(labelled.complex_join(re, im, zero))
         return outs[0] if len(outs) == 1 else outs
 
 

@@ -1159,9 +1159,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------
-// gram_f64: Gpart[bx][L x L] = sum over this block's rows of P[r,:]^T P[r,:]  (float64)
-//   grid = (nbx, nb*nb) where nb = ceil(L/64); each block owns one 64x64 sub-block of G
-//   and a strided set of 32-row slabs.  HBM-bound on P (rows x L x 4 B), tiny.
 // lower triangle of a symmetric product from its upper one: C[m][l] = C[l][m] for l < m  (64 x 64 tiles through LDS)
 __global__ __launch_bounds__(256) void symmetrize_lower_kernel(float* __restrict__ C, int64_t n, int64_t ld) {
   __shared__ float T[64][65];
@@ -1180,60 +1177,8 @@ __global__ __launch_bounds__(256) void symmetrize_lower_kernel(float* __restrict
 }
 
 // ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gram_f64_kernel(const float* __restrict__ P, int64_t rows,
-                                                        int L, double* __restrict__ Gpart) {
-  __shared__ __attribute__((aligned(16))) float Pa[32][64];
-  __shared__ __attribute__((aligned(16))) float Pb[32][64];
-  const int nb = (L + 63) / 64;
-  const int bi = blockIdx.y / nb, bj = blockIdx.y % nb;
-  const int tid = threadIdx.x;
-  const int ti = tid >> 4, tj = tid & 15;
-  double acc[4][4];
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int y = 0; y < 4; ++y) acc[x][y] = 0.0;
-  const int lr = tid >> 4;         // 0..15  (two passes -> 32 rows)
-  const int lc = (tid & 15) * 4;   // float4 column
-  for (int64_t r0 = (int64_t)blockIdx.x * 32; r0 < rows; r0 += (int64_t)gridDim.x * 32) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int rr = lr + 16 * h;
-      const int64_t r = r0 + rr;
-      f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = {0.f, 0.f, 0.f, 0.f};
-      if (r < rows) {
-        const int ca = bi * 64 + lc, cb = bj * 64 + lc;
-        if (ca < L) va = *reinterpret_cast<const f32x4*>(P + r * L + ca);
-        if (cb < L) vb = *reinterpret_cast<const f32x4*>(P + r * L + cb);
-      }
-      *reinterpret_cast<f32x4*>(&Pa[rr][lc]) = va;
-      *reinterpret_cast<f32x4*>(&Pb[rr][lc]) = vb;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < 32; ++r) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(&Pa[r][4 * ti]);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(&Pb[r][4 * tj]);
-#pragma unroll
-      for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) acc[x][y] += (double)a[x] * (double)b[y];
-    }
-    __syncthreads();
-  }
-  double* G = Gpart + (int64_t)blockIdx.x * L * L;
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int y = 0; y < 4; ++y) {
-      const int gi = bi * 64 + 4 * ti + x, gj = bj * 64 + 4 * tj + y;
-      if (gi < L && gj < L) G[(int64_t)gi * L + gj] = acc[x][y];
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// gram_mfma: the same float64 Gram matrix on the fp64 matrix cores (v_mfma_f64_16x16x4_f64).
-//   grid = (nbx, nb*nb); every workgroup writes one partial of its 64x64 sub-block (its four waves meet in LDS in a fixed
+// gram_mfma: Gpart[bx][L x L] = sum over this block's rows of P[r,:]^T P[r,:]  (float64) on the fp64 matrix cores
+//   (v_mfma_f64_16x16x4_f64).  grid = (nbx, nb*nb) where nb = ceil(L/64); every workgroup writes one partial of its 64x64 sub-block (its four waves meet in LDS in a fixed
 //   order); the nbx partials are summed in a fixed order by f64_reduce_kernel.
 //   Per k-step a wave reads 4 rows x 64 columns (lane (c = l % 16, k = l / 16) loads the float4 at
 //   P[row + k][64 b + 4 c ..]: one full 256 B row per 16 lanes), converts to float64 and issues the 16

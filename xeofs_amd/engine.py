@@ -1326,6 +1326,39 @@ def gwpca(ctx: Context, mat: ResidentMatrix, xy: np.ndarray, k: int, bandwidth: 
 
 
 # --------------------------------------------------------------------------- #
+# panels of the float64 kernel entries below: staging an input, validating a caller's output      #
+# --------------------------------------------------------------------------- #
+def device_panel(ctx: Context, A, name: str = "the panel", dtypes=None):
+    """A host array or a device tensor -> a device tensor the float64 kernel entries read: two dimensions (ValueError naming
+    `name` otherwise), one of `dtypes` (torch.float32 and torch.float64 by default; anything else becomes the first), unit
+    column stride and a row stride of at least the columns.  What already is all that is returned as it is."""
+    torch = _torch()
+    dtypes = dtypes or (torch.float32, torch.float64)
+    if not hasattr(A, "data_ptr"):
+        A = np.asarray(A)
+        host = {torch.float32: np.float32, torch.float64: np.float64}
+        keep = [host[d] for d in dtypes if host[d] == A.dtype]
+        A = torch.from_numpy(np.ascontiguousarray(A, dtype=keep[0] if keep else host[dtypes[0]]))
+    A = A.to(f"cuda:{ctx.device}")
+    if A.dim() != 2:
+        raise ValueError(f"{name} must be a matrix, got {A.dim()} dimensions")
+    if A.dtype not in dtypes:
+        A = A.to(dtypes[0])
+    if A.stride(1) != 1 or A.stride(0) < A.shape[1]:
+        A = A.contiguous()
+    return A
+
+
+def _check_out(out, rows: int, cols: int, dtypes, what: str):
+    """a caller's `out`: a device tensor [rows x cols] of one of `dtypes` with unit column stride, whose row stride may
+    exceed the columns"""
+    if (not hasattr(out, "data_ptr") or tuple(out.shape) != (rows, cols) or out.dtype not in dtypes
+            or (rows and (out.stride(1) != 1 or out.stride(0) < cols))):
+        raise ValueError(f"out must be a {what} device tensor of shape ({rows}, {cols}) with unit column stride")
+    return out
+
+
+# --------------------------------------------------------------------------- #
 # lag-summed covariance of optimal persistence analysis (eofx_lagcov_f64, csrc/eofx_lagcov.hpp)   #
 # --------------------------------------------------------------------------- #
 LAGCOV_PMAX = 1024        # columns the kernels take
@@ -1337,13 +1370,7 @@ def lagcov(ctx: Context, S, w):
     array or a device tensor, whose row stride may exceed p -- and the weights w [ntau] of the lags 0 .. ntau - 1
     (opa.py:104-171 as one filter along the samples and one cross-product)"""
     torch = _torch()
-    dev = f"cuda:{ctx.device}"
-    if not hasattr(S, "data_ptr"):
-        S = torch.from_numpy(_f32c(S)).to(dev)
-    if S.dim() != 2:
-        raise ValueError(f"S must be a matrix, got {S.dim()} dimensions")
-    if S.dtype != torch.float32 or S.stride(1) != 1 or S.stride(0) < S.shape[1]:
-        S = S.to(torch.float32).contiguous()
+    S = device_panel(ctx, S, "S", (torch.float32,))
     n, p = S.shape
     w = np.ascontiguousarray(w.detach().cpu().numpy() if hasattr(w, "detach") else w, dtype=np.float64)
     if w.ndim != 1:
@@ -1366,17 +1393,8 @@ def pcmul(ctx: Context, X, M, out_dtype=None, out=None):
     device tensor whose row stride may exceed a; M: float64, a host array or a device tensor; `out`: a device tensor
     [rows x b] to write, whose row stride may exceed b."""
     torch = _torch()
-    dev = f"cuda:{ctx.device}"
-    if not hasattr(X, "data_ptr"):
-        X = np.asarray(X)
-        X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64 if X.dtype == np.float64 else np.float32)).to(dev)
-    if X.dim() != 2:
-        raise ValueError(f"X must be a matrix, got {X.dim()} dimensions")
-    if X.dtype not in (torch.float32, torch.float64):
-        X = X.to(torch.float32)
+    X = device_panel(ctx, X, "X")
     rows, a = X.shape
-    if rows and (X.stride(1) != 1 or X.stride(0) < a):
-        X = X.contiguous()
     if hasattr(M, "data_ptr"):
         M = M.to(torch.float64).contiguous()
     else:
@@ -1389,9 +1407,8 @@ def pcmul(ctx: Context, X, M, out_dtype=None, out=None):
         if out_dtype not in (torch.float32, torch.float64):
             raise ValueError(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
         out = torch.empty((rows, b), dtype=out_dtype, device=X.device)
-    elif (not hasattr(out, "data_ptr") or tuple(out.shape) != (rows, b) or out.dtype not in (torch.float32, torch.float64)
-          or (rows and (out.stride(1) != 1 or out.stride(0) < b))):
-        raise ValueError(f"out must be a float32 or float64 device tensor of shape ({rows}, {b}) with unit column stride")
+    else:
+        _check_out(out, rows, b, (torch.float32, torch.float64), "float32 or float64")
     code = {torch.float32: 0, torch.float64: 1}      # EOFX_PCMUL_F32 | EOFX_PCMUL_F64
     raise_for(ctx.lib.eofx_pcmul_f64(ctx.handle, ptr(X), code[X.dtype], rows, a, X.stride(0) if rows else a, ptr(M), b, ptr(out),
                                      code[out.dtype], out.stride(0) if rows else b), ctx.handle)
@@ -1413,14 +1430,7 @@ def viewcov(ctx: Context, Z, offsets, center=True, keep_diag=False, out=None):
     n - 1.  Only the tiles on or above the diagonal are computed; C equals its transpose bit for bit.  `out`: a float64
     device tensor [p x p] to write, whose row stride may exceed p."""
     torch = _torch()
-    dev = f"cuda:{ctx.device}"
-    if not hasattr(Z, "data_ptr"):
-        Z = np.asarray(Z)
-        if Z.ndim != 2:
-            raise ValueError(f"Z must be a matrix, got {Z.ndim} dimensions")
-        Z = torch.from_numpy(_f32c(Z)).to(dev)
-    if Z.dim() != 2:
-        raise ValueError(f"Z must be a matrix, got {Z.dim()} dimensions")
+    Z = device_panel(ctx, Z, "Z", (torch.float32,))
     n, p = Z.shape
     off = np.asarray(offsets).reshape(-1)
     m = off.size - 1
@@ -1431,14 +1441,11 @@ def viewcov(ctx: Context, Z, offsets, center=True, keep_diag=False, out=None):
     if m < 1 or off[0] != 0 or off[-1] != p or np.any(np.diff(off) <= 0) or np.any(off != np.floor(off)):
         raise ValueError(f"offsets must be integers strictly increasing from 0 to p = {p}, got {off.tolist()}")
     off = np.ascontiguousarray(off, dtype=np.int32)
-    if Z.dtype != torch.float32 or Z.stride(1) != 1 or Z.stride(0) < p:
-        Z = Z.to(torch.float32).contiguous()
     mean = torch.sum(Z, dim=0, dtype=torch.float64).div_(n).contiguous() if center else None
     if out is None:
         out = torch.empty((p, p), dtype=torch.float64, device=Z.device)
-    elif (not hasattr(out, "data_ptr") or tuple(out.shape) != (p, p) or out.dtype != torch.float64 or out.stride(1) != 1
-          or out.stride(0) < p):
-        raise ValueError(f"out must be a float64 device tensor of shape ({p}, {p}) with unit column stride")
+    else:
+        _check_out(out, p, p, (torch.float64,), "float64")
     raise_for(ctx.lib.eofx_viewcov_f64(ctx.handle, ptr(Z), n, p, Z.stride(0), ptr(mean), ptr(off), m, int(bool(keep_diag)),
                                        ptr(out), out.stride(0)), ctx.handle)
     return out

@@ -135,6 +135,20 @@ def is_xarray(obj) -> bool:
     return _xr is not None and isinstance(obj, (_xr.DataArray, _xr.Dataset))
 
 
+def first_array(X):
+    """the first array of whatever a model is handed: a labelled array, a Dataset (its first variable), a list or tuple
+    (its first entry), a bare array or a device tensor"""
+    if is_dataset(X):
+        return X[next(iter(X.data_vars))]
+    return X[0] if isinstance(X, (list, tuple)) else X
+
+
+def is_complex(X) -> bool:
+    """whether the first array of `X` holds complex data, from its dtype alone (numpy and torch dtypes alike) -- nothing is
+    materialised"""
+    return "complex" in str(first_array(X).dtype)
+
+
 def unpack(obj):
     """-> (values ndarray, dims tuple, coords dict, name, attrs) from either array flavour."""
     if _xr is not None and isinstance(obj, _xr.DataArray):
@@ -151,6 +165,18 @@ def pack(values, dims, coords, name, attrs, like):
     if _xr is not None and isinstance(like, _xr.DataArray):
         return _xr.DataArray(values, dims=dims, coords=coords, name=name, attrs=attrs)
     return DataArray(values, dims, coords, name, attrs)
+
+
+def complex_join(re, im, im_offset=None):
+    """re + 1j (im - im_offset), labelled as `re`: the complex reconstruction from the separately un-scaled parts; lists
+    (multi-field outputs) are joined entry by entry"""
+    if isinstance(re, list):
+        return [complex_join(a, b, z) for a, b, z in zip(re, im, im_offset or [None] * len(re))]
+    vals, dims, coords, name, attrs = unpack(re)
+    vim = unpack(im)[0]
+    if im_offset is not None:
+        vim = vim - unpack(im_offset)[0]
+    return pack(vals + 1j * vim, dims, coords, name, attrs, re)
 
 
 def mode_array(values, name, attrs, like):

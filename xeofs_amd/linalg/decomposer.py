@@ -51,6 +51,13 @@ class Decomposer:
         # branch keeps its parameters: sketch width max(20, k + 10), n_power_iter (default 4) power passes.
         self.lazy_input = bool(lazy_input)
 
+    @classmethod
+    def for_model(cls, params, n_modes, ctx, **kwargs):
+        """the inner PCA of a model: `n_modes` modes with the `solver`, `random_state`, `compute` and `solver_kwargs` of the
+        model's parameter dict"""
+        return cls(n_modes=n_modes, ctx=ctx, solver=params["solver"], random_state=params["random_state"],
+                   compute=params["compute"], solver_kwargs=params["solver_kwargs"], **kwargs)
+
     def policy(self, n, p, quiet=False):
         """The solver ladder of decomposer.py:86-131 for an (n x p) matrix -> (k, n_oversamples, n_iter, wide):
         the sketch the engine is asked for, and whether it is wider than the sketch kernels hold.  Raises / warns as
@@ -112,6 +119,7 @@ class Decomposer:
         rank = min(n, p)
         k, n_over, n_iter, wide = self.policy(n, p)
         self.n_modes_precompute = k
+        self.route_ = "exact" if n_iter == 0 else "randomized"      # the branch of the ladder: what the models report
         if wide:
             # more modes than the sketch kernels hold (e.g. float n_modes -> int(0.3 * rank) modes): at that
             # width the exact small-side Gram route is cheaper than the randomized passes (xeofs_amd/pca.py)
@@ -157,7 +165,16 @@ class Decomposer:
         if self.policy(n, p) != (k, n_over, n_iter, False):
             return self.fit(mat, total_variance=total_variance)
         self.n_modes_precompute = k
+        self.route_ = "randomized"          # (fused_plan offers no other branch)
         return self._finish(U, s, V, n, k, total_variance)
+
+    def projected_scores(self, mat, keep=None):
+        """-> (V32 [p x q], S32 [n x q]): the leading `keep` patterns (all by default) and the scores as the reference's PCA
+        defines them, the projection X V (preprocessing/pca.py:115-139) -- U s up to the decomposition's rounding, and what
+        a model's `transform` reproduces for its training data.  One more pass over the resident matrix, through the
+        kernel `transform` uses."""
+        V32 = np.ascontiguousarray(self.V_[:, :keep], dtype=np.float32)
+        return V32, np.ascontiguousarray(engine.project(self.ctx, mat, V32), dtype=np.float32)
 
     def _finish(self, U, s, V, n, k, total_variance):
         """variance-fraction truncation, decomposer.py:179-212"""

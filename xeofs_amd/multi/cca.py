@@ -137,13 +137,6 @@ def total_explained_covariance(abs_eigenvalues, minimum_dimension: int) -> float
     return float(s[::2][:minimum_dimension].sum())
 
 
-def _is_complex(view) -> bool:
-    """whether a view (an array, a Dataset or a list of arrays: its first array decides) holds complex data, from its dtype
-    alone -- nothing is materialised"""
-    first = view[next(iter(view.data_vars))] if labelled.is_dataset(view) else (view[0] if isinstance(view, (list, tuple)) else view)
-    return "complex" in str(first.dtype)                      # (numpy and torch dtypes alike)
-
-
 class CCA(Deferred):
     """Drop-in for xeofs.multi.CCA (xeofs/multi/cca.py:222-706).  `fit(views, dim)` takes a list of labelled arrays sharing
     the sample dimension(s); every accessor returns one entry per view unless noted."""
@@ -191,7 +184,7 @@ class CCA(Deferred):
         self.use_coslat = process_parameter("use_coslat", prm["use_coslat"], False, m)
         self.init_pca_modes = process_parameter("init_pca_modes", prm["init_pca_modes"], 0.75, m)
         self.c = process_parameter("c", prm["c"], 0, m)
-        if any(_is_complex(v) for v in views):
+        if any(labelled.is_complex(v) for v in views):
             raise TypeError("This method does not support complex data.")
         self.ctx = self.ctx or engine.default_context()
         # 1. one preprocessor per view: centred, not standardised, coslat per view; the views stay resident
@@ -237,8 +230,7 @@ class CCA(Deferred):
         n_pca = process_init_pca_modes(self.init_pca_modes, self.n_samples_, self.n_features_)
         Vs, Ss, evs = [], [], []
         for i, (mat, pre) in enumerate(zip(mats, self._preprocessors)):
-            dec = Decomposer(n_modes=n_pca[i], ctx=ctx, solver=prm["solver"], random_state=prm["random_state"],
-                             compute=prm["compute"], solver_kwargs=self._solver_kwargs)
+            dec = Decomposer.for_model(dict(prm, solver_kwargs=self._solver_kwargs), n_pca[i], ctx)
             dec.fit(mat, total_variance=pre.total_variance)
             ev = dec.s_.astype(np.float64) ** 2 / (mat.n - 1)
             keep, warning = pca_modes_to_keep(ev / pre.total_variance, prm["variance_fraction"])
@@ -249,9 +241,9 @@ class CCA(Deferred):
                 raise ValueError(f"the PCA of view {i} kept {keep} modes; CCA takes at most {engine.PCMUL_AMAX} per view: lower "
                                  f"variance_fraction (variance_fraction={prm['variance_fraction']}) or init_pca_modes "
                                  f"(init_pca_modes={self.init_pca_modes[i]})")
-            V32 = np.ascontiguousarray(dec.V_[:, :keep], dtype=np.float32)
+            V32, S32 = dec.projected_scores(mat, keep)
             Vs.append(V32)
-            Ss.append(np.ascontiguousarray(engine.project(ctx, mat, V32), dtype=np.float32))
+            Ss.append(S32)
             evs.append(ev[:keep])
         p = sum(V.shape[1] for V in Vs)
         if p > engine.VIEWCOV_PMAX:
@@ -283,7 +275,6 @@ class CCA(Deferred):
         """cca.py:307-384 on the resident, preprocessed views"""
         prm, ctx = self._params, self.ctx
         torch = engine._torch()
-        dev = f"cuda:{ctx.device}"
         m, n, k = self.n_views_, self.n_samples_, int(self.n_modes)
         t0 = time.perf_counter()
         if prm["pca"]:
@@ -299,7 +290,7 @@ class CCA(Deferred):
         p = int(off[-1])
         if k > p:
             raise ValueError(f"n_modes = {k} exceeds the {p} columns of the concatenated views")
-        Zd = torch.cat([torch.from_numpy(S).to(dev) for S in Ss], dim=1)           # n x p float32
+        Zd = torch.cat([engine.device_panel(ctx, S) for S in Ss], dim=1)          # n x p float32
         t1 = time.perf_counter()
         # 4. C and D
         cov = engine.viewcov(ctx, Zd, off)                                         # m C: the statistics below want it too
@@ -321,7 +312,7 @@ class CCA(Deferred):
         # 6. weights (feature space, rounded once to float32), loadings, variates, canonical loadings
         xs = [np.ascontiguousarray(x[off[i]:off[i + 1]]) for i in range(m)]
         if prm["pca"]:
-            weights = [engine.pcmul(ctx, torch.from_numpy(V).to(dev), xi, torch.float32).cpu().numpy() for V, xi in zip(Vs, xs)]
+            weights = [engine.pcmul(ctx, V, xi, torch.float32).cpu().numpy() for V, xi in zip(Vs, xs)]
         else:
             weights = [xi.astype(np.float32) for xi in xs]
         loadings = [(w.astype(np.float64) / np.linalg.norm(w.astype(np.float64), axis=0)).astype(np.float32) for w in weights]
@@ -332,7 +323,7 @@ class CCA(Deferred):
         explained_variance = [t.astype(np.float64).var(axis=0) for t in transformed]
         var1 = Zd.to(torch.float64).var(dim=0, unbiased=True).cpu().numpy()
         total_variance = [float(var1[off[i]:off[i + 1]].sum()) for i in range(m)]
-        Td = torch.cat([torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32)).to(dev) for t in transformed], dim=1)
+        Td = torch.cat([engine.device_panel(ctx, t) for t in transformed], dim=1)
         covT = engine.viewcov(ctx, Td, np.arange(m + 1) * k).cpu().numpy()         # column i of view v at v k + i
         explained_covariance = np.array([np.linalg.svd(covT[i::k, i::k], compute_uv=False)[0] for i in range(k)])
         if p <= CCA_HOST_EIG_PMAX:

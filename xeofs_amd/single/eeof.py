@@ -121,21 +121,14 @@ class ExtendedEOF(EOF):
 
     @staticmethod
     def _n_samples(X, dim):
-        if labelled.is_dataset(X):
-            X = X[next(iter(X.data_vars))]
-        if isinstance(X, (list, tuple)):
-            X = X[0]
-        vals, dims, _, _, _ = labelled.unpack(X)
+        vals, dims, _, _, _ = labelled.unpack(labelled.first_array(X))
         sd = (dim,) if isinstance(dim, str) else tuple(dim)
         return int(np.prod([vals.shape[dims.index(d)] for d in sd if d in dims], dtype=np.int64))
 
     def _fit_now(self, X, dim, weights=None):
         self._check_length(self._n_samples(X, dim))
-        self.ctx = self.ctx or engine.default_context()
-        self.preprocessor.ctx = self.ctx
         self._decomposer_kwargs["lazy_input"] = labelled.is_lazy(X)
-        mat = self.preprocessor.fit_transform(X, dim, weights)
-        self.sample_dims = self.preprocessor.sample_dims
+        mat = self._preprocess(X, dim, weights)
         n_emb = self._check_length(mat.n)           # (samples dropped by the Sanitizer shorten the series)
         if self.n_pca_modes:
             return self._fit_pca(mat, X, dim, weights, n_emb)
@@ -181,14 +174,9 @@ class ExtendedEOF(EOF):
         """eeof.py:99-122, 157-162: PCA scores of the (centred) preprocessed field, their embedding, a small EOF on it;
         components = V_pca V_eeof on the device."""
         ctx, E, tau, m = self.ctx, self.embedding, self.tau, self.n_pca_modes
-        pmat = mat
-        if not self._params["center"]:
-            # the reference's PCA centres the preprocessed field: (X w / std) - mean = the preprocessing of X with center=True
-            from ..preprocessing import Preprocessor
-
-            pre = Preprocessor(True, self._params["standardize"], self._params["use_coslat"], self._params["check_nans"],
-                               ctx=ctx, in_place=True)
-            pmat = pre.fit_transform(X, dim, weights)
+        pmat = self._centred_twin(mat, X, dim, weights)
+        # exactly these arguments, not Decomposer.for_model: the model's `solver` and `compute` do not reach the inner PCA.
+        # Honouring `solver` would change results and belongs to an issue of its own.
         pca = Decomposer(n_modes=m, ctx=ctx, random_state=self._params["random_state"],
                          solver_kwargs=self._decomposer_kwargs.get("solver_kwargs", {}))
         pca.fit(pmat)

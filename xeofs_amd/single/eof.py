@@ -25,6 +25,18 @@ from ..preprocessing import Preprocessor, parse_scores
 COMPLEX_N_ITER_DEFAULT = "converge"
 
 
+def _undefined(what: str, it: str):
+    """an accessor of EOF that the reference's model (OPA, POP, SparsePCA) does not define"""
+    def accessor(self):
+        raise AttributeError(f"{type(self).__name__} has no {what} (the reference's model does not define {it})")
+
+    return accessor
+
+
+NO_SINGULAR_VALUES = _undefined("singular values", "them")
+NO_EXPLAINED_VARIANCE = _undefined("explained variance", "it")
+
+
 class EOF(Deferred):
     """Drop-in for xeofs.single.EOF (xeofs/single/eof.py:15-240).
 
@@ -66,16 +78,42 @@ class EOF(Deferred):
             return self._defer(lambda: self._fit_now(X, dim, weights))
         return self._fit_now(X, dim, weights)
 
-    def _fit_now(self, X, dim, weights=None):
+    def _bind_context(self):
         self.ctx = self.ctx or engine.default_context()
         self.preprocessor.ctx = self.ctx
+        return self.ctx
+
+    def _preprocess(self, X, dim, weights=None, dec=None, omega=None, **kwargs):
+        """The prologue of every fit: the context, the preprocessor bound to it, the resident preprocessed matrix and the
+        sample dimensions.  `dec`: a Decomposer to fit in the same pass (Preprocessor.fit_transform_decompose); `kwargs` go
+        to Preprocessor.fit_transform."""
+        self._bind_context()
+        if dec is None:
+            mat = self.preprocessor.fit_transform(X, dim, weights, **kwargs)
+        else:
+            dec.ctx = self.ctx
+            mat = self.preprocessor.fit_transform_decompose(X, dim, weights, dec, omega)
+        self.sample_dims = self.preprocessor.sample_dims
+        return mat
+
+    def _centred_twin(self, mat, X, dim, weights):
+        """The matrix the reference's inner PCA decomposes: it centres the preprocessed field (opa.py:135-147,
+        eeof.py:99-122), and (X w / std) - mean is the preprocessing of X with center=True.  -> `mat` itself for a centred
+        model, otherwise a second resident matrix of the same input.  The caller owns what it gets: it frees the twin when
+        it is done with it, `mat` when it no longer needs it, and never the same matrix twice (`twin is mat`)."""
+        if self._params["center"]:
+            return mat
+        prm = self._params
+        pre = Preprocessor(True, prm["standardize"], prm["use_coslat"], prm["check_nans"], ctx=self.ctx, in_place=True)
+        return pre.fit_transform(X, dim, weights)
+
+    def _fit_now(self, X, dim, weights=None):
         self._decomposer_kwargs["lazy_input"] = labelled.is_lazy(X)
         omega = None if self._decomposer_kwargs["lazy_input"] else self._sketch_ahead(X, dim)
         # Preprocessor.fit_transform + Decomposer.fit (eof.py:85-97) as ONE engine call where the shape allows: the
         # column statistics ride on the first pass of the randomized SVD (eofx_fit_f32)
-        dec = Decomposer(ctx=self.ctx, **self._decomposer_kwargs)
-        mat = self.preprocessor.fit_transform_decompose(X, dim, weights, dec, omega)
-        self.sample_dims = self.preprocessor.sample_dims
+        dec = Decomposer(**self._decomposer_kwargs)
+        mat = self._preprocess(X, dim, weights, dec, omega)
         return self._fit_algorithm(mat, dec=dec)
 
     def _sketch_ahead(self, X, dim):
@@ -202,7 +240,7 @@ class ComplexEOF(EOF):
         vals, dims, coords, name, attrs = labelled.unpack(X)
         re = labelled.pack(np.ascontiguousarray(vals.real), dims, coords, name, attrs, X)
         im = labelled.pack(np.ascontiguousarray(vals.imag), dims, coords, name, attrs, X)
-        self.preprocessor_imag.ctx = self.ctx
+        self.preprocessor_imag.ctx = self._bind_context()       # (peek_std below runs before the prologue)
         std_c = None
         if self._params["standardize"]:
             # scaler.py:105-108 on complex data: numpy's std of a complex array is the real
@@ -212,18 +250,14 @@ class ComplexEOF(EOF):
             s_re, s_im = (np.where(v <= eps, 0.0, v)
                           for v in (self.preprocessor.peek_std(re, dim), self.preprocessor_imag.peek_std(im, dim)))
             std_c = np.maximum(np.sqrt(s_re ** 2 + s_im ** 2), eps)
-        A = self.preprocessor.fit_transform(re, dim, weights, std_override=std_c)
+        A = self._preprocess(re, dim, weights, std_override=std_c)
         B = self.preprocessor_imag.fit_transform(im, dim, weights, std_override=std_c)
         tv = self.preprocessor.total_variance + self.preprocessor_imag.total_variance
         return A, B, tv
 
     def _fit_now(self, X, dim, weights=None):
         self._reject_lazy(X)
-        self.ctx = self.ctx or engine.default_context()
-        self.preprocessor.ctx = self.ctx
-        A, B, tv = self._complex_parts(X, dim, weights)
-        self.sample_dims = self.preprocessor.sample_dims
-        return self._fit_complex(A, B, tv)
+        return self._fit_complex(*self._complex_parts(X, dim, weights))
 
     @staticmethod
     def _reject_lazy(X):
@@ -283,12 +317,7 @@ class ComplexEOF(EOF):
             return re
         Sim = np.ascontiguousarray(np.concatenate([S.imag, -S.real], axis=1), dtype=np.float32)
         im = self.preprocessor_imag.inverse_transform_data(engine.reconstruct(self.ctx, Sim, Vri), "reconstructed_data", fields, vs)
-
-        def join(a, b):
-            va, dims, coords, name, attrs = labelled.unpack(a)
-            return labelled.pack(va + 1j * labelled.unpack(b)[0], dims, coords, name, attrs, a)
-
-        return [join(a, b) for a, b in zip(re, im)] if isinstance(re, list) else join(re, im)
+        return labelled.complex_join(re, im)
 
     def components_amplitude(self, normalized=True):
         c = self.components(normalized)
@@ -326,8 +355,6 @@ class HilbertEOF(ComplexEOF):
 
     def _fit_now(self, X, dim, weights=None):
         self._reject_lazy(X)
-        self.ctx = self.ctx or engine.default_context()
-        self.preprocessor.ctx = self.ctx
         omega = self._sketch_ahead(X, dim)          # drawn on a worker thread while the Hilbert stage runs
         centred = bool(self._params["center"])
         # A centred field stays in place (the raw field through the Scaler map): the Hilbert stage then builds the
@@ -337,8 +364,7 @@ class HilbertEOF(ComplexEOF):
         # a land / sea mask (all-NaN grid points) stays in place too: zero columns through the Hilbert stage and the passes
         # of the decomposition (round 5; `_hilbert_masked_ok = False` forces the compaction route, for comparisons)
         self.preprocessor.masked_ok = self.preprocessor.in_place and getattr(self, "_hilbert_masked_ok", True)
-        A = self.preprocessor.fit_transform(X, dim, weights)
-        self.sample_dims = self.preprocessor.sample_dims
+        A = self._preprocess(X, dim, weights)
         if centred and self._operator_route_ok(A):
             return self._fit_operator(A, omega)
         B, A2 = engine.hilbert(self.ctx, A, self.padding, self.decay_factor, want_real=not centred)

@@ -46,14 +46,6 @@ def _is_y(name) -> bool:
     return isinstance(name, str) and name.lower() in Y_NAMES
 
 
-def _first_array(X):
-    if labelled.is_dataset(X):
-        return X[next(iter(X.data_vars))]
-    if isinstance(X, (list, tuple)):
-        return X[0]
-    return X
-
-
 def _coords_along(obj, dim):
     """{name: values} of the coordinates that run along `dim` besides `dim` itself: extra coords of the stand-in DataArray,
     non-dimension coordinates or MultiIndex levels of an xarray.DataArray"""
@@ -68,7 +60,7 @@ def sample_coordinates(X, sample_dims) -> np.ndarray:
     """(x, y) of every sample in the stacked sample order of the Preprocessor (sample dims in the given order,
     C order) -> [n, 2] float64.  x is the longitude for haversine.  gwpca.py:136-165 with coordinates taken by name."""
     sample_dims = _as_tuple(sample_dims)
-    obj = _first_array(X)
+    obj = labelled.first_array(X)
     vals, dims, coords, _, _ = labelled.unpack(obj)
     if len(sample_dims) == 1:
         d = sample_dims[0]
@@ -127,8 +119,7 @@ class GWPCA:
     def fit(self, X, dim, weights=None):
         sample_dims = _as_tuple(dim)
         xy = sample_coordinates(X, sample_dims)          # before any device work: the argument errors come first
-        vals = labelled.unpack(_first_array(X))[0]
-        if np.iscomplexobj(vals):
+        if labelled.is_complex(X):
             raise TypeError("GWPCA does not support complex data.")
         self.ctx = self.ctx or engine.default_context()
         self.preprocessor.ctx = self.ctx

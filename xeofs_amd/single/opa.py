@@ -32,8 +32,7 @@ import numpy as np
 
 from .. import engine, labelled, spca
 from ..linalg.decomposer import Decomposer
-from ..preprocessing import Preprocessor
-from .eof import EOF
+from .eof import EOF, NO_EXPLAINED_VARIANCE, NO_SINGULAR_VALUES
 
 
 def opa_lag_weights(n: int, tau_max: int) -> np.ndarray:
@@ -71,26 +70,12 @@ class OPA(EOF):
         self._params["solver_kwargs"] = dict(solver_kwargs)
 
     # ------------------------------------------------------------------ fit
-    @staticmethod
-    def _first_values(X):
-        return labelled.unpack(X[next(iter(X.data_vars))] if labelled.is_dataset(X) else
-                               (X[0] if isinstance(X, (list, tuple)) else X))[0]
-
     def _fit_now(self, X, dim, weights=None):
-        vals = self._first_values(X)
-        if vals.is_complex() if hasattr(vals, "is_complex") else np.iscomplexobj(vals):      # (device tensor | host array)
+        if labelled.is_complex(X):
             raise TypeError("This method does not support complex data.")
-        self.ctx = self.ctx or engine.default_context()
-        self.preprocessor.ctx = self.ctx
-        mat = self.preprocessor.fit_transform(X, dim, weights)
-        self.sample_dims = self.preprocessor.sample_dims
-        pmat = mat
-        if not self._params["center"]:
-            # the reference's inner PCA centres the preprocessed field (opa.py:135-147):
-            # (X w / std) - mean = the preprocessing of X with center=True
-            pre = Preprocessor(True, self._params["standardize"], self._params["use_coslat"], self._params["check_nans"],
-                               ctx=self.ctx, in_place=True)
-            pmat = pre.fit_transform(X, dim, weights)
+        mat = self._preprocess(X, dim, weights)
+        pmat = self._centred_twin(mat, X, dim, weights)
+        if pmat is not mat:
             mat.free()
         try:
             return self._fit_algorithm(pmat)
@@ -105,10 +90,7 @@ class OPA(EOF):
         w = opa_lag_weights(n, prm["tau_max"])
         # 1. inner PCA (opa.py:135-152)
         t0 = time.perf_counter()
-        pca = Decomposer(n_modes=prm["n_pca_modes"], ctx=ctx, solver=prm["solver"], random_state=prm["random_state"],
-                         compute=prm["compute"], solver_kwargs=prm["solver_kwargs"])
-        pca.fit(mat)
-        route = "exact" if pca.policy(mat.n, mat.p, quiet=True)[2] == 0 else "randomized"
+        pca = Decomposer.for_model(prm, prm["n_pca_modes"], ctx).fit(mat)
         root = np.sqrt(n - 1.0)
         S32 = np.ascontiguousarray(pca.U_.astype(np.float64) * pca.s_.astype(np.float64) / root, dtype=np.float32)
         Cmp32 = np.ascontiguousarray(pca.V_.astype(np.float64) * root, dtype=np.float32)
@@ -117,7 +99,7 @@ class OPA(EOF):
             raise ValueError(f"n_modes must be smaller or equal to the {q} PCA modes kept (n_modes={k})")
         t1 = time.perf_counter()
         # 2. lag covariances: C_0 from the actual scores and M, one kernel call each
-        Sd = torch.from_numpy(S32).to(f"cuda:{ctx.device}")
+        Sd = engine.device_panel(ctx, S32)
         C0 = engine.lagcov(ctx, Sd, np.array([1.0 / (n - 1.0)])).cpu().numpy()
         M = engine.lagcov(ctx, Sd, w).cpu().numpy()
         t2 = time.perf_counter()
@@ -152,7 +134,7 @@ class OPA(EOF):
         self._Vq = Vq * sg
         self._pca_scores, self._pca_components = S32, Cmp32
         t4 = time.perf_counter()
-        self.stats = dict(route=route, n_pca_modes=q, ms_pca=1e3 * (t1 - t0), ms_lagcov=1e3 * (t2 - t1),
+        self.stats = dict(route=pca.route_, n_pca_modes=q, ms_pca=1e3 * (t1 - t0), ms_lagcov=1e3 * (t2 - t1),
                           ms_eigen=1e3 * (t3 - t2), ms_project=1e3 * (t4 - t3))
         return self
 
@@ -174,10 +156,5 @@ class OPA(EOF):
     def decorrelation_time(self):
         return self._mode_array(self.data["decorrelation_time"], "decorrelation_time")
 
-    def singular_values(self):
-        raise AttributeError("OPA has no singular values (the reference's model does not define them)")
-
-    def explained_variance(self):
-        raise AttributeError("OPA has no explained variance (the reference's model does not define it)")
-
-    explained_variance_ratio = explained_variance
+    singular_values = NO_SINGULAR_VALUES
+    explained_variance = explained_variance_ratio = NO_EXPLAINED_VARIANCE

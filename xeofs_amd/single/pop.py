@@ -36,7 +36,7 @@ import numpy as np
 from .. import engine, labelled
 from ..linalg.decomposer import Decomposer
 from ..preprocessing import parse_scores
-from .eof import EOF, ComplexEOF
+from .eof import EOF, NO_EXPLAINED_VARIANCE, NO_SINGULAR_VALUES, ComplexEOF
 
 POP_QMAX = engine.PCMUL_AMAX          # PCA modes the PC-space product takes
 
@@ -153,18 +153,12 @@ class POP(EOF):
 
     # ------------------------------------------------------------------ fit
     def _fit_now(self, X, dim, weights=None):
-        from .opa import OPA
-
         if not self._params["use_pca"]:
             raise NotImplementedError("POP without the PCA reduction (use_pca=False) needs the inverse of a feature x feature "
                                       "covariance and is not implemented; use use_pca=True")
-        vals = OPA._first_values(X)
-        if vals.is_complex() if hasattr(vals, "is_complex") else np.iscomplexobj(vals):      # (device tensor | host array)
+        if labelled.is_complex(X):
             raise TypeError("This method does not support complex data.")
-        self.ctx = self.ctx or engine.default_context()
-        self.preprocessor.ctx = self.ctx
-        mat = self.preprocessor.fit_transform(X, dim, weights)
-        self.sample_dims = self.preprocessor.sample_dims
+        mat = self._preprocess(X, dim, weights)
         try:
             return self._fit_algorithm(mat)
         finally:
@@ -184,22 +178,16 @@ class POP(EOF):
             if n_pca != "all":
                 raise ValueError("`n_pca_modes` must be an integer, float or 'all'")
             n_pca = min(mat.n, mat.p)
-        pca = Decomposer(n_modes=n_pca, init_rank_reduction=prm["pca_init_rank_reduction"], ctx=ctx, solver=prm["solver"],
-                         random_state=prm["random_state"], compute=prm["compute"], solver_kwargs=prm["solver_kwargs"])
+        pca = Decomposer.for_model(prm, n_pca, ctx, init_rank_reduction=prm["pca_init_rank_reduction"])
         pca.fit(mat, total_variance=self.preprocessor.total_variance)
-        route = "exact" if pca.policy(mat.n, mat.p, quiet=True)[2] == 0 else "randomized"
-        # the reference's PCA keeps V and defines the scores as the projection X V (preprocessing/pca.py:115-139) -- U s up
-        # to the decomposition's rounding.  One more pass over the resident field, through the same kernel `transform` uses.
-        V32 = np.ascontiguousarray(pca.V_, dtype=np.float32)
-        S32 = np.ascontiguousarray(engine.project(ctx, mat, V32), dtype=np.float32)
+        V32, S32 = pca.projected_scores(mat)
         q = S32.shape[1]
         if q > POP_QMAX:
             raise ValueError(f"the PCA kept {q} modes; POP takes at most {POP_QMAX}: lower n_pca_modes "
                              f"(n_pca_modes={prm['n_pca_modes']})")
         t1 = time.perf_counter()
         # 2. C0 = S[:-1]^T S[:-1] and C1 = S[1:]^T S[:-1], one kernel call each
-        dev = f"cuda:{ctx.device}"
-        Sd = torch.from_numpy(S32).to(dev)
+        Sd = engine.device_panel(ctx, S32)
         C0 = engine.lagcov(ctx, Sd[:n - 1], np.array([1.0])).cpu().numpy()
         C1 = engine.lagcov(ctx, Sd, np.array([0.0, 1.0])).cpu().numpy().T          # (sum_t s_t s_{t+1}^T)^T
         t2 = time.perf_counter()
@@ -217,7 +205,7 @@ class POP(EOF):
         Sd64 = Sd.to(torch.float64)
         total_variance = float((Sd64 * Sd64).sum()) / (n - 1)
         # 7. components V [Re Pq | Im Pq], rounded once to float32
-        Cd = engine.pcmul(ctx, torch.from_numpy(V32).to(dev), np.concatenate([Pq.real, Pq.imag], axis=1), torch.float32)
+        Cd = engine.pcmul(ctx, V32, np.concatenate([Pq.real, Pq.imag], axis=1), torch.float32)
         Zh, Ch = Z.cpu().numpy(), Cd.cpu().numpy()
         scores = (Zh[:, :q] + 1j * Zh[:, q:])[:, order]
         comps = np.empty((Ch.shape[0], q), np.complex64)
@@ -229,7 +217,7 @@ class POP(EOF):
         self._Pq, self._W = Pq, pop_coefficient_matrix(Pq)
         self._pca_scores, self._pca_components = S32, V32
         t4 = time.perf_counter()
-        self.stats = dict(route=route, n_pca_modes=q, ms_pca=1e3 * (t1 - t0), ms_lagcov=1e3 * (t2 - t1),
+        self.stats = dict(route=pca.route_, n_pca_modes=q, ms_pca=1e3 * (t1 - t0), ms_lagcov=1e3 * (t2 - t1),
                           ms_eigen=1e3 * (t3 - t2), ms_project=1e3 * (t4 - t3))
         return self
 
@@ -259,10 +247,8 @@ class POP(EOF):
         if normalized:
             S = S * self.data["norms"][modes - 1]
         C = self.data["components"][:, modes - 1]
-        torch, ctx = engine._torch(), self.ctx
-        dev = f"cuda:{ctx.device}"
-        Zr = torch.from_numpy(np.ascontiguousarray(S.real)).to(dev)
-        Zi = torch.from_numpy(np.ascontiguousarray(S.imag)).to(dev)
+        ctx = self.ctx
+        Zr, Zi = engine.device_panel(ctx, S.real), engine.device_panel(ctx, S.imag)      # float64, staged once for the blocks
         P = C.shape[0]
         rec_re, rec_im = np.empty((S.shape[0], P)), np.empty((S.shape[0], P))
         for c0 in range(0, P, engine.PCMUL_BMAX):
@@ -277,12 +263,7 @@ class POP(EOF):
             im = pre.inverse_transform_data(rec_im, "reconstructed_data", fields, vs)
         finally:
             pre.mean_ = mean
-
-        def join(a, b):
-            va, dims, coords, name, attrs = labelled.unpack(a)
-            return labelled.pack(va + 1j * labelled.unpack(b)[0], dims, coords, name, attrs, a)
-
-        return [join(a, b) for a, b in zip(re, im)] if isinstance(re, list) else join(re, im)
+        return labelled.complex_join(re, im)
 
     # ------------------------------------------------------------------ accessors
     def components(self):
@@ -317,10 +298,5 @@ class POP(EOF):
     def scores_phase(self):
         return ComplexEOF._map(self.scores(), np.angle, "scores_phase")
 
-    def singular_values(self):
-        raise AttributeError("POP has no singular values (the reference's model does not define them)")
-
-    def explained_variance(self):
-        raise AttributeError("POP has no explained variance (the reference's model does not define it)")
-
-    explained_variance_ratio = explained_variance
+    singular_values = NO_SINGULAR_VALUES
+    explained_variance = explained_variance_ratio = NO_EXPLAINED_VARIANCE

@@ -20,7 +20,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import engine, labelled, spca
-from .eof import EOF
+from .eof import EOF, NO_SINGULAR_VALUES
 
 VALID_SOLVERS = ("auto", "full", "randomized")
 
@@ -47,9 +47,7 @@ class SparsePCA(EOF):
     # ------------------------------------------------------------------ fit
     def _check_arguments(self, X):
         prm = self._params
-        vals = labelled.unpack(X[next(iter(X.data_vars))] if labelled.is_dataset(X) else
-                               (X[0] if isinstance(X, (list, tuple)) else X))[0]
-        if np.iscomplexobj(vals):
+        if labelled.is_complex(X):
             raise TypeError("This method does not support complex data.")
         if prm["solver"] not in VALID_SOLVERS:
             raise ValueError(f"Unrecognized solver '{prm['solver']}'. Valid options are 'auto', 'full', and 'randomized'.")
@@ -60,11 +58,7 @@ class SparsePCA(EOF):
 
     def _fit_now(self, X, dim, weights=None):
         self._check_arguments(X)
-        self.ctx = self.ctx or engine.default_context()
-        self.preprocessor.ctx = self.ctx
-        mat = self.preprocessor.fit_transform(X, dim, weights)
-        self.sample_dims = self.preprocessor.sample_dims
-        return self._fit_algorithm(mat)
+        return self._fit_algorithm(self._preprocess(X, dim, weights))
 
     def use_exact(self, n: int, p: int) -> bool:
         """sparse_pca.py:161-178: "auto" takes the exact route iff max(n, p) < 500 and n_modes > int(0.8 min(n, p))"""
@@ -115,8 +109,7 @@ class SparsePCA(EOF):
         """the sparse weight matrix B (not renormalised, as in the reference)"""
         return self.preprocessor.inverse_transform_components(self.data["components"], "components", self.attrs)
 
-    def singular_values(self):
-        raise AttributeError("SparsePCA has no singular values (the reference's model does not define them)")
+    singular_values = NO_SINGULAR_VALUES
 
 
 def explained_variance(dtilde, n: int, m_c: int, k: int, oversample: int, exact: bool) -> np.ndarray:

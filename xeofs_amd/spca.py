@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import ptr, raise_for
-from .engine import Context, ResidentMatrix, _torch, panel_mul, panel_tmul, panel_width, sketch_matrix
+from .engine import Context, ResidentMatrix, _torch, device_panel, panel_mul, panel_tmul, panel_width, sketch_matrix
 
 SPCA_KMAX = 64            # the loop kernels' limits (modes, columns of V); wider shapes take the general route
 SPCA_LMAX = 128
@@ -20,9 +20,7 @@ SPCA_GAMMA = 0.1          # outlier threshold of the robust route (compute_spca'
 
 def _dev64(ctx: Context, a):
     """a float64 C-contiguous device tensor of a numpy array / tensor"""
-    torch = _torch()
-    return torch.as_tensor(np.asarray(a) if not hasattr(a, "data_ptr") else a, dtype=torch.float64,
-                           device=f"cuda:{ctx.device}").contiguous()
+    return device_panel(ctx, a, "a", (_torch().float64,)).contiguous()
 
 
 def spca_gram(ctx: Context, X, Y):
