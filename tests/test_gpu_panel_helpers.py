@@ -3,7 +3,7 @@ bit where the operation is exact): ties, signed zeros, constant columns, row cou
 the grid stride, row counts beyond the partial cap (the part loop wraps), panel widths 32, 64, 96 and 256.
 
 Tolerances: exact / bitwise where stated; 1 ulp of float32 for |re + i im|; 1e-14 * sum|a||b| for the float64 dot product;
-1e-12 relative for the float64 norms; the per-element product bound 1e-5 * sum|a||b| of tests/test_gpu_parity.py for the
+1e-12 relative for the float64 norms; rows * 2^-53 * sum|a||b| for the float64 Gram matrix of a panel; the per-element product bound 1e-5 * sum|a||b| of tests/test_gpu_parity.py for the
 Gram and complex products; 2e-5 of the series' scale for the Hilbert operator (test_hilbert_stage_vs_oracle);
 1e-12 / 1e-11 * ||A|| for the host eigensolver.
 """
@@ -199,6 +199,26 @@ def test_panel_rownorm(ctx, rows, L):
     got = engine.panel_rownorm(ctx, _dev(P), rows)
     ref = np.sqrt((P[:rows].astype(np.float64) ** 2).sum(1))
     assert np.all(np.abs(got - ref) <= 1e-12 * ref)
+
+
+@pytest.mark.parametrize("L", [32, 64, 96, 160, 256])
+@pytest.mark.parametrize("rows", [1, 5, 4099])
+def test_panel_gram_edges(ctx, rows, L):
+    """eofx_panel_gram_f64 at its edges: fewer rows than one k-step of four, a ragged k-step, 33 row partials with a ragged
+    tail; half a 64-column sub-block, one, a ragged second, three, four.  The products of float32 values are exact in
+    float64, so only the rows - 1 additions round: |G - P^T P| <= rows 2^-53 |P|^T |P| per element.  G == G^T bit for
+    bit (the mirrored stores, the diagonal tiles) and a second call returns the same bits."""
+    from xeofs_amd import engine
+
+    rng = np.random.default_rng(1000 * rows + L)
+    P = (rng.standard_normal((rows, L)) * 10.0 ** rng.uniform(-2, 2, (1, L))).astype(np.float32)
+    dP = _dev(P)
+    G = _host(engine.panel_gram(ctx, dP))
+    P64 = P.astype(np.float64)
+    ref, S = P64.T @ P64, np.abs(P64).T @ np.abs(P64)
+    assert np.all(np.abs(G - ref) <= rows * 2.0 ** -53 * S)
+    assert np.array_equal(G.view(np.uint64), G.T.view(np.uint64))
+    assert np.array_equal(G.view(np.uint64), _host(engine.panel_gram(ctx, dP)).view(np.uint64))
 
 
 @pytest.mark.parametrize("layout", ["written", "in_place", "masked"])

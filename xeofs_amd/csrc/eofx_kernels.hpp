@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "eofx_mfma64.hpp"
+
 namespace eofx {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -1023,8 +1025,6 @@ __global__ __launch_bounds__(256) void panel_absmax_kernel(const float* __restri
 //   row k0 + kq: the four floats are element (i = c, k = kq) of FOUR A fragments (sub-tile t holds columns 4 i + t).
 //   Split-K partials are float64 (Cd), reduced by splitk_reduce_f64_kernel; a single split writes float32 directly.
 // ---------------------------------------------------------------------------------
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
 template <int NB>
 __global__ __launch_bounds__(512) void atb_f64_kernel(const float* __restrict__ A, int64_t lda,
                                                        const float* __restrict__ B, int ldb,
@@ -1178,32 +1178,29 @@ __global__ __launch_bounds__(256) void symmetrize_lower_kernel(float* __restrict
 
 // ---------------------------------------------------------------------------------
 // gram_mfma: Gpart[bx][L x L] = sum over this block's rows of P[r,:]^T P[r,:]  (float64) on the fp64 matrix cores
-//   (v_mfma_f64_16x16x4_f64).  grid = (nbx, nb*nb) where nb = ceil(L/64); every workgroup writes one partial of its 64x64 sub-block (its four waves meet in LDS in a fixed
-//   order); the nbx partials are summed in a fixed order by f64_reduce_kernel.
-//   Per k-step a wave reads 4 rows x 64 columns (lane (c = l % 16, k = l / 16) loads the float4 at
-//   P[row + k][64 b + 4 c ..]: one full 256 B row per 16 lanes), converts to float64 and issues the 16
-//   products a[qa] x b[qb]: lane c of "column group" q stands for column 4 c + q, so tile (qa, qb) holds
-//   G[64 bi + 4 i + qa][64 bj + 4 j + qb].  Products and sums are exact float64 (inputs are float32).
+//   (eofx_mfma64.hpp).  grid = (nbx, nb*nb) where nb = ceil(L/64); every workgroup writes one partial of its 64x64
+//   sub-block (its four waves meet in LDS in a fixed order); the nbx partials are summed in a fixed order by
+//   f64_reduce_kernel.
+//   Per k-step a wave reads 4 rows x 64 columns (lane (c, k) loads the float4 at P[row + k][64 b + 4 c ..]: one full
+//   256 B row per 16 lanes), converts to float64 and issues the 16 products a[x] b[y]: the float4's element x stands
+//   for column 4 c + x, so the accumulators are an interleaved block.  Products and sums are exact float64 (inputs
+//   are float32).
 // ---------------------------------------------------------------------------------
-
 __global__ __launch_bounds__(256) void gram_mfma_kernel(const float* __restrict__ P, int64_t rows, int L,
                                                          double* __restrict__ Gpart) {
   const int nb = (L + 63) / 64;
   const int bi = blockIdx.y / nb, bj = blockIdx.y % nb;
   if (bi > bj) return;             // G is symmetric: the sub-block (bj, bi) writes this one as well
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lc = lane & 15, lk = lane >> 4;
-  const int ca = 64 * bi + 4 * lc, cb = 64 * bj + 4 * lc;
+  const int wave = threadIdx.x >> 6;
+  const Mfma64Lane ln = mfma64_lane();
+  const int ca = 64 * bi + 4 * ln.c, cb = 64 * bj + 4 * ln.c;
   const bool same = (bi == bj);
   f64x4 acc[4][4];
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int y = 0; y < 4; ++y) acc[x][y] = f64x4{0.0, 0.0, 0.0, 0.0};
+  mfma64_zero(acc);
   const int64_t wstride = (int64_t)gridDim.x * 4 * 4;        // rows covered by one sweep of all waves
   // software pipeline: the loads of the next k-step are in flight while the 16 products of this one issue
   auto fetch = [&](int64_t r0, f32x4& va, f32x4& vb) {
-    const int64_t r = r0 + lk;
+    const int64_t r = r0 + ln.k;
     va = f32x4{0.f, 0.f, 0.f, 0.f};
     vb = va;
     if (r < rows) {
@@ -1225,19 +1222,12 @@ __global__ __launch_bounds__(256) void gram_mfma_kernel(const float* __restrict_
       const f32x4 va = pa[d], vb = pb[d];
       fetch(r0 + (GRAM_PF + d) * wstride, pa[d], pb[d]);
       __builtin_amdgcn_sched_barrier(0);
-      if (same) {       // diagonal sub-block: tile (x, y) is the transpose of tile (y, x) -- 10 of the 16 products
-#pragma unroll
-        for (int x = 0; x < 4; ++x)
-#pragma unroll
-          for (int y = x; y < 4; ++y)
-            acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)va[x], (double)vb[y], acc[x][y], 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int x = 0; x < 4; ++x)
-#pragma unroll
-          for (int y = 0; y < 4; ++y)
-            acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)va[x], (double)vb[y], acc[x][y], 0, 0, 0);
-      }
+      const double a[4] = {(double)va[0], (double)va[1], (double)va[2], (double)va[3]};
+      const double b[4] = {(double)vb[0], (double)vb[1], (double)vb[2], (double)vb[3]};
+      if (same)         // diagonal sub-block: tile (x, y) is the transpose of tile (y, x) -- 10 of the 16 products
+        mfma64_step(acc, a, b, [](int x, int y) { return y >= x; });
+      else
+        mfma64_step(acc, a, b, Mfma64All{});
     }
   }
   // The four waves add their tiles into ONE 64 x 64 block in LDS, wave after wave (fixed order), and the workgroup writes
@@ -1245,25 +1235,17 @@ __global__ __launch_bounds__(256) void gram_mfma_kernel(const float* __restrict_
   // the products themselves: 67 MB of partials for a 265 MB panel, profiles/r03_small_kernel_probe.txt).
   __shared__ double Gs[64][65];
   for (int w = 0; w < 4; ++w) {
-    if (wave == w) {
-#pragma unroll
-      for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) {
-          if (same && x > y) continue;                          // (tile (y, x) writes both triangles)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int i = 4 * (lk + 4 * q) + x, j = 4 * lc + y; // D[lane / 16 + 4 reg][lane % 16] (measured layout)
-            if (w == 0) {
-              Gs[i][j] = acc[x][y][q];
-              if (same && x < y) Gs[j][i] = acc[x][y][q];
-            } else {
-              Gs[i][j] += acc[x][y][q];
-              if (same && x < y) Gs[j][i] += acc[x][y][q];
-            }
-          }
-        }
-    }
+    if (wave == w)
+      mfma64_each_interleaved(acc, [&](int x, int y) { return !(same && x > y); },     // (tile (y, x) writes both triangles)
+                              [&](int x, int y, int i, int j, double v) {
+                                if (w == 0) {
+                                  Gs[i][j] = v;
+                                  if (same && x < y) Gs[j][i] = v;
+                                } else {
+                                  Gs[i][j] += v;
+                                  if (same && x < y) Gs[j][i] += v;
+                                }
+                              });
     __syncthreads();
   }
   double* G = Gpart + (int64_t)blockIdx.x * (int64_t)L * L;
@@ -1300,7 +1282,7 @@ __global__ __launch_bounds__(256) void f64_reduce_kernel(const double* __restric
 // dimensions (Pa: La columns, Pb: Lb columns; both multiples of 64) on the fp64 matrix cores -- the projection
 // coefficients K^H W and the columns of the Rayleigh-Ritz matrix of the complex block-Krylov decomposition.
 //   grid = (nbx, (La / 64) * (Lb / 64)); same wave layout, prefetch depth and fixed-order wave merge as gram_mfma_kernel
-//   (its bi != bj case); partial b of sub-block (bi, bj) lands in part[b][La x Lb]; f64_reduce_kernel sums the partials.
+//   (its bi != bj case; kept as its own text: one shared body measured 2 % slower here, docs/EXPERIMENTS.md); partial b of sub-block (bi, bj) lands in part[b][La x Lb]; f64_reduce_kernel sums the partials.
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void xgram_mfma_kernel(const float* __restrict__ Pa, int64_t lda, const float* __restrict__ Pb,
                                                           int64_t ldb, int64_t rows, int La, int Lb, double* __restrict__ part) {
@@ -1351,7 +1333,7 @@ __global__ __launch_bounds__(256) void xgram_mfma_kernel(const float* __restrict
         for (int y = 0; y < 4; ++y)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const int i = 4 * (lk + 4 * q) + x, j = 4 * lc + y;    // D[lane / 16 + 4 reg][lane % 16], as in gram_mfma_kernel
+            const int i = 4 * (lk + 4 * q) + x, j = 4 * lc + y;    // the interleaved block of eofx_mfma64.hpp
             if (w == 0) Gs[i][j] = acc[x][y][q];
             else Gs[i][j] += acc[x][y][q];
           }
@@ -1635,7 +1617,6 @@ __global__ void chol_blocked_export_kernel(const double* __restrict__ X, int Lb,
 //      B fragment is read from LDS under the same naming: Ms[kc + 16 tt + 4 kq + c][16 q + i].  No LDS trip for P.
 //   D[kq + 4 r][i] of tile (t, q) (measured layout) = out[row0 + 16 t + kq + 4 r][c0 + 16 q + i].
 // ---------------------------------------------------------------------------------
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int PMM_LD = 66;   // doubles per staged row of Mx
 
 // GEN (round 5, the block-Krylov steps of eofx_rsvd_c64): the inner dimension is a list of 64-column chunks, chunk c at
@@ -2808,12 +2789,35 @@ __global__ __launch_bounds__(256) void cpanel_colabsmax_kernel(const float* __re
 // 64 x 64 real result [Xr | Xi]^T [Tr | Ti] carries the four blocks of X^H T = (Xr^T Tr + Xi^T Ti) + i (Xr^T Ti - Xi^T Tr).
 // grid = (nblocks); each workgroup owns a strided set of 32-row tiles; partials reduced in fixed order.
 // ---------------------------------------------------------------------------------
+// The element-wise step t = f(b).  br_ / bi_ are the real and imaginary parts that b belongs to (modes 2 / 3), taken by
+// reference so that the real modes never read them.  |b|^2 is written as the fused multiply-add that the compiler made
+// of br_ * br_ + bi_ * bi_ in both kernels: which square it fuses is otherwise its choice, and the bits of G with it.
+__device__ __forceinline__ double rot_transform(int mode, double b, const double& br_, const double& bi_, double aux,
+                                                double power) {
+  double t;
+  if (mode >= 2) {       // complex: the column pairs with its partner half a panel away
+    const double a2 = fma(br_, br_, bi_ * bi_);
+    if (mode == 2) {
+      t = b * (a2 - aux);
+    } else {
+      const double za = sqrt(a2) / aux;
+      t = (power == 1.0 || !(za > 0.0)) ? b / aux : (b / aux) * pow(za, power - 1.0);
+    }
+  } else if (mode == 0) {
+    t = b * (b * b - aux);
+  } else {
+    const double z = b / aux;
+    t = (power == 1.0) ? z : z * pow(fabs(z), power - 1.0);
+  }
+  return t;
+}
+
 __global__ __launch_bounds__(256) void rot_step_kernel(const float* __restrict__ X, int64_t rows, int L,
                                                        const double* __restrict__ R,
                                                        const double* __restrict__ aux, int mode,
                                                        double power, double* __restrict__ Gpart) {
-  // Both matrix products of a 32-row tile run on the fp64 matrix cores (v_mfma_f64_16x16x4_f64; operand / result lane
-  // maps as in gram_mfma_kernel): b = x R as 2 x 4 tiles over 16 k-steps (wave w: row tile w & 1, column tiles
+  // Both matrix products of a 32-row tile run on the fp64 matrix cores (operand / result lane maps: eofx_mfma64.hpp):
+  // b = x R as 2 x 4 tiles over 16 k-steps (wave w: row tile w & 1, column tiles
   // 2 (w >> 1) + {0, 1}), then G += left^T t as 4 x 4 tiles over 8 k-steps (wave w: tile row w, accumulators kept
   // across the whole launch).  Only the elementwise transform in between is vector-ALU work.  LDS rows are padded by
   // two doubles (float: four) so that the four k-rows a wave reads at once fall into different banks.
@@ -2822,16 +2826,16 @@ __global__ __launch_bounds__(256) void rot_step_kernel(const float* __restrict__
   __shared__ double Ts[32][66];
   __shared__ double Ls[32][66];   // b = x R (the left factor in modes 1 / 3, the partner parts in modes 2 / 3)
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 15, lk = lane >> 4;
+  const int wave = tid >> 6;
+  const Mfma64Lane ln = mfma64_lane();
+  const int li = ln.c, lk = ln.k;
   for (int i = tid; i < 64 * 64; i += 256) {
     const int r = i >> 6, c = i & 63;
     Rs[r][c] = (r < L && c < L) ? R[(int64_t)r * L + c] : 0.0;
   }
   const int brow = tid >> 3, bc0 = (tid & 7) * 8;   // elementwise step: row brow, columns bc0..bc0+7
   f64x4 acc[4];
-#pragma unroll
-  for (int y = 0; y < 4; ++y) acc[y] = f64x4{0.0, 0.0, 0.0, 0.0};
+  mfma64_zero(acc);
   double auxr[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) auxr[e] = (bc0 + e < L) ? aux[bc0 + e] : ((mode & 1) ? 1.0 : 0.0);
@@ -2846,40 +2850,23 @@ __global__ __launch_bounds__(256) void rot_step_kernel(const float* __restrict__
     }
     __syncthreads();
     // b = x R
-    f64x4 bt[2] = {f64x4{0.0, 0.0, 0.0, 0.0}, f64x4{0.0, 0.0, 0.0, 0.0}};
+    f64x4 bt[2];
+    mfma64_zero(bt);
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
       const double a = (double)Xs[16 * rt + li][4 * s + lk];
 #pragma unroll
       for (int c = 0; c < 2; ++c)
-        bt[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Rs[4 * s + lk][16 * (ct0 + c) + li], bt[c], 0, 0, 0);
+        mfma64_step(bt[c], a, Rs[4 * s + lk][16 * (ct0 + c) + li]);
     }
 #pragma unroll
     for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Ls[16 * rt + lk + 4 * r][16 * (ct0 + c) + li] = bt[c][r];   // D[lk + 4 r][li]
+      mfma64_each(bt[c], [&](int r, int j, double v) { Ls[16 * rt + r][16 * (ct0 + c) + j] = v; });
     __syncthreads();
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const double b = Ls[brow][bc0 + e];
-      double t;
-      if (mode >= 2) {       // complex: column j pairs with column j + 32
-        const int cr = (bc0 + e) & 31;
-        const double br_ = Ls[brow][cr], bi_ = Ls[brow][cr + 32];
-        const double a2 = br_ * br_ + bi_ * bi_;
-        if (mode == 2) {
-          t = b * (a2 - auxr[e]);
-        } else {
-          const double za = sqrt(a2) / auxr[e];
-          t = (power == 1.0 || !(za > 0.0)) ? b / auxr[e] : (b / auxr[e]) * pow(za, power - 1.0);
-        }
-      } else if (mode == 0) {
-        t = b * (b * b - auxr[e]);
-      } else {
-        const double z = b / auxr[e];
-        t = (power == 1.0) ? z : z * pow(fabs(z), power - 1.0);
-      }
-      Ts[brow][bc0 + e] = t;
+      const int cr = (bc0 + e) & 31;       // complex: column j pairs with column j + 32
+      Ts[brow][bc0 + e] = rot_transform(mode, Ls[brow][bc0 + e], Ls[brow][cr], Ls[brow][cr + 32], auxr[e], power);
     }
     __syncthreads();
     // G += left^T t  (left = x in modes 0 / 2, b in modes 1 / 3): k runs over the 32 rows of the tile
@@ -2888,18 +2875,17 @@ __global__ __launch_bounds__(256) void rot_step_kernel(const float* __restrict__
       const double a = (mode & 1) ? Ls[4 * s + lk][16 * wave + li] : (double)Xs[4 * s + lk][16 * wave + li];
 #pragma unroll
       for (int y = 0; y < 4; ++y)
-        acc[y] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Ts[4 * s + lk][16 * y + li], acc[y], 0, 0, 0);
+        mfma64_step(acc[y], a, Ts[4 * s + lk][16 * y + li]);
     }
     __syncthreads();
   }
   double* G = Gpart + (int64_t)blockIdx.x * L * L;
 #pragma unroll
   for (int y = 0; y < 4; ++y)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int gi = 16 * wave + lk + 4 * r, gj = 16 * y + li;      // D[lk + 4 r][li] of tile (wave, y)
-      if (gi < L && gj < L) G[(int64_t)gi * L + gj] = acc[y][r];
-    }
+    mfma64_each(acc[y], [&](int r, int j, double v) {     // tile (wave, y)
+      const int gi = 16 * wave + r, gj = 16 * y + j;
+      if (gi < L && gj < L) G[(int64_t)gi * L + gj] = v;
+    });
 }
 
 // The same step for 65 .. 256 modes (panels 128 / 256 wide; complex: 64 / 128 columns per half).  An LW x LW float64
@@ -2958,26 +2944,8 @@ __global__ __launch_bounds__(512) void rot_step_wide_kernel(const float* __restr
     __syncthreads();
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const int col = 64 * cb + bq + e;
-      const double b = Ls[brow][col];
-      double t;
-      if (mode >= 2) {
-        const int cr = col & (HALF - 1);
-        const double br_ = Ls[brow][cr], bi_ = Ls[brow][cr + HALF];
-        const double a2 = br_ * br_ + bi_ * bi_;
-        if (mode == 2) {
-          t = b * (a2 - auxr[e]);
-        } else {
-          const double za = sqrt(a2) / auxr[e];
-          t = (power == 1.0 || !(za > 0.0)) ? b / auxr[e] : (b / auxr[e]) * pow(za, power - 1.0);
-        }
-      } else if (mode == 0) {
-        t = b * (b * b - auxr[e]);
-      } else {
-        const double z = b / auxr[e];
-        t = (power == 1.0) ? z : z * pow(fabs(z), power - 1.0);
-      }
-      Ts[brow][bq + e] = t;
+      const int col = 64 * cb + bq + e, cr = col & (HALF - 1);
+      Ts[brow][bq + e] = rot_transform(mode, Ls[brow][col], Ls[brow][cr], Ls[brow][cr + HALF], auxr[e], power);
     }
     __syncthreads();
     // G[:, block] += left^T t

@@ -11,8 +11,8 @@
 //   lagcov_fir_kernel     Y [n x p] float64 written once (the route of ntau > LAGCOV_FUSE_NTAU);
 //   lagcov_cross_kernel   per row tile of 64 samples and column block of 64: the tile of Y in LDS -- filtered there from the
 //                         staged rows of S plus their ntau - 1 halo rows (FUSED: Y never reaches HBM) or read from the
-//                         written Y --, then S^T Y on the fp64 matrix cores (v_mfma_f64_16x16x4_f64), wave w owning the
-//                         64 x 64 output block of column block 4 g + w of S.  A workgroup walks its row tiles in ascending
+//                         written Y --, then S^T Y on the fp64 matrix cores (eofx_mfma64.hpp; a blocked 4 x 4 block
+//                         of accumulators), wave w owning the 64 x 64 output block of column block 4 g + w of S.  A workgroup walks its row tiles in ascending
 //                         order and writes one partial; f64_reduce_kernel (eofx_kernels.hpp) sums the partials in a fixed order.
 // Both filters slide a window of 16 outputs per thread along the samples: one read of S feeds 16 fused multiply-adds, and
 // every Y[t, j] is summed over tau ascending.  The weights are read from a copy padded with 15 zeros on either side
@@ -77,13 +77,11 @@ __global__ __launch_bounds__(256, 2) void lagcov_cross_kernel(const float* __res
   float* Sh = reinterpret_cast<float*>(lagcov_lds + LAGCOV_R * LAGCOV_YLD);   // [LAGCOV_SROWS][64] (FUSED)
   const int nb = (p + 63) / 64;
   const int bj = blockIdx.y % nb, bi = 4 * (blockIdx.y / nb) + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63, lc = lane & 15, lk = lane >> 4;
+  const Mfma64Lane ln = mfma64_lane();
+  const int lc = ln.c, lk = ln.k;
   const int64_t ntiles = (n + LAGCOV_R - 1) / LAGCOV_R;
   f64x4 acc[4][4];
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int y = 0; y < 4; ++y) acc[x][y] = f64x4{0.0, 0.0, 0.0, 0.0};
+  mfma64_zero(acc);
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t r0 = tile * LAGCOV_R;
     // this wave's rows of S, eight k-steps at a time: the first half is in flight while the tile of Y is made, the second
@@ -128,29 +126,22 @@ __global__ __launch_bounds__(256, 2) void lagcov_cross_kernel(const float* __res
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int s = 0; s < H; ++s) {
-          double b[4];
+          double a[4], b[4];
+#pragma unroll
+          for (int x = 0; x < 4; ++x) a[x] = (double)av[h][s][x];
 #pragma unroll
           for (int y = 0; y < 4; ++y) b[y] = Ys[(4 * (H * h + s) + lk) * LAGCOV_YLD + 16 * y + lc];
-#pragma unroll
-          for (int x = 0; x < 4; ++x)
-#pragma unroll
-            for (int y = 0; y < 4; ++y)
-              acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[h][s][x], b[y], acc[x][y], 0, 0, 0);
+          mfma64_step(acc, a, b, Mfma64All{});
         }
     }
     __syncthreads();      // the next tile overwrites the LDS
   }
   if (bi >= nb) return;
   double* G = part + (int64_t)blockIdx.x * p * p;
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int y = 0; y < 4; ++y)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int gi = 64 * bi + 16 * x + lk + 4 * q, gj = 64 * bj + 16 * y + lc;    // D[lane / 16 + 4 reg][lane % 16]
-        if (gi < p && gj < p) G[(int64_t)gi * p + gj] = acc[x][y][q];
-      }
+  mfma64_each_blocked(acc, Mfma64All{}, [&](int, int, int i, int j, double v) {
+    const int gi = 64 * bi + i, gj = 64 * bj + j;
+    if (gi < p && gj < p) G[(int64_t)gi * p + gj] = v;
+  });
 }
 
 }  // namespace eofx

@@ -3,10 +3,9 @@
 //     Y [rows x b] = X [rows x a] M [a x b]        (X float32 | float64, M float64, Y float64 | float32; a <= 1024, b <= 2048)
 //
 // a tall panel -- the n samples' PCA scores or the P features' PCA patterns -- times a small dense matrix whose inner length
-// is the number of PCA modes.  Accumulated in float64 on the fp64 matrix cores (v_mfma_f64_16x16x4_f64) and rounded once.
+// is the number of PCA modes.  Accumulated in float64 on the fp64 matrix cores (eofx_mfma64.hpp) and rounded once.
 //   pcmul_kernel   a workgroup of four waves owns a tile of 64 rows and 256 columns of Y, wave w the 64 x 64 block of columns
-//                  64 w .. 64 w + 63 (16 accumulators of 16 x 16, the lane layout of lagcov_cross_kernel: A[i][k] from lane
-//                  (i, k) = (lane % 16, lane / 16), B[k][j] from lane (j, k), D[lane / 16 + 4 reg][lane % 16]).  The inner
+//                  64 w .. 64 w + 63 (a blocked 4 x 4 block of accumulators).  The inner
 //                  length is walked in slabs of 16: the slab of X (64 x 16, converted to float64 in registers) and of M
 //                  (16 x 256) are fetched into registers while the products of the previous slab issue, then stored to LDS.
 //                  Row strides: 18 doubles for X (lanes (i, k) and (i, k + 1), i < 16, on 32 distinct bank pairs: 36 i mod 64
@@ -36,17 +35,16 @@ __global__ __launch_bounds__(256, 2) void pcmul_kernel(const TX* __restrict__ X,
                                                        const double* __restrict__ M, int b, TY* __restrict__ Y, int64_t ldy) {
   __shared__ double Xs[PCMUL_R * PCMUL_XLD];
   __shared__ double Ms[PCMUL_K * PCMUL_MLD];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lk = lane >> 4;
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const Mfma64Lane ln = mfma64_lane();
+  const int lc = ln.c, lk = ln.k;
   const int64_t r0 = (int64_t)blockIdx.x * PCMUL_R;
   const int cg = blockIdx.y * PCMUL_C;             // first column of the workgroup
   const int c0 = cg + 64 * wave;                   // first column of the wave
   const int nxb = (int)((rows - r0 < PCMUL_R ? rows - r0 : (int64_t)PCMUL_R) + 15) / 16;       // 16-row blocks with a row of Y
   const int nyb = c0 >= b ? 0 : ((b - c0 < 64 ? b - c0 : 64) + 15) / 16;                       // 16-column blocks of this wave
   f64x4 acc[4][4];
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int y = 0; y < 4; ++y) acc[x][y] = f64x4{0.0, 0.0, 0.0, 0.0};
+  mfma64_zero(acc);
   double xr[PCMUL_XE], mr[PCMUL_ME];
   auto fetch = [&](int k0) {
 #pragma unroll
@@ -80,23 +78,14 @@ __global__ __launch_bounds__(256, 2) void pcmul_kernel(const TX* __restrict__ X,
       for (int x = 0; x < 4; ++x) av[x] = Xs[(16 * x + lc) * PCMUL_XLD + 4 * s + lk];
 #pragma unroll
       for (int y = 0; y < 4; ++y) bv[y] = Ms[(4 * s + lk) * PCMUL_MLD + 64 * wave + 16 * y + lc];
-#pragma unroll
-      for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y)
-          if (x < nxb && y < nyb) acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[x], bv[y], acc[x][y], 0, 0, 0);
+      mfma64_step(acc, av, bv, [&](int x, int y) { return x < nxb && y < nyb; });
     }
   }
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int y = 0; y < 4; ++y)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int64_t r = r0 + 16 * x + lk + 4 * q;                      // D[lane / 16 + 4 reg][lane % 16]
-        const int c = c0 + 16 * y + lc;
-        if (r < rows && c < b) Y[r * ldy + c] = (TY)acc[x][y][q];
-      }
+  mfma64_each_blocked(acc, Mfma64All{}, [&](int, int, int i, int j, double v) {
+    const int64_t r = r0 + i;
+    const int c = c0 + j;
+    if (r < rows && c < b) Y[r * ldy + c] = (TY)v;
+  });
 }
 
 }  // namespace eofx

@@ -7,8 +7,7 @@
 // covariance and subtracts its diagonal blocks; here those blocks and the lower triangle are never computed.
 //   viewcov_zero_kernel     C = +0.0 over its p x p window (row stride ldc).
 //   viewcov_kernel          one workgroup of four waves per LISTED tile of 128 x 128 outputs, wave (wi, wj) owning the 64 x 64
-//                           block (16 accumulators of 16 x 16, the lane layout of lagcov_cross_kernel: A[i][k] from lane
-//                           (i, k) = (lane % 16, lane / 16), B[k][j] from lane (j, k), D[lane / 16 + 4 reg][lane % 16]).
+//                           block (a blocked 4 x 4 block of accumulators on the fp64 matrix cores, eofx_mfma64.hpp).
 //                           The host lists the tiles (bi, bj), bj >= bi, that hold a wanted output: on or above the diagonal
 //                           and, without keep_diag, not wholly inside one view.  The samples are walked in slabs of 16: the
 //                           two slabs of Z (16 x 128 columns of the rows and of the columns of the tile) are fetched as
@@ -63,7 +62,9 @@ __global__ __launch_bounds__(256, 2) void viewcov_kernel(const float* __restrict
                                                          double* __restrict__ C, int64_t ldc, double* __restrict__ part) {
   __shared__ double As[VIEWCOV_K * VIEWCOV_LD];
   __shared__ double Bs[VIEWCOV_K * VIEWCOV_LD];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lk = lane >> 4;
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const Mfma64Lane ln = mfma64_lane();
+  const int lc = ln.c, lk = ln.k;
   const int wi = wave >> 1, wj = wave & 1;
   const int bi = tiles[2 * blockIdx.x], bj = tiles[2 * blockIdx.x + 1];
   const int i0 = bi * VIEWCOV_T, j0 = bj * VIEWCOV_T;       // first row and column of the tile
@@ -85,10 +86,9 @@ __global__ __launch_bounds__(256, 2) void viewcov_kernel(const float* __restrict
   const int64_t s0 = (int64_t)blockIdx.y * chunk;
   const int64_t s1 = s0 + chunk < nslabs ? s0 + chunk : nslabs;
   f64x4 acc[4][4];
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int y = 0; y < 4; ++y) acc[x][y] = f64x4{0.0, 0.0, 0.0, 0.0};
+  mfma64_zero(acc);
+  // the 16 x 16 blocks of this wave that are computed and written
+  const auto keep = [&](int x, int y) { return x < nxb && y < nyb && !(diag && x > y); };
   float ar[VIEWCOV_E], br[VIEWCOV_E];
   auto fetch = [&](int64_t slab) {
 #pragma unroll
@@ -118,30 +118,20 @@ __global__ __launch_bounds__(256, 2) void viewcov_kernel(const float* __restrict
       for (int x = 0; x < 4; ++x) av[x] = As[(4 * s + lk) * VIEWCOV_LD + 64 * wi + 16 * x + lc];
 #pragma unroll
       for (int y = 0; y < 4; ++y) bv[y] = Bs[(4 * s + lk) * VIEWCOV_LD + 64 * wj + 16 * y + lc];
-#pragma unroll
-      for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y)
-          if (x < nxb && y < nyb && !(diag && x > y)) acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[x], bv[y], acc[x][y], 0, 0, 0);
+      mfma64_step(acc, av, bv, keep);
     }
   }
   if (!active) return;
   const double denom = (double)(n - 1);
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int y = 0; y < 4; ++y)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (x >= nxb || y >= nyb || (diag && x > y)) continue;
-        const int li = 64 * wi + 16 * x + lk + 4 * q, lj = 64 * wj + 16 * y + lc;     // D[lane / 16 + 4 reg][lane % 16]
-        if constexpr (SPLIT) {
-          part[((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * VIEWCOV_TT + li * VIEWCOV_T + lj] = acc[x][y][q];
-        } else {
-          const int gi = i0 + li, gj = j0 + lj;
-          if (gi < p && gj < p && gi <= gj && (keep_diag || view[gi] != view[gj])) viewcov_store(C, ldc, gi, gj, acc[x][y][q] / denom);
-        }
-      }
+  mfma64_each_blocked(acc, keep, [&](int, int, int i, int j, double v) {
+    const int li = 64 * wi + i, lj = 64 * wj + j;
+    if constexpr (SPLIT) {
+      part[((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * VIEWCOV_TT + li * VIEWCOV_T + lj] = v;
+    } else {
+      const int gi = i0 + li, gj = j0 + lj;
+      if (gi < p && gj < p && gi <= gj && (keep_diag || view[gi] != view[gj])) viewcov_store(C, ldc, gi, gj, v / denom);
+    }
+  });
 }
 
 // grid (128 * 128 / 256, ntiles), block 256: element e = 256 blockIdx.x + tid of tile blockIdx.y, summed over g ascending.
