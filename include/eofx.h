@@ -535,6 +535,25 @@ int eofx_pcmul_f64(eofx_ctx *ctx, const void *X, int x_dtype, int64_t rows, int 
  * or m > 64.                                                                                                           */
 int eofx_viewcov_f64(eofx_ctx *ctx, const float *Z, int64_t n, int p, int64_t ld, const double *mean, const int *off, int m,
                      int keep_diag, double *C, int64_t ldc);
+/* ---- gap operators of DINEOF (Beckers & Rixen 2003; csrc/eofx_lrfill.hpp) -----------------------------------------------
+ * DINEOF is EOF analysis of a field with isolated missing values: fit a rank-k SVD, write the rank-k reconstruction into
+ * the gaps, repeat.  The gaps are a bit mask: bit (j & 31) of the 32-bit word bits[i ldb + (j >> 5)] stands for entry
+ * (i, j) of a float32 device field [n x p] with row stride ld >= p; ldb >= ceil(p / 32).
+ * eofx_gapmask_f32: one streaming pass over X sets the bit of every NaN (any payload, either sign) and clears every other
+ * bit of the ceil(p / 32) words of a row, the bits of columns >= p in the last word included; *count (host) = the number of
+ * set bits, exact.  n == 0 or p == 0 is a no-op with *count = 0.                                                       */
+int eofx_gapmask_f32(eofx_ctx *ctx, const float *X, int64_t n, int64_t p, int64_t ld, int32_t *bits, int64_t ldb,
+                     int64_t *count);
+/* eofx_lrfill_f32: F[i, j] <- sum_{m < k} A[i, m] B[j, m] for every entry whose bit is set, in place; A [n x k] (the scores
+ * U diag(s)) and B [p x k] (the components) float32 device panels with row strides lda, ldbm >= k.  The products run on the
+ * matrix cores with float32 operands: every written value is an fmaf chain over m, one rounding per term.  Entries whose bit
+ * is clear, the padding up to ld, and entries named only by bits of columns >= p are never written; a 128 x 128 tile
+ * without a set bit is not touched.  sums [3] float64 (host|device) = (number of written entries, sum (new - old)^2,
+ * sum new^2), from per-workgroup partials added in a fixed order: no atomics, two runs are equal bit for bit.  n == 0 or
+ * p == 0 is a no-op with zero sums.  EOFX_ERR_ARG for k > 256 (LRFILL_KMAX), k < 1 or a stride below its extent;
+ * EOFX_ERR_SHAPE for ld > 2^26 (a buffer resource covers 4 ld + 32 entries).                                              */
+int eofx_lrfill_f32(eofx_ctx *ctx, float *F, int64_t n, int64_t p, int64_t ld, const int32_t *bits, int64_t ldb,
+                    const float *A, int64_t lda, const float *B, int64_t ldbm, int k, double *sums);
 /* Gram matrix of a resident matrix (float32, device): side 0 = sample space G[n_pad x n_pad] = X X^T,
  * side 1 = feature space G[p_pad x p_pad] = X^T X (rows/columns beyond n / p are zero).  Used for
  * (a) the total squared covariance sum(|X^T Y|^2) = <X X^T, Y Y^T> (cross/cpcca.py:991-1000) when X and

@@ -121,6 +121,8 @@ SIGNATURES = {
     "eofx_lagcov_f64": (_int, [_vp, _vp, _i64, _int, _i64, _vp, _int, _vp]),
     "eofx_pcmul_f64": (_int, [_vp, _vp, _int, _i64, _int, _i64, _vp, _int, _vp, _int, _i64]),
     "eofx_viewcov_f64": (_int, [_vp, _vp, _i64, _int, _i64, _vp, _vp, _int, _int, _vp, _i64]),
+    "eofx_gapmask_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _pi64]),
+    "eofx_lrfill_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _vp]),
     "eofx_resample_f32": (_int, [_vp, _vp, _vp, _i64, _int, C.POINTER(_vp), _vp, _pd]),
     "eofx_mat_gram_f32": (_int, [_vp, _vp, _int, _vp]),
     "eofx_mat_cross_gram_f32": (_int, [_vp, _vp, _vp, _int, _vp]),

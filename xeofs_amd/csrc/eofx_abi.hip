@@ -14,6 +14,7 @@
 #include "eofx_lagcov.hpp"
 #include "eofx_pcmul.hpp"
 #include "eofx_viewcov.hpp"
+#include "eofx_lrfill.hpp"
 #ifndef EOFX_AXB_DMA_DEFAULT
 #define EOFX_AXB_DMA_DEFAULT 1
 #endif
@@ -6925,5 +6926,80 @@ extern "C" int eofx_viewcov_f64(eofx_ctx* ctx, const float* Z, int64_t n, int p,
     KCHK();
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));       // (the staged lists are a pageable host buffer; the arena is handed back)
+  return EOFX_OK;
+}
+
+// ---- gap operators of DINEOF (csrc/eofx_lrfill.hpp) ----------------------------------------------------------------------
+extern "C" int eofx_gapmask_f32(eofx_ctx* ctx, const float* X, int64_t n, int64_t p, int64_t ld, int32_t* bits, int64_t ldb,
+                                int64_t* count) {
+  if (!ctx || !count) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  const int64_t nwords = (p + 31) / 32;
+  if (n < 0 || p < 0 || ld < p || ldb < nwords)
+    return set_err(ctx, EOFX_ERR_ARG, "n >= 0, p >= 0, ld >= p and ldb >= ceil(p / 32) are required (n = %lld, p = %lld, ld = %lld, ldb = %lld)",
+                   (long long)n, (long long)p, (long long)ld, (long long)ldb);
+  *count = 0;
+  if (n == 0 || p == 0) return EOFX_OK;            // (an empty field has no buffer to name)
+  if (!X || !bits) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (!is_device_ptr(X) || !is_device_ptr(bits)) return set_err(ctx, EOFX_ERR_ARG, "X and bits must be device buffers");
+  ENTER(ctx);
+  const int64_t units = n * ((p + GAPMASK_COLS - 1) / GAPMASK_COLS);
+  const int G = (int)std::min<int64_t>((units + 3) / 4, LRFILL_WGS);               // a function of the shape alone
+  CHK(arena_reserve(ctx, (size_t)G * 8 + 8 + 2 * 256));
+  ArenaScope scope(ctx);
+  ARENA(unsigned long long, part, G);
+  ARENA(long long, total, 1);
+  hipLaunchKernelGGL(gapmask_kernel, dim3((unsigned)G), dim3(256), 0, ctx->stream, X, n, p, ld, (unsigned*)bits, ldb, part);
+  KCHK();
+  hipLaunchKernelGGL(gapmask_finish_kernel, dim3(1), dim3(256), 0, ctx->stream, (const unsigned long long*)part, G, total);
+  KCHK();
+  long long host = 0;
+  HIPCHK(hipMemcpyAsync(&host, total, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *count = (int64_t)host;
+  return EOFX_OK;
+}
+
+extern "C" int eofx_lrfill_f32(eofx_ctx* ctx, float* F, int64_t n, int64_t p, int64_t ld, const int32_t* bits, int64_t ldb,
+                               const float* A, int64_t lda, const float* B, int64_t ldbm, int k, double* sums) {
+  if (!ctx || !sums) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  const int64_t nwords = (p + 31) / 32;
+  if (k > LRFILL_KMAX) return set_err(ctx, EOFX_ERR_ARG, "the low-rank fill takes k <= %d, got %d", LRFILL_KMAX, k);
+  if (n < 0 || p < 0 || k < 1 || ld < p || ldb < nwords || lda < k || ldbm < k)
+    return set_err(ctx, EOFX_ERR_ARG,
+                   "n >= 0, p >= 0, k >= 1, ld >= p, ldb >= ceil(p / 32), lda >= k and ldbm >= k are required (n = %lld, p = %lld, k = %d, "
+                   "ld = %lld, ldb = %lld, lda = %lld, ldbm = %lld)",
+                   (long long)n, (long long)p, k, (long long)ld, (long long)ldb, (long long)lda, (long long)ldbm);
+  if (ld > LRFILL_LDMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the low-rank fill takes a row stride of at most %lld entries, got %lld", (long long)LRFILL_LDMAX,
+                   (long long)ld);
+  const bool dev_sums = is_device_ptr(sums);
+  if (n == 0 || p == 0) {                          // (an empty field has no buffer to name)
+    if (!dev_sums) {
+      sums[0] = sums[1] = sums[2] = 0.0;
+      return EOFX_OK;
+    }
+    ENTER(ctx);
+    HIPCHK(hipMemsetAsync(sums, 0, 3 * 8, ctx->stream));
+    return EOFX_OK;
+  }
+  if (!F || !bits || !A || !B) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (!is_device_ptr(F) || !is_device_ptr(bits) || !is_device_ptr(A) || !is_device_ptr(B))
+    return set_err(ctx, EOFX_ERR_ARG, "F, bits, A and B must be device buffers");
+  ENTER(ctx);
+  const int64_t ntiles = ((n + LRFILL_T - 1) / LRFILL_T) * ((p + LRFILL_T - 1) / LRFILL_T);
+  const int G = (int)std::min<int64_t>(ntiles, LRFILL_WGS);                         // a function of the shape alone
+  CHK(arena_reserve(ctx, (size_t)G * 3 * 8 + 3 * 8 + 2 * 256));
+  ArenaScope scope(ctx);
+  ARENA(double, part, (size_t)G * 3);
+  ARENA(double, total, 3);
+  hipLaunchKernelGGL(lrfill_kernel, dim3((unsigned)G), dim3(256), 0, ctx->stream, F, n, p, ld, (const unsigned*)bits, ldb, A, lda, B,
+                     ldbm, k, part);
+  KCHK();
+  hipLaunchKernelGGL(lrfill_finish_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)part, G, dev_sums ? sums : total);
+  KCHK();
+  if (!dev_sums) {
+    HIPCHK(hipMemcpyAsync(sums, total, 3 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));     // (sums may be a pageable host buffer; the arena is handed back)
+  }
   return EOFX_OK;
 }

@@ -1449,3 +1449,76 @@ def viewcov(ctx: Context, Z, offsets, center=True, keep_diag=False, out=None):
     raise_for(ctx.lib.eofx_viewcov_f64(ctx.handle, ptr(Z), n, p, Z.stride(0), ptr(mean), ptr(off), m, int(bool(keep_diag)),
                                        ptr(out), out.stride(0)), ctx.handle)
     return out
+
+
+# --------------------------------------------------------------------------- #
+# gap operators of DINEOF (eofx_gapmask_f32 / eofx_lrfill_f32, csrc/eofx_lrfill.hpp)                  #
+# --------------------------------------------------------------------------- #
+LRFILL_KMAX = 256         # modes the fill takes
+LRFILL_LDMAX = 1 << 26    # row stride of the field in entries
+
+
+def gap_words(p: int) -> int:
+    """32-bit words of one row of the gap mask of a field with p columns"""
+    return (int(p) + 31) // 32
+
+
+def _check_bits(bits, n: int, p: int):
+    """a gap mask: an int32 device tensor [n x >= gap_words(p)] with unit column stride"""
+    torch = _torch()
+    if (not hasattr(bits, "data_ptr") or bits.dim() != 2 or bits.dtype != torch.int32 or not bits.is_cuda or bits.shape[0] != n
+            or bits.shape[1] < gap_words(p) or (n and p and (bits.stride(1) != 1 or bits.stride(0) < gap_words(p)))):
+        raise ValueError(f"bits must be an int32 device tensor of shape ({n}, >= {gap_words(p)}) with unit column stride")
+    return bits
+
+
+def _device_field(X, name: str):
+    """a float32 device tensor [n x p] with unit column stride and a row stride of at least p, as it lies"""
+    torch = _torch()
+    if (not hasattr(X, "data_ptr") or not X.is_cuda or X.dim() != 2 or X.dtype != torch.float32
+            or (X.shape[0] and X.shape[1] and (X.stride(1) != 1 or X.stride(0) < X.shape[1]))):
+        raise ValueError(f"{name} must be a float32 device tensor of two dimensions with unit column stride")
+    return X
+
+
+def gap_mask(ctx: Context, X, out=None):
+    """(bits, count) of a float32 device field X [n x p], whose row stride may exceed p: bit j & 31 of the int32 word
+    bits[i, j >> 5] is set iff X[i, j] is NaN, the bits of columns >= p in the last word are 0; count: the set bits, exact.
+    One streaming pass.  `out`: an int32 device tensor [n x >= gap_words(p)] to write (words past gap_words(p) are left)."""
+    torch = _torch()
+    X = _device_field(X, "X")
+    n, p = X.shape
+    bits = torch.empty((n, gap_words(p)), dtype=torch.int32, device=X.device) if out is None else _check_bits(out, n, p)
+    count = C.c_int64()
+    raise_for(ctx.lib.eofx_gapmask_f32(ctx.handle, ptr(X), n, p, X.stride(0) if n and p else p, ptr(bits),
+                                       bits.stride(0) if n and p else gap_words(p), C.byref(count)), ctx.handle)
+    return bits, int(count.value)
+
+
+def lrfill(ctx: Context, F, bits, A, B):
+    """F[i, j] <- sum_m A[i, m] B[j, m] at every entry of the float32 device field F [n x p] whose bit of the gap mask `bits`
+    (`gap_mask`) is set, in place and nowhere else; A [n x k] (the scores U diag(s)) and B [p x k] (the components): float32
+    panels, host arrays or device tensors whose row stride may exceed k, k <= LRFILL_KMAX.  Float32 products on the matrix
+    cores (an fmaf chain per entry).  -> (count, sum (new - old)^2, sum new^2) over the written entries, the sums in float64
+    and equal bit for bit between two runs."""
+    torch = _torch()
+    F = _device_field(F, "F")
+    n, p = F.shape
+    _check_bits(bits, n, p)
+    A = device_panel(ctx, A, "A", (torch.float32,))
+    B = device_panel(ctx, B, "B", (torch.float32,))
+    k = A.shape[1]
+    if A.shape[0] != n or B.shape != (p, k):
+        raise ValueError(f"A must be ({n}, k) and B ({p}, k), got {tuple(A.shape)} and {tuple(B.shape)}")
+    if k > LRFILL_KMAX:
+        raise ValueError(f"the low-rank fill takes k <= {LRFILL_KMAX}, got k = {k}")
+    if k < 1:
+        raise ValueError("the low-rank fill needs k >= 1 modes")
+    if n and p and F.stride(0) > LRFILL_LDMAX:
+        raise ValueError(f"the low-rank fill takes a row stride of at most {LRFILL_LDMAX} entries, got {F.stride(0)}")
+    sums = np.zeros(3, np.float64)
+    live = bool(n and p)
+    raise_for(ctx.lib.eofx_lrfill_f32(ctx.handle, ptr(F), n, p, F.stride(0) if live else p, ptr(bits),
+                                      bits.stride(0) if live else gap_words(p), ptr(A), A.stride(0) if n else k, ptr(B),
+                                      B.stride(0) if p else k, k, ptr(sums)), ctx.handle)
+    return int(sums[0]), float(sums[1]), float(sums[2])

@@ -263,9 +263,10 @@ class Preprocessor:
         coords["mode"] = np.arange(1, k + 1)
         return labelled.pack(blk, ("mode",) + f.sample_dims, coords, name, dict(attrs or {}), f.like)
 
-    def inverse_transform_data(self, X2d, name="reconstructed_data", fields=None, valid_sample=None):
+    def inverse_transform_data(self, X2d, name="reconstructed_data", fields=None, valid_sample=None, per_field=False):
         """(n_valid, p_valid) preprocessed-space matrix -> original dims and units
-        (scaler.py:165-190 un-scaling, sanitizer.py:128-153 NaN re-expansion, stacker unstack)."""
+        (scaler.py:165-190 un-scaling, sanitizer.py:128-153 NaN re-expansion, stacker unstack).
+        per_field: one array per field whatever the flavour of the input (not wrapped back into a list / dataset / array)."""
         fields = fields or self.fields
         vs = self.valid_sample if valid_sample is None else valid_sample
         vf = self.valid_feature
@@ -285,4 +286,104 @@ class Preprocessor:
             src = f.sample_dims + f.feature_dims
             blk = np.transpose(blk, [src.index(d) for d in f.dims])
             outs.append(labelled.pack(blk, f.dims, {d: f.coords[d] for d in f.dims}, name, {}, f.like))
-        return self._wrap(outs)
+        return outs if per_field else self._wrap(outs)
+
+
+class GapPreprocessor(Preprocessor):
+    """The Preprocessor of a field with ISOLATED missing values (DINEOF, xeofs_amd/single/dineof.py): where the Sanitizer
+    raises, the gaps become a bit mask (engine.gap_mask) and zeros of the preprocessed field.  Features and samples that are
+    entirely NaN are dropped as the Sanitizer drops them; the Scaler's statistics (scaler.py:105-108: nanmean, nanstd with
+    ddof = 0 clipped at float32 eps) run over the valid entries of each feature, in float64, as torch reductions over column
+    blocks.  `fit_transform` returns device tensors, not a resident matrix: the model decomposes the field again and again
+    and writes into it in between.  `transform` and the way back are the Preprocessor's."""
+
+    BLOCK_ELEMENTS = 1 << 24      # entries of one column block of the statistics (its float64 temporaries: 128 MiB each)
+
+    def __init__(self, center=True, standardize=False, use_coslat=False, ctx=None):
+        super().__init__(center, standardize, use_coslat, True, ctx=ctx, in_place=True)
+
+    def _blocks(self, n, p):
+        step = max(1, self.BLOCK_ELEMENTS // max(n, 1))
+        return [(a, min(a + step, p)) for a in range(0, p, step)]
+
+    def fit_transform(self, X, sample_dims, weights=None):
+        """-> (F [n' x p'] float32 contiguous device tensor, (X - mean) scale with zeros at the gaps; bits, the gap mask of
+        engine.gap_mask; the number of gaps).  Sets mean_, std_, feature_weights, valid_feature, valid_sample as
+        Preprocessor.fit_transform does, and `sumsq_valid` (sum of F^2, float64).  The compacted input is released on return."""
+        import torch
+
+        self.sample_dims = _as_tuple(sample_dims)
+        ctx = self.ctx or engine.default_context()
+        self.fields = self._fields(X, self.sample_dims)
+        M, self.feature_weights = self._stack(self.fields, weights)
+        T = M if labelled._is_torch(M) else torch.from_numpy(M)
+        n, P = T.shape
+        # Sanitizer: features and samples that are entirely NaN (a sample is, when it is NaN at every feature)
+        col = torch.zeros(P, dtype=torch.int64, device=T.device)
+        row = torch.zeros(n, dtype=torch.int64, device=T.device)
+        for a, b in self._blocks(n, P):
+            nan = torch.isnan(T[:, a:b])
+            col[a:b] = nan.sum(0)
+            row += nan.sum(1)
+        vf, vs = (col < n).cpu().numpy(), (row < P).cpu().numpy()
+        self.valid_feature, self.valid_sample = vf, vs
+        if not vf.any() or not vs.any():
+            raise ValueError("the field holds no valid entry")
+        if not vs.all():
+            T = T[torch.as_tensor(np.flatnonzero(vs), device=T.device)]
+        if not vf.all():
+            T = T[:, torch.as_tensor(np.flatnonzero(vf), device=T.device)]
+        Xc = T.to(f"cuda:{ctx.device}").contiguous()          # the compacted field
+        n, p = Xc.shape
+        bits, gaps = engine.gap_mask(ctx, Xc)
+        w = None if self.feature_weights is None else torch.as_tensor(self.feature_weights[vf], device=Xc.device)
+        mean = torch.zeros(p, dtype=torch.float64, device=Xc.device)
+        std = torch.ones(p, dtype=torch.float64, device=Xc.device)
+        F = torch.empty((n, p), dtype=torch.float32, device=Xc.device)
+        sumsq = torch.zeros((), dtype=torch.float64, device=Xc.device)
+        eps = float(np.finfo(np.float32).eps)
+        for a, b in self._blocks(n, p):
+            blk = Xc[:, a:b].to(torch.float64)
+            ok = ~torch.isnan(blk)
+            cnt = ok.sum(0)
+            mu = torch.where(ok, blk, 0.0).sum(0) / cnt
+            dev = blk - mu
+            if self.standardize:
+                std[a:b] = torch.sqrt(torch.where(ok, dev * dev, 0.0).sum(0) / cnt).clamp_min(eps)
+            if self.center:
+                mean[a:b], blk = mu, dev
+            del dev
+            scale = 1.0 / std[a:b]
+            if w is not None:
+                scale = scale * w[a:b]
+            out = torch.where(ok, blk * scale, 0.0).to(torch.float32)
+            F[:, a:b] = out
+            sumsq += (out.to(torch.float64) ** 2).sum()
+        self.mean_ = _scatter(mean.cpu().numpy(), vf) if self.center else None
+        self.std_ = _scatter(std.cpu().numpy(), vf) if self.standardize else None
+        del Xc, T                         # (F and the mask are all that stays on the device)
+        self.sumsq_valid = float(sumsq)
+        self.total_variance = None        # (the model's: it needs the filled values)
+        return F, bits, gaps
+
+    def filled_data(self, X2d, name="filled"):
+        """the preprocessed-space matrix X2d [n' x p'] in the caller's units and labels, every valid entry of the input
+        taken from the input itself (bit for bit, in its dtype); dropped features and samples stay NaN"""
+        outs = self.inverse_transform_data(X2d, name, per_field=True)
+        res = []
+        for f, o in zip(self.fields, outs):
+            src = labelled.unpack(f.like)[0]
+            src = src.cpu().numpy() if labelled._is_torch(src) else np.asarray(src)
+            vals, dims, coords, _, attrs = labelled.unpack(o)
+            out = np.asarray(vals).astype(src.dtype)
+            keep = ~np.isnan(src)
+            out[keep] = src[keep]
+            res.append(labelled.pack(out, dims, coords, name, attrs, f.like))
+        return self._wrap(res)
+
+
+def _scatter(v, valid):
+    """a per-valid-feature vector as one per stacked feature, NaN at the dropped ones (as the engine reports them)"""
+    out = np.full(valid.size, np.nan)
+    out[valid] = v
+    return out

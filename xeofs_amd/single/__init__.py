@@ -1,3 +1,4 @@
+from .dineof import DINEOF  # noqa: F401
 from .eeof import ExtendedEOF  # noqa: F401
 from .eof import EOF, ComplexEOF, HilbertEOF  # noqa: F401
 from .gwpca import GWPCA  # noqa: F401
