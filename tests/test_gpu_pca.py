@@ -200,13 +200,17 @@ def test_resident_pca_randomized_route(ctx, n, p, n_modes):
     mat.free()
 
 
-@pytest.mark.parametrize("l", [100, 333, 700])
-def test_blocked_device_cholesky_qr(ctx, l):
+@pytest.mark.parametrize("l,host", [(100, False), (333, False), (700, False), (100, True)], ids=["100", "333", "700", "100-host"])
+def test_blocked_device_cholesky_qr(ctx, monkeypatch, l, host):
     """eofx_panel_cholqr_f32 / eofx_panel_rinv_f64 beyond one wavefront's 64 columns: the blocked device factorisation
-    (launch_rinv_blocked) against numpy, with an exactly dependent column (zero column out, as in the 64-column kernel)."""
+    (launch_rinv_blocked) against numpy, with an exactly dependent column (zero column out, as in the 64-column kernel).
+    host: the same through the host route of launch_rinv (EOFX_HOST_RINV, read per call; also taken when the arena is too
+    small for the blocked route)."""
     import torch
     from xeofs_amd import engine
 
+    if host:
+        monkeypatch.setenv("EOFX_HOST_RINV", "1")
     rows = 2560
     rng = np.random.default_rng(l)
     L = (l + 31) // 32 * 32

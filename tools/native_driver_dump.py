@@ -1,0 +1,154 @@
+"""Every array the native SVD drivers return (plus `engine.last_iterations`) on fixed synthetic fields, into one .npz -- to
+compare two builds of libeofx.so bit for bit where the host algebra between the GPU passes is touched
+(`native_driver_dump.py OUT.npz`, with EOFX_LIB naming the library; then `--compare A.npz B.npz`, or
+`--compare3 A1.npz A2.npz B.npz`: what differs between two runs of the SAME build is listed and held to the tolerance of its
+existing test instead (TOLERANCE), everything else must be equal between A1 and B).  The sibling of cross_surface_dump.py one level down: engine.rsvd tall / wide / with a sketch
+beyond 64 columns on either route of the Cholesky inverse / with more modes than rank / on a peaked spectrum over a tall panel
+above 16 MiB, engine.crosscov_rsvd with more modes than rank, engine.rsvd_c64 at the edge cases of
+tests/test_gpu_complex.py with and without the block-Krylov recurrence, engine.rsvd_hilbert_c64 under both rules, and the
+two host eigen-solvers."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+from cross_surface_dump import compare
+
+
+# relative tolerance (of max |array|) at which the existing test of each driver compares it with float64: what an array that
+# is not reproducible from run to run is held to (tests/test_gpu_complex.py, test_gpu_pca.py, test_host_logic.py)
+TOLERANCE = (("rsvd_c64.n_iter_1", 2e-3), ("rsvd_c64.n_iter_2", 1e-4), ("host_", 1e-12), ("", 1e-5))
+
+
+def compare3(a1, a2, b):
+    A1, A2, B = np.load(a1), np.load(a2), np.load(b)
+
+    def differ(P, Q):
+        return sorted(set(P.files) ^ set(Q.files)) + [k for k in sorted(set(P.files) & set(Q.files))
+                                                      if P[k].dtype != Q[k].dtype or not np.array_equal(P[k], Q[k], equal_nan=P[k].dtype.kind in "fc")]
+    unstable = differ(A1, A2)
+    bad = [k for k in differ(A1, B) if k not in unstable]
+    print(f"native_driver_dump: {len(A1.files)} arrays; {len(unstable)} differ between two runs of the same build"
+          + (": " + ", ".join(unstable) if unstable else "") + f"; of the other {len(A1.files) - len(unstable)}, {len(bad)} differ"
+          + (": " + ", ".join(bad) if bad else ""))
+    for k in unstable:          # not reproducible: held to the tolerance of its test instead
+        tol = next(t for prefix, t in TOLERANCE if k.startswith(prefix))
+        ok = k in B.files and B[k].shape == A1[k].shape
+        if ok:
+            scale = max(float(np.abs(A1[k]).max()), 1e-300)
+            d12, d1b = np.abs(A1[k] - A2[k]).max() / scale, np.abs(A1[k] - B[k]).max() / scale
+            ok = bool(d1b <= tol)
+            print(f"  {k}: max |A1 - A2| = {d12:.3e}, max |A1 - B| = {d1b:.3e} of max |A1|, tolerance {tol:.0e}: {'ok' if ok else 'DIFFERS'}")
+        if not ok:
+            bad.append(k)
+    return 1 if bad else 0
+
+
+def low_rank(rng, n, p, rank, decay, noise, cplx=False):
+    def g(*shape):
+        return rng.standard_normal(shape) + 1j * rng.standard_normal(shape) if cplx else rng.standard_normal(shape)
+    X = (g(n, rank) * (6.0 * decay ** np.arange(rank))) @ g(rank, p) / np.sqrt(p)
+    if noise:
+        X = X + noise * g(n, p) / np.sqrt(p)
+    return X
+
+
+def main(out_path):
+    from xeofs_amd import _lib, engine
+
+    ctx = engine.default_context()
+    out = {}
+
+    def record(key, obj, iters=False):
+        if isinstance(obj, dict):
+            obj = [obj[name] for name in sorted(obj) if isinstance(obj[name], (np.ndarray, float, int, np.generic))]
+        for i, o in enumerate(obj):
+            out[f"{key}.{i}"] = np.asarray(o)
+        if iters:
+            out[f"{key}.iterations"] = np.asarray(engine.last_iterations(ctx))
+
+    def with_env(name, value, fn):
+        old = os.environ.pop(name, None)
+        if value is not None:
+            os.environ[name] = value
+        try:
+            return fn()
+        finally:
+            os.environ.pop(name, None)
+            if old is not None:
+                os.environ[name] = old
+
+    rng = np.random.default_rng(2024)
+    # --- engine.rsvd
+    for tag, n, p, k, kw, field in (
+            ("tall", 700, 60, 5, {}, dict(rank=8, decay=0.7, noise=0.3)),
+            ("wide", 60, 700, 5, {}, dict(rank=8, decay=0.7, noise=0.3)),
+            ("l100", 300, 1500, 90, {}, dict(rank=40, decay=0.9, noise=0.3)),
+            ("null_modes", 60, 700, 8, {}, dict(rank=4, decay=0.7, noise=0.0)),
+            ("peaked", 200, 140000, 5, {}, dict(rank=6, decay=0.2, noise=0.02))):
+        X = low_rank(rng, n, p, **field)
+        mat = engine.from_dense(ctx, (X - X.mean(axis=0)).astype(np.float32))
+        for host in ((None, "1") if tag == "l100" else (None,)):
+            record(f"rsvd.{tag}" + (".host_rinv" if host else ""),
+                   with_env("EOFX_HOST_RINV", host, lambda: engine.rsvd(ctx, mat, k, random_state=5, **kw)))
+        mat.free()
+    # --- engine.crosscov_rsvd, more modes than rank
+    T = rng.standard_normal((80, 3))
+    xm = engine.from_dense(ctx, (T @ rng.standard_normal((3, 50))).astype(np.float32))
+    ym = engine.from_dense(ctx, (T @ rng.standard_normal((3, 40))).astype(np.float32))
+    record("crosscov_rsvd.null_modes", engine.crosscov_rsvd(ctx, xm, ym, 6, random_state=5))
+    xm.free()
+    ym.free()
+    # --- engine.rsvd_c64: the cases of tests/test_gpu_complex.py::test_complex_rsvd_krylov_edge_cases
+    for case in ("wide_sketch", "full_width", "rank_deficient", "n_iter_1", "n_iter_2", "converge", "feature_side"):
+        crng = np.random.default_rng(11)
+        n, p, k, n_iter, noise = 300, 900, 6, "auto", 0.02
+        if case == "wide_sketch":
+            n, p, k = 60, 400, 28
+        elif case == "full_width":
+            n, p, k = 24, 300, 14
+        elif case == "n_iter_1":
+            n_iter = 1
+        elif case == "n_iter_2":
+            n_iter = 2
+        elif case == "converge":
+            n_iter, noise = "converge", 0.3
+        elif case == "feature_side":
+            n, p = 900, 260
+        r = 5 if case == "rank_deficient" else 9
+        Z = low_rank(crng, n, p, r, 0.6, 0.0 if case == "rank_deficient" else noise, cplx=True).astype(np.complex64)
+        A = engine.from_dense(ctx, np.ascontiguousarray(Z.real))
+        B = engine.from_dense(ctx, np.ascontiguousarray(Z.imag))
+        for krylov in (None, "0"):
+            record(f"rsvd_c64.{case}.krylov{int(krylov is None)}",
+                   with_env("EOFX_C64_KRYLOV", krylov, lambda: engine.rsvd_c64(ctx, A, B, k, random_state=2, n_iter=n_iter)), iters=True)
+        A.free()
+        B.free()
+    # --- engine.rsvd_hilbert_c64
+    X = low_rank(rng, 300, 900, 9, 0.6, 0.3)
+    mat = engine.from_dense(ctx, (X - X.mean(axis=0)).astype(np.float32))
+    for rule in ("auto", "converge"):
+        record(f"rsvd_hilbert_c64.{rule}", engine.rsvd_hilbert_c64(ctx, mat, 6, random_state=2, n_iter=rule), iters=True)
+    mat.free()
+    # --- the host eigen-solvers
+    for n in (1, 60, 120):
+        S = rng.standard_normal((n, n))
+        record(f"host_eigh.{n}", engine.host_eigh(S + S.T))
+    m, nev = 240, 30
+    Hm = rng.standard_normal((m, m)) + 1j * rng.standard_normal((m, m))
+    Hm = Hm @ Hm.conj().T
+    Hr, Hi = np.ascontiguousarray(Hm.real), np.ascontiguousarray(Hm.imag)
+    w, Xr, Xi = np.zeros(nev), np.zeros((m, nev)), np.zeros((m, nev))
+    rc = _lib.load().eofx_host_zheigh_top_f64(Hr.ctypes.data, Hi.ctypes.data, m, nev, w.ctypes.data, Xr.ctypes.data, Xi.ctypes.data)
+    assert rc == 0
+    record(f"host_zheigh_top.{m}.{nev}", (w, Xr, Xi))
+    np.savez(out_path, **out)
+    print(f"native_driver_dump: wrote {len(out)} arrays to {out_path}")
+    return 0
+
+
+if __name__ == "__main__":
+    if sys.argv[1] == "--compare":
+        sys.exit(compare(*sys.argv[2:4]))
+    sys.exit(compare3(*sys.argv[2:5]) if sys.argv[1] == "--compare3" else main(sys.argv[1]))

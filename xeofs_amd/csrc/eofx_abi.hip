@@ -8,6 +8,7 @@
 #include "eofx_gram.hpp"
 #include "eofx_axb_dma.hpp"
 #include "eofx_hosteig.hpp"
+#include "eofx_hostla.hpp"
 #include "eofx_lag.hpp"
 #include "eofx_gw.hpp"
 #include "eofx_spca.hpp"
@@ -523,141 +524,13 @@ static int pinned_scratch(eofx_ctx* ctx, double** out) {
 // ------------------------------------------------------------------------------------
 // small host linear algebra
 // ------------------------------------------------------------------------------------
-// Symmetric eigen-decomposition: Householder tridiagonalisation followed by the implicit-shift
-// QL iteration, eigenvectors accumulated (the classic tred2/tql2 scheme), float64.
-// sqrt(a^2 + b^2): the plain form unless it over- or underflows (std::hypot's care costs 20-40 ns a call, and the QL iteration
-// makes two per rotation)
-static inline double hypot_fast(double a, double b) {
-  const double q = a * a + b * b;
-  if (q > 1e-280 && q < 1e280) return std::sqrt(q);
-  return std::hypot(a, b);
-}
 extern "C" int eofx_host_zheigh_top_f64(const double* Hr, const double* Hi, int m, int nev, double* w, double* Xr, double* Xi) {
   if (!Hr || !Hi || !w || !Xr || !Xi || m <= 0 || nev <= 0 || nev > m) return EOFX_ERR_ARG;
   return hosteig::zheigh_top(Hr, Hi, m, nev, w, Xr, Xi) == 0 ? EOFX_OK : EOFX_ERR_LINALG;
 }
 extern "C" int eofx_host_eigh_f64(const double* Ain, int n, double* w, double* Vec) {
   if (!Ain || !w || !Vec || n <= 0) return EOFX_ERR_ARG;
-  std::vector<double> z((size_t)n * n), d(n), e(n);
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j < n; ++j) z[(size_t)i * n + j] = 0.5 * (Ain[(size_t)i * n + j] + Ain[(size_t)j * n + i]);
-#define Z(i, j) z[(size_t)(i) * n + (j)]
-  // --- Householder reduction to tridiagonal form, accumulating the transformation in z
-  for (int i = n - 1; i >= 1; --i) {
-    const int l = i - 1;
-    double h = 0.0, scale = 0.0;
-    if (l > 0) {
-      for (int k = 0; k <= l; ++k) scale += std::fabs(Z(i, k));
-      if (scale == 0.0) {
-        e[i] = Z(i, l);
-      } else {
-        for (int k = 0; k <= l; ++k) {
-          Z(i, k) /= scale;
-          h += Z(i, k) * Z(i, k);
-        }
-        double f = Z(i, l);
-        double g = (f >= 0.0) ? -std::sqrt(h) : std::sqrt(h);
-        e[i] = scale * g;
-        h -= f * g;
-        Z(i, l) = f - g;
-        f = 0.0;
-        for (int j = 0; j <= l; ++j) {
-          Z(j, i) = Z(i, j) / h;
-          g = 0.0;
-          for (int k = 0; k <= j; ++k) g += Z(j, k) * Z(i, k);
-          for (int k = j + 1; k <= l; ++k) g += Z(k, j) * Z(i, k);
-          e[j] = g / h;
-          f += e[j] * Z(i, j);
-        }
-        const double hh = f / (h + h);
-        for (int j = 0; j <= l; ++j) {
-          f = Z(i, j);
-          e[j] = g = e[j] - hh * f;
-          for (int k = 0; k <= j; ++k) Z(j, k) -= (f * e[k] + g * Z(i, k));
-        }
-      }
-    } else {
-      e[i] = Z(i, l);
-    }
-    d[i] = h;
-  }
-  d[0] = 0.0;
-  e[0] = 0.0;
-  for (int i = 0; i < n; ++i) {
-    const int l = i - 1;
-    if (d[i] != 0.0) {
-      for (int j = 0; j <= l; ++j) {
-        double g = 0.0;
-        for (int k = 0; k <= l; ++k) g += Z(i, k) * Z(k, j);
-        for (int k = 0; k <= l; ++k) Z(k, j) -= g * Z(k, i);
-      }
-    }
-    d[i] = Z(i, i);
-    Z(i, i) = 1.0;
-    for (int j = 0; j <= l; ++j) Z(j, i) = Z(i, j) = 0.0;
-  }
-  // --- implicit QL on the tridiagonal (d, e).  The rotations touch two COLUMNS of the accumulated transformation at a time: they
-  // run on its transpose, where those are two contiguous rows (vectorised; 247 -> ~150 us for the 60 x 60 problem a fit waits for)
-  std::vector<double> zt((size_t)n * n);
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j < n; ++j) zt[(size_t)j * n + i] = z[(size_t)i * n + j];
-  for (int i = 1; i < n; ++i) e[i - 1] = e[i];
-  e[n - 1] = 0.0;
-  for (int l = 0; l < n; ++l) {
-    int iter = 0, m;
-    do {
-      for (m = l; m < n - 1; ++m) {
-        const double dd = std::fabs(d[m]) + std::fabs(d[m + 1]);
-        if (std::fabs(e[m]) <= 2.220446049250313e-16 * dd) break;
-      }
-      if (m != l) {
-        if (iter++ == 200) return EOFX_ERR_LINALG;
-        double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
-        double r = hypot_fast(g, 1.0);
-        g = d[m] - d[l] + e[l] / (g + (g >= 0.0 ? std::fabs(r) : -std::fabs(r)));
-        double s = 1.0, c = 1.0, p = 0.0;
-        int i;
-        for (i = m - 1; i >= l; --i) {
-          double f = s * e[i];
-          const double b = c * e[i];
-          e[i + 1] = (r = hypot_fast(f, g));
-          if (r == 0.0) {
-            d[i + 1] -= p;
-            e[m] = 0.0;
-            break;
-          }
-          s = f / r;
-          c = g / r;
-          g = d[i + 1] - p;
-          r = (d[i] - g) * s + 2.0 * c * b;
-          d[i + 1] = g + (p = s * r);
-          g = c * r - b;
-          {
-            double* __restrict__ ri = zt.data() + (size_t)i * n;
-            double* __restrict__ rj = zt.data() + (size_t)(i + 1) * n;
-            for (int k = 0; k < n; ++k) {
-              const double fk = rj[k], zk = ri[k];
-              rj[k] = s * zk + c * fk;
-              ri[k] = c * zk - s * fk;
-            }
-          }
-        }
-        if (r == 0.0 && i >= l) continue;
-        d[l] -= p;
-        e[l] = g;
-        e[m] = 0.0;
-      }
-    } while (m != l);
-  }
-#undef Z
-  std::vector<int> idx(n);
-  for (int i = 0; i < n; ++i) idx[i] = i;
-  std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return d[a] > d[b]; });
-  for (int j = 0; j < n; ++j) {
-    w[j] = d[idx[j]];
-    for (int i = 0; i < n; ++i) Vec[(size_t)i * n + j] = zt[(size_t)idx[j] * n + i];
-  }
-  return EOFX_OK;
+  return hosteig::eigh(Ain, n, w, Vec) == 0 ? EOFX_OK : EOFX_ERR_LINALG;
 }
 
 // ------------------------------------------------------------------------------------
@@ -1122,44 +995,6 @@ static int launch_xgram(eofx_ctx* ctx, const float* Pa, int64_t lda, int La, con
   hipLaunchKernelGGL(f64_reduce_kernel, dim3((int)((count + 63) / 64)), dim3(256), 0, ctx->stream, part, C, count, nbx);
   KCHK();
   return EOFX_OK;
-}
-
-// host fallback of chol_rinv for sketches wider than one wavefront's 64 columns: same algorithm,
-// same dependent-column rule, float64.  G, Rinv are L x L row-major; only the l x l block is used.
-static void host_chol_rinv(const double* G, int L, int l, double* Rinv, double tol) {
-  std::vector<double> A((size_t)l * l, 0.0), X((size_t)l * l, 0.0), d0(l);
-  std::vector<char> dead(l, 0);
-  for (int r = 0; r < l; ++r) {
-    d0[r] = G[(size_t)r * L + r];
-    for (int c = r; c < l; ++c) A[(size_t)r * l + c] = G[(size_t)r * L + c];
-  }
-  for (int j = 0; j < l; ++j) {
-    const double d = A[(size_t)j * l + j];
-    const bool dj = !(d > tol * d0[j]) || !(d0[j] > 0.0);
-    dead[j] = dj;
-    const double rjj = dj ? 1.0 : std::sqrt(d);
-    const double piv = dj ? 0.0 : 1.0 / rjj;
-    A[(size_t)j * l + j] = rjj;
-    double* rowj = &A[(size_t)j * l];
-    for (int c = j + 1; c < l; ++c) rowj[c] *= piv;
-    for (int r = j + 1; r < l; ++r) {
-      const double f = rowj[r];
-      if (f == 0.0) continue;
-      double* rowr = &A[(size_t)r * l];
-      for (int c = r; c < l; ++c) rowr[c] -= f * rowj[c];
-    }
-  }
-  for (int c = 0; c < l; ++c) {
-    if (dead[c]) continue;
-    X[(size_t)c * l + c] = 1.0 / A[(size_t)c * l + c];
-    for (int r = c - 1; r >= 0; --r) {
-      double sum = 0.0;
-      for (int t = r + 1; t <= c; ++t) sum += A[(size_t)r * l + t] * X[(size_t)t * l + c];
-      X[(size_t)r * l + c] = -sum / A[(size_t)r * l + r];
-    }
-  }
-  for (int r = 0; r < L; ++r)
-    for (int c = 0; c < L; ++c) Rinv[(size_t)r * L + c] = (r < l && c < l) ? X[(size_t)r * l + c] : 0.0;
 }
 
 // out = P R^-1 with G = R^T R (leading l x l block)
@@ -2159,7 +1994,6 @@ static int rsvd_auto_iters(int k, int64_t n, int64_t p) {
 
 // All panels are carved from the arena by the caller-visible drivers (reserve first).
 constexpr size_t EOFX_ORTH_TALL_BYTES = (size_t)16 << 20;
-constexpr double EOFX_PEAKED_RATIO = 30.0;
 // Is the tall panel re-normalised between the two products of a power iteration?  scikit-learn normalises after EVERY
 // product; leaving that step out is exact in exact arithmetic, but one iteration then squares sigma_1 / sigma_l inside
 // the float32 panel and the Cholesky-QR that follows squares it again: modes more than ~500x below the leading one
@@ -2168,7 +2002,7 @@ constexpr double EOFX_PEAKED_RATIO = 30.0;
 //   * always: small tall panels (<= 16 MiB: microseconds), the float64 mode, and the FIRST iteration of every fit;
 //   * afterwards only where it matters: after the first iteration the small-side Gram matrix W^T W is a Rayleigh
 //     quotient of X X^T on an orthonormal basis; if the square root of the ratio of its extreme eigenvalues
-//     (~ sigma_1 / sigma_l) exceeds EOFX_PEAKED_RATIO the remaining iterations keep the step.
+//     (~ sigma_1 / sigma_l) exceeds hostla::PEAKED_RATIO the remaining iterations keep the step.
 // ONE rule (eofx_orth_tall_rule / eofx_peaked_spectrum) for the C++ drivers and the panel-level (sharded) driver.
 static bool orth_tall_rule(int64_t tall_pad, int L, int prec_power) {
   if (std::getenv("EOFX_FORCE_ORTH_TALL")) return true;    // experiments (tools/cond_study.py)
@@ -2186,10 +2020,8 @@ extern "C" int eofx_peaked_spectrum(const double* G, int ld, int l) {
   for (double v : A)
     if (!std::isfinite(v)) return 0;
   if (eofx_host_eigh_f64(A.data(), l, w.data(), V.data()) != EOFX_OK) return 1;
-  const double hi = w[0], lo = w[l - 1];                 // descending
-  if (!(hi > 0.0)) return 0;
-  if (!(lo > 0.0)) return 1;
-  return std::sqrt(hi / lo) > EOFX_PEAKED_RATIO ? 1 : 0;
+  if (!(w[0] > 0.0)) return 0;                 // (descending; no positive eigenvalue: the complex driver keeps the step there)
+  return hostla::peaked_spectrum(w.data(), l) ? 1 : 0;
 }
 
 // R^-1 (device, L x L float64, leading l x l block) of the Cholesky factor of G: the device kernel up to one
@@ -2284,7 +2116,7 @@ static int launch_rinv(eofx_ctx* ctx, const double* G, int L, int l, double* Rin
     std::vector<double> hG((size_t)L * L), hR((size_t)L * L);
     HIPCHK(hipMemcpyAsync(hG.data(), G, sizeof(double) * L * L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    host_chol_rinv(hG.data(), L, l, hR.data(), 1e-13);
+    hostla::chol_rinv_padded(hG.data(), L, l, hR.data(), 1e-13);      // (same algorithm and dependent-column rule as the kernels)
     HIPCHK(hipMemcpyAsync(Rinv, hR.data(), sizeof(double) * L * L, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
@@ -2515,7 +2347,6 @@ static int fix_null_columns(eofx_ctx* ctx, float* P, int64_t rows, int64_t rows_
   ARENA(double, Mx, (size_t)Lo * Lo);
   ARENA(float, tmp, (size_t)rows_pad * Lo);
   ARENA(int, dflag, Lo);
-  const int m = k - first;
   std::vector<double> hG((size_t)Lo * Lo), hM((size_t)Lo * Lo);
   std::vector<int> flag(Lo, 0);
   const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, 4096));
@@ -2536,70 +2367,12 @@ static int fix_null_columns(eofx_ctx* ctx, float* P, int64_t rows, int64_t rows_
   int rounds_done = 0;
   for (int attempt = 0; attempt < 8 && rounds_done < 2; ++attempt) {
     CHK(gram());
-    // columns that cannot be kept: zero (the dead columns of a Cholesky-QR) or not finite
-    bool bad = false;
-    std::fill(flag.begin(), flag.end(), 0);
-    for (int j = first; j < k; ++j) {
-      const double d = hG[(size_t)j * Lo + j];
-      if (!std::isfinite(d) || !(d > 1e-30)) flag[j] = 1, bad = true;
-      for (int i = 0; i < k && !flag[j]; ++i)
-        if (!std::isfinite(hG[(size_t)i * Lo + j])) flag[j] = 1, bad = true;
-    }
-    if (bad && rounds_done == 0) {
+    const int verdict = hostla::null_column_transform(hG.data(), Lo, first, k, rounds_done == 0, hM.data(), flag.data());
+    if (verdict != hostla::NULLCOL_OK) {      // the flagged columns (zero, not finite, inside the span before them) are replaced
+      if (rounds_done > 0) break;             // (cannot happen after a successful round; leave what the round produced)
       CHK(refill());
       continue;
     }
-    // S = C_NN - C_GN^T C_GN (the columns before `first` are orthonormal), its Cholesky factor R, Mx = [I, -C_GN R^-1; 0, R^-1]
-    std::vector<double> S((size_t)m * m), Ri((size_t)m * m, 0.0);
-    for (int a = 0; a < m; ++a)
-      for (int b = 0; b < m; ++b) {
-        double v = hG[(size_t)(first + a) * Lo + first + b];
-        for (int g = 0; g < first; ++g) v -= hG[(size_t)g * Lo + first + a] * hG[(size_t)g * Lo + first + b];
-        S[(size_t)a * m + b] = v;
-      }
-    // right-looking Cholesky with a pivot floor: a column left with < 1e-6 of its squared length lay inside the span before it
-    bool dependent = false;
-    std::vector<double> A(S);
-    for (int j = 0; j < m; ++j) {
-      const double d = A[(size_t)j * m + j];
-      if (!(d > 1e-6 * std::max(S[(size_t)j * m + j], 1e-300)) || !std::isfinite(d)) {
-        flag[first + j] = 1;          // (all such columns are found in one sweep: this one drops out of the factorisation)
-        dependent = true;
-        for (int c = j; c < m; ++c) A[(size_t)j * m + c] = 0.0;
-        A[(size_t)j * m + j] = 1.0;
-        continue;
-      }
-      const double rjj = std::sqrt(d);
-      A[(size_t)j * m + j] = rjj;
-      for (int c = j + 1; c < m; ++c) A[(size_t)j * m + c] /= rjj;
-      for (int r = j + 1; r < m; ++r) {
-        const double f = A[(size_t)j * m + r];
-        for (int c = r; c < m; ++c) A[(size_t)r * m + c] -= f * A[(size_t)j * m + c];
-      }
-    }
-    if (dependent) {
-      if (rounds_done > 0) break;     // (cannot happen after a successful round; leave what the round produced)
-      CHK(refill());
-      continue;
-    }
-    for (int c = 0; c < m; ++c) {       // R^-1 (upper triangular)
-      Ri[(size_t)c * m + c] = 1.0 / A[(size_t)c * m + c];
-      for (int r = c - 1; r >= 0; --r) {
-        double sum = 0.0;
-        for (int t = r + 1; t <= c; ++t) sum += A[(size_t)r * m + t] * Ri[(size_t)t * m + c];
-        Ri[(size_t)r * m + c] = -sum / A[(size_t)r * m + r];
-      }
-    }
-    std::fill(hM.begin(), hM.end(), 0.0);
-    for (int i = 0; i < first; ++i) hM[(size_t)i * Lo + i] = 1.0;
-    for (int a = 0; a < m; ++a)
-      for (int b = a; b < m; ++b) hM[(size_t)(first + a) * Lo + first + b] = Ri[(size_t)a * m + b];
-    for (int g = 0; g < first; ++g)
-      for (int b = 0; b < m; ++b) {
-        double v = 0.0;
-        for (int a = 0; a <= b; ++a) v += hG[(size_t)g * Lo + first + a] * Ri[(size_t)a * m + b];
-        hM[(size_t)g * Lo + first + b] = -v;
-      }
     HIPCHK(hipMemcpyAsync(Mx, hM.data(), sizeof(double) * Lo * Lo, hipMemcpyHostToDevice, ctx->stream));
     CHK(launch_matmul(ctx, P, rows_pad, Lo, Mx, Lo, tmp));
     // only the re-orthonormalised columns go back: the columns before `first` keep their bits
@@ -4561,124 +4334,9 @@ static int panel_colargminmax(eofx_ctx* ctx, const float* P, int64_t rows, int L
 // Replaces scipy.sparse.linalg.svds(lobpcg) at xeofs/linalg/decomposer.py:149-160.  A complex panel of h columns is
 // a real panel [Re | Im] of 2 h columns; a pass over the data is ONE launch of the streaming kernel in its two-matrix
 // form (Z^H W = A^T [Wr|Wi] + B^T [Wi|-Wr],  Z Y = A [Yr|Yi] + B [-Yi|Yr]); orthonormalisation is a complex
-// Cholesky-QR on the Hermitian Gram matrix assembled from one real float64 Gram of the panel (host, l <= 64).
+// Cholesky-QR on the Hermitian Gram matrix assembled from one real float64 Gram of the panel (host, l <= 64: eofx_hostla.hpp).
 // ------------------------------------------------------------------------------------
-namespace {
-typedef std::complex<double> zdouble;
-
-// Hermitian l x l Gram P^H P from the real LP x LP Gram of [Pr | Pi] (h = LP / 2)
-static void hermitian_from_real(const std::vector<double>& G, int LP, int l, std::vector<zdouble>& H) {
-  const int h = LP / 2;
-  H.assign((size_t)l * l, zdouble(0.0, 0.0));
-  for (int i = 0; i < l; ++i)
-    for (int j = 0; j < l; ++j) {
-      const double rr = G[(size_t)i * LP + j], ii = G[(size_t)(h + i) * LP + h + j];
-      const double ri = G[(size_t)i * LP + h + j], ir = G[(size_t)(h + i) * LP + j];
-      H[(size_t)i * l + j] = zdouble(rr + ii, ri - ir);
-    }
-  for (int i = 0; i < l; ++i)
-    for (int j = i; j < l; ++j) {
-      const zdouble v = 0.5 * (H[(size_t)i * l + j] + std::conj(H[(size_t)j * l + i]));
-      H[(size_t)i * l + j] = v;
-      H[(size_t)j * l + i] = std::conj(v);
-    }
-}
-// T (l x l upper triangular) with (P T)^H (P T) = I for H = P^H P; dependent columns -> zero columns (same rule as the
-// real driver's chol_rinv: pivot below tol * original diagonal)
-static void host_zchol_rinv(const std::vector<zdouble>& Hin, int l, std::vector<zdouble>& T, double tol,
-                            std::vector<zdouble>* Rout = nullptr, int* n_live = nullptr, const double* dref = nullptr, double tolref = 0.0) {
-  std::vector<zdouble> A(Hin);
-  std::vector<double> d0(l);
-  std::vector<char> dead(l, 0);
-  for (int j = 0; j < l; ++j) d0[j] = Hin[(size_t)j * l + j].real();
-  for (int j = 0; j < l; ++j) {        // H = R^H R, R upper triangular, stored in the upper part of A
-    const double d = A[(size_t)j * l + j].real();
-    const bool dj = !(d > tol * d0[j]) || !(d0[j] > 0.0) || (dref && !(d > tolref * dref[j]));   // (dref: see eofx_rsvd_c64)
-    dead[j] = dj;
-    const double rjj = dj ? 1.0 : std::sqrt(d);
-    const double piv = dj ? 0.0 : 1.0 / rjj;
-    A[(size_t)j * l + j] = rjj;
-    for (int c = j + 1; c < l; ++c) A[(size_t)j * l + c] *= piv;
-    for (int r = j + 1; r < l; ++r) {
-      const zdouble f = std::conj(A[(size_t)j * l + r]);
-      if (f == zdouble(0.0, 0.0)) continue;
-      for (int c = r; c < l; ++c) A[(size_t)r * l + c] -= f * A[(size_t)j * l + c];
-    }
-  }
-  if (Rout) {                          // P = Q R (a dependent column keeps its coefficients on the earlier columns of Q)
-    Rout->assign((size_t)l * l, zdouble(0.0, 0.0));
-    for (int r = 0; r < l; ++r)
-      for (int c = r; c < l; ++c) (*Rout)[(size_t)r * l + c] = (r == c && dead[r]) ? zdouble(0.0, 0.0) : A[(size_t)r * l + c];
-  }
-  if (n_live) {
-    *n_live = 0;
-    for (int j = 0; j < l; ++j) *n_live += dead[j] ? 0 : 1;
-  }
-  T.assign((size_t)l * l, zdouble(0.0, 0.0));
-  for (int c = 0; c < l; ++c) {        // T = R^-1 column by column
-    if (dead[c]) continue;
-    T[(size_t)c * l + c] = 1.0 / A[(size_t)c * l + c];
-    for (int r = c - 1; r >= 0; --r) {
-      zdouble sum(0.0, 0.0);
-      for (int t = r + 1; t <= c; ++t) sum += A[(size_t)r * l + t] * T[(size_t)t * l + c];
-      T[(size_t)r * l + c] = -sum / A[(size_t)r * l + r];
-    }
-  }
-}
-// Hermitian eigen-decomposition through the real symmetric embedding [[Hr, -Hi], [Hi, Hr]] (every eigenvalue twice,
-// eigenvectors (x; y) <-> x + i y) and the real tridiagonal QL solver; complex Gram-Schmidt inside clusters removes the
-// duplicates.  -> w descending, V columns (row-major l x l).
-static int host_heigh(const std::vector<zdouble>& H, int l, std::vector<double>& w, std::vector<zdouble>& V) {
-  const int m = 2 * l;
-  std::vector<double> E((size_t)m * m), ew(m), ev((size_t)m * m);
-  for (int i = 0; i < l; ++i)
-    for (int j = 0; j < l; ++j) {
-      const zdouble v = H[(size_t)i * l + j];
-      E[(size_t)i * m + j] = v.real();
-      E[(size_t)(l + i) * m + l + j] = v.real();
-      E[(size_t)i * m + l + j] = -v.imag();
-      E[(size_t)(l + i) * m + j] = v.imag();
-    }
-  const int rc = eofx_host_eigh_f64(E.data(), m, ew.data(), ev.data());   // descending eigenvalues, columns
-  if (rc != EOFX_OK) return rc;
-  w.assign(l, 0.0);
-  V.assign((size_t)l * l, zdouble(0.0, 0.0));
-  int got = 0;
-  const double scale = std::max(std::fabs(ew[0]), std::fabs(ew[m - 1]));
-  for (int c = 0; c < m && got < l; ++c) {
-    std::vector<zdouble> v(l);
-    for (int i = 0; i < l; ++i) v[i] = zdouble(ev[(size_t)i * m + c], ev[(size_t)(l + i) * m + c]);
-    for (int pass = 0; pass < 2; ++pass)
-      for (int g = 0; g < got; ++g) {
-        if (std::fabs(w[g] - ew[c]) > 1e-6 * scale + 1e-300) continue;    // other clusters are orthogonal already
-        zdouble dot(0.0, 0.0);
-        for (int i = 0; i < l; ++i) dot += std::conj(V[(size_t)i * l + g]) * v[i];
-        for (int i = 0; i < l; ++i) v[i] -= dot * V[(size_t)i * l + g];
-      }
-    double nrm = 0.0;
-    for (int i = 0; i < l; ++i) nrm += std::norm(v[i]);
-    nrm = std::sqrt(nrm);
-    if (nrm < 0.5) continue;             // the partner (i v) of an accepted vector
-    for (int i = 0; i < l; ++i) V[(size_t)i * l + got] = v[i] / nrm;
-    w[got] = ew[c];
-    ++got;
-  }
-  return got == l ? EOFX_OK : EOFX_ERR_LINALG;
-}
-// real LP x Lo matrix E with [Pr|Pi] E = [Re(P M) | Im(P M)] for complex M (l x m), h = LP/2, ho = Lo/2
-static void embed_right(const std::vector<zdouble>& M, int l, int mcols, int LP, int Lo, std::vector<double>& E) {
-  const int h = LP / 2, ho = Lo / 2;
-  E.assign((size_t)LP * Lo, 0.0);
-  for (int i = 0; i < l; ++i)
-    for (int j = 0; j < mcols; ++j) {
-      const zdouble v = M[(size_t)i * mcols + j];
-      E[(size_t)i * Lo + j] = v.real();
-      E[(size_t)(h + i) * Lo + j] = -v.imag();
-      E[(size_t)i * Lo + ho + j] = v.imag();
-      E[(size_t)(h + i) * Lo + ho + j] = v.real();
-    }
-}
-}  // namespace
+using hostla::zdouble;
 
 // The Hilbert stage as ONE linear map along the samples: for a series y [n] (padding "exp": linear fit, exponential pads,
 // transform of the 3n-long series, middle third -- reference utils/hilbert_transform.py:47-92; no padding: the circular
@@ -5061,14 +4719,12 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
     if (shd && tall_side) CHK(comm_allreduce(ctx, G, (int64_t)LP * LP, 1, 0));     // rows sharded over the ranks
     HIPCHK(hipMemcpyAsync(hG.data(), G, sizeof(double) * LP * LP, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    hermitian_from_real(hG, LP, l, H);
-    for (const zdouble& v : H)
-      if (!std::isfinite(v.real()) || !std::isfinite(v.imag()))
-        return set_err(ctx, EOFX_ERR_LINALG, "SVD failed. This may be due to isolated NaN values in the data.");
+    if (!hostla::hermitian_from_real(hG.data(), LP, l, H))
+      return set_err(ctx, EOFX_ERR_LINALG, "SVD failed. This may be due to isolated NaN values in the data.");
     return EOFX_OK;
   };
-  auto right_mul = [&](const float* P, int64_t rows_pad, const std::vector<zdouble>& M, int mcols, int Lout, float* out) -> int {
-    embed_right(M, l, mcols, LP, Lout, hE);
+  auto right_mul = [&](const float* P, int64_t rows_pad, const std::vector<zdouble>& M, int mcols, int Lout, float* out, const double* colscale = nullptr) -> int {
+    hostla::embed_right(M.data(), l, l, mcols, LP, Lout, hE, colscale);
     HIPCHK(hipMemcpyAsync(Ed, hE.data(), sizeof(double) * LP * Lout, hipMemcpyHostToDevice, ctx->stream));
     CHK(launch_matmul(ctx, P, rows_pad, LP, Ed, Lout, out));
     HIPCHK(hipStreamSynchronize(ctx->stream));    // hE / Ed are reused
@@ -5076,7 +4732,7 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
   };
   auto orth = [&](const float* P, int64_t rows_pad, float* out, bool tall_side = false) -> int {
     CHK(gram_h(P, rows_pad, tall_side));
-    host_zchol_rinv(H, l, T, 1e-13);
+    hostla::chol_rinv(H.data(), l, l, T, 1e-13);
     return right_mul(P, rows_pad, T, l, LP, out);
   };
   // start panel [Omega | 0]: a real Gaussian (or the identity for a full-width sketch, which the caller passes as omega)
@@ -5095,22 +4751,6 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
   // ---- block Lanczos state: blocks Z_0 .. Z_{nb-1} side by side in Kw (orthonormal, dead columns zero); block b < nW has
   //      been multiplied: slot b of Pt holds A_op Z_b (or its Q factor, then Rf[b] is the triangular factor) and block b of Ww
   //      holds W_b with M Z_b = W_b Rf[b]
-  auto cplx_block = [&](const double* g, int64_t ldc, std::vector<zdouble>& out) {   // complex l x l block of a real LP x LP cross-Gram block
-    out.assign((size_t)l * l, zdouble(0.0, 0.0));
-    for (int i = 0; i < l; ++i)
-      for (int j = 0; j < l; ++j)
-        out[(size_t)i * l + j] = zdouble(g[(size_t)i * ldc + j] + g[(size_t)(h + i) * ldc + h + j], g[(size_t)i * ldc + h + j] - g[(size_t)(h + i) * ldc + j]);
-  };
-  auto zmatmul = [&](const std::vector<zdouble>& X, const std::vector<zdouble>& Y) {    // l x l
-    std::vector<zdouble> Z((size_t)l * l, zdouble(0.0, 0.0));
-    for (int i = 0; i < l; ++i)
-      for (int t = 0; t < l; ++t) {
-        const zdouble x = X[(size_t)i * l + t];
-        if (x == zdouble(0.0, 0.0)) continue;
-        for (int j = 0; j < l; ++j) Z[(size_t)i * l + j] += x * Y[(size_t)t * l + j];
-      }
-    return Z;
-  };
   auto copy_block = [&](float* wide, const float* src, int blk) -> int {
     HIPCHK(hipMemcpy2DAsync(wide + (size_t)blk * LP, sizeof(float) * ldk, src, sizeof(float) * LP, sizeof(float) * LP, (size_t)small_pad,
                             hipMemcpyDeviceToDevice, ctx->stream));
@@ -5131,58 +4771,57 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
   };
   int nb = 0, nW = 0;
   bool exhausted = false, orth_rest = orth_always;
-  std::vector<std::vector<zdouble>> Rf(nbmax);      // (empty = identity: the tall panel was not orthonormalised)
+  std::vector<std::vector<zdouble>> Rf(nbmax), raw; // (Rf: empty = identity: the tall panel was not orthonormalised)
   std::vector<zdouble> Hqq, blk;
   std::vector<double> dref(l), ones(l, 1.0);
-  // multiply the newest block (b = nb - 1 = nW): slot b, W_b; then the next block = what is left of W_b after two rounds of
+  // multiply the newest block (b = nb - 1 = nW): slot b of Pt <- A_op Z_b, or its Q factor and Rf[b]; hqq (optional): P^H P of the product
+  auto multiply_newest = [&](std::vector<zdouble>* hqq) -> int {
+    float* slot = Pt + (size_t)nW * tall_pad * LP;
+    Rf[nW].clear();
+    if (ctx->last_iters == 0 || orth_rest) {
+      CHK(fwd(Zs, Yt, pp));
+      CHK(gram_h(Yt, tall_pad, true));
+      if (hqq) *hqq = H;
+      hostla::chol_rinv(H.data(), l, l, T, 1e-13, &Rf[nW]);
+      return right_mul(Yt, tall_pad, T, l, LP, slot);
+    }
+    CHK(fwd(Zs, slot, pp));
+    if (hqq) {
+      CHK(gram_h(slot, tall_pad, true));
+      *hqq = H;
+    }
+    return EOFX_OK;
+  };
+  // one step: multiply the newest block, W_b; then the next block = what is left of W_b after two rounds of
   // (project on all blocks, Cholesky-QR).  A column of the new block dies when what is left of it after the columns before it
   // falls below 1e-13 of its own squared norm (as everywhere), or -- first round -- below 1e-10 of its squared norm BEFORE the
   // projection (a residual below 1e-5 of the product is the rounding noise of a converged direction), or -- second round --
   // when the re-projected unit column kept less than half its length (it lay inside the blocks already there).
   auto lanczos_step = [&]() -> int {
     const int b = nW;
-    float* slot = Pt + (size_t)b * tall_pad * LP;
-    Rf[b].clear();
-    if (ctx->last_iters == 0 || orth_rest) {
-      CHK(fwd(Zs, Yt, pp));
-      CHK(gram_h(Yt, tall_pad, true));
-      host_zchol_rinv(H, l, T, 1e-13, &Rf[b]);
-      CHK(right_mul(Yt, tall_pad, T, l, LP, slot));
-    } else {
-      CHK(fwd(Zs, slot, pp));
-    }
-    CHK(bwd(slot, Ws, pp));
+    CHK(multiply_newest(nullptr));
+    CHK(bwd(Pt + (size_t)b * tall_pad * LP, Ws, pp));
     const bool first = ctx->last_iters == 0;
     ++ctx->last_iters;
     CHK(copy_block(Ww, Ws, b));
     nW = b + 1;
     CHK(project(Ws, nb, Vs, true));
     CHK(gram_h(Vs, small_pad));                      // (synchronises: hC is on the host)
-    for (int j = 0; j < l; ++j) dref[j] = H[(size_t)j * l + j].real();      // |W_j|^2 = |V_j|^2 + |K^H W_j|^2
-    for (int c = 0; c < nb; ++c) {
-      cplx_block(&hC[(size_t)c * LP * LP], LP, blk);
-      for (int i = 0; i < l; ++i)
-        for (int j = 0; j < l; ++j) dref[j] += std::norm(blk[(size_t)i * l + j]);
-    }
+    hostla::product_norms(H, hC.data(), nb, LP, l, dref);
     if (first && !orth_always && n_iter > 1) {       // peaked spectrum?  H_00 = Z_0^H M Z_0 is on the host
-      cplx_block(hC.data(), LP, blk);
-      std::vector<zdouble> H00 = Rf[0].empty() ? blk : zmatmul(blk, Rf[0]), V0;
-      for (int i = 0; i < l; ++i)
-        for (int j = i; j < l; ++j) {
-          const zdouble v = 0.5 * (H00[(size_t)i * l + j] + std::conj(H00[(size_t)j * l + i]));
-          H00[(size_t)i * l + j] = v;
-          H00[(size_t)j * l + i] = std::conj(v);
-        }
+      hostla::cplx_block(hC.data(), LP, h, l, blk);
+      std::vector<zdouble> H00 = Rf[0].empty() ? blk : hostla::zmatmul(blk, Rf[0], l), V0;
+      hostla::hermitise(H00, l);
       std::vector<double> w0;
-      orth_rest = host_heigh(H00, l, w0, V0) != EOFX_OK || !(w0[l - 1] > 0.0) || std::sqrt(w0[0] / w0[l - 1]) > EOFX_PEAKED_RATIO;
+      orth_rest = hosteig::heigh(H00, l, w0, V0) != 0 || hostla::peaked_spectrum(w0.data(), l);      // (a failed solve keeps the step)
     }
     int live = 0;
-    host_zchol_rinv(H, l, T, 1e-13, nullptr, &live, dref.data(), 1e-10);
+    hostla::chol_rinv(H.data(), l, l, T, 1e-13, (std::vector<zdouble>*)nullptr, &live, dref.data(), 1e-10);
     CHK(right_mul(Vs, small_pad, T, l, LP, Zs));
     if (live > 0) {
       CHK(project(Zs, nb, Vs, false));
       CHK(gram_h(Vs, small_pad));
-      host_zchol_rinv(H, l, T, 1e-13, nullptr, &live, ones.data(), 0.25);
+      hostla::chol_rinv(H.data(), l, l, T, 1e-13, (std::vector<zdouble>*)nullptr, &live, ones.data(), 0.25);
       CHK(right_mul(Vs, small_pad, T, l, LP, Zs));
     }
     if (trace) fprintf(stderr, "[eofx_rsvd_c64] product %d: %d live columns in the next block (%d blocks)\n", ctx->last_iters, live, nb + (live > 0));
@@ -5197,7 +4836,7 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
   // Rayleigh-Ritz over the first nbr blocks: H = K^H M K from the columns K^H W_i Rf[i] (i < nW) and, when the newest block has no
   // product yet, P^H P of its tall panel (Hqq).  -> leading l eigenvectors X (order nbr l), values wv; res[j] (with_res): the
   // norm of the part of M K y_j outside the first nbr blocks, read off the coupling to block nbr.
-  std::vector<double> Xr, Xi, wv, hCf;
+  std::vector<double> Xr, Xi, wv, hCf, Hr, Hi;
   auto rayleigh_ritz = [&](int nbr, bool with_last, std::vector<double>* res) -> int {
     const int nWr = std::min(nW, nbr);
     const int nrow = res ? std::min(nb, nbr + 1) : nbr;         // one more block row: the coupling
@@ -5205,38 +4844,9 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
     hCf.resize((size_t)nrow * LP * nWr * LP);
     HIPCHK(hipMemcpyAsync(hCf.data(), Cf, sizeof(double) * hCf.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    const int64_t ldc = (int64_t)nWr * LP;
     const int m = nbr * l;
-    std::vector<std::vector<zdouble>> raw((size_t)nrow * nbr);
-    for (int i = 0; i < nWr; ++i)
-      for (int j = 0; j < nrow; ++j) {
-        cplx_block(&hCf[(size_t)j * LP * ldc + (size_t)i * LP], ldc, blk);
-        raw[(size_t)j * nbr + i] = Rf[i].empty() ? blk : zmatmul(blk, Rf[i]);
-      }
-    if (with_last) raw[(size_t)(nbr - 1) * nbr + nbr - 1] = Hqq;
-    std::vector<double> Hr((size_t)m * m, 0.0), Hi((size_t)m * m, 0.0);
-    for (int a = 0; a < nbr; ++a)
-      for (int c = a; c < nbr; ++c) {
-        const std::vector<zdouble>& u = raw[(size_t)a * nbr + c];     // block (a, c)
-        const std::vector<zdouble>& v = raw[(size_t)c * nbr + a];     // block (c, a): its conjugate transpose is another reading of (a, c)
-        if (u.empty() && v.empty()) continue;
-        const double wu = u.empty() ? 0.0 : (v.empty() ? 1.0 : 0.5), wvv = v.empty() ? 0.0 : (u.empty() ? 1.0 : 0.5);
-        for (int i = 0; i < l; ++i)
-          for (int j = 0; j < l; ++j) {
-            zdouble val(0.0, 0.0);
-            if (!u.empty()) val += wu * u[(size_t)i * l + j];
-            if (!v.empty()) val += wvv * std::conj(v[(size_t)j * l + i]);
-            const size_t ij = (size_t)(a * l + i) * m + c * l + j, ji = (size_t)(c * l + j) * m + a * l + i;
-            Hr[ij] = val.real();
-            Hi[ij] = val.imag();
-            if (a != c) {
-              Hr[ji] = val.real();
-              Hi[ji] = -val.imag();
-            }
-          }
-      }
-    for (double v : Hr)
-      if (!std::isfinite(v)) return set_err(ctx, EOFX_ERR_LINALG, "SVD failed. This may be due to isolated NaN values in the data.");
+    hostla::ritz_assemble(hCf.data(), nrow, nWr, nbr, LP, l, Rf, with_last ? &Hqq : nullptr, raw, Hr, Hi);
+    if (!hostla::all_finite(Hr.data(), Hr.size())) return set_err(ctx, EOFX_ERR_LINALG, "SVD failed. This may be due to isolated NaN values in the data.");
     wv.assign(l, 0.0);
     Xr.assign((size_t)m * l, 0.0);
     Xi.assign((size_t)m * l, 0.0);
@@ -5244,35 +4854,11 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
     const int rc_rr = hosteig::zheigh_top(Hr.data(), Hi.data(), m, l, wv.data(), Xr.data(), Xi.data());
     if (trace) fprintf(stderr, "[eofx_rsvd_c64] host Rayleigh-Ritz solve, order %d: %.2f ms\n", m,
                        1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_rr0).count());
-    if (rc_rr != 0) {
-      // general-purpose route (real symmetric embedding): slower, no assumptions
-      std::vector<zdouble> Hz((size_t)m * m), Vz;
-      for (size_t e = 0; e < Hz.size(); ++e) Hz[e] = zdouble(Hr[e], Hi[e]);
-      std::vector<double> wz;
-      if (host_heigh(Hz, m, wz, Vz) != EOFX_OK) return set_err(ctx, EOFX_ERR_LINALG, "complex SVD: Rayleigh-Ritz eigen-solver failed");
-      for (int i = 0; i < m; ++i)
-        for (int j = 0; j < l; ++j) {
-          Xr[(size_t)i * l + j] = Vz[(size_t)i * m + j].real();
-          Xi[(size_t)i * l + j] = Vz[(size_t)i * m + j].imag();
-        }
-      std::copy(wz.begin(), wz.begin() + l, wv.begin());
-    }
+    if (rc_rr != 0 && hosteig::zheigh_top_embedded(Hr.data(), Hi.data(), m, l, wv.data(), Xr.data(), Xi.data()) != 0)
+      return set_err(ctx, EOFX_ERR_LINALG, "complex SVD: Rayleigh-Ritz eigen-solver failed");
     if (res) {
       res->assign(l, 0.0);
-      if (nrow > nbr)
-        for (int j = 0; j < l; ++j) {
-          double r2 = 0.0;
-          for (int i2 = 0; i2 < l; ++i2) {           // row i2 of block nbr of M K y_j
-            zdouble acc(0.0, 0.0);
-            for (int c = 0; c < nWr; ++c) {
-              const std::vector<zdouble>& cb = raw[(size_t)nbr * nbr + c];
-              if (cb.empty()) continue;
-              for (int t = 0; t < l; ++t) acc += cb[(size_t)i2 * l + t] * zdouble(Xr[(size_t)(c * l + t) * l + j], Xi[(size_t)(c * l + t) * l + j]);
-            }
-            r2 += std::norm(acc);
-          }
-          (*res)[j] = std::sqrt(r2);
-        }
+      if (nrow > nbr) hostla::ritz_residual(raw, nbr, nWr, l, Xr.data(), Xi.data(), *res);
     }
     return EOFX_OK;
   };
@@ -5281,12 +4867,10 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
   auto coeff_stack = [&](int nbr, bool with_rf) -> int {
     hEall.assign((size_t)nbr * LP * LP, 0.0);
     std::vector<double> eb;
-    std::vector<zdouble> yb((size_t)l * l);
     for (int b = 0; b < nbr; ++b) {
-      for (int i = 0; i < l; ++i)
-        for (int j = 0; j < l; ++j) yb[(size_t)i * l + j] = zdouble(Xr[(size_t)(b * l + i) * l + j], Xi[(size_t)(b * l + i) * l + j]);
-      const std::vector<zdouble> cb = (with_rf && !Rf[b].empty()) ? zmatmul(Rf[b], yb) : yb;
-      embed_right(cb, l, l, LP, LP, eb);
+      const std::vector<zdouble> yb = hostla::ritz_block(Xr.data(), Xi.data(), b, l);
+      const std::vector<zdouble> cb = (with_rf && !Rf[b].empty()) ? hostla::zmatmul(Rf[b], yb, l) : yb;
+      hostla::embed_right(cb.data(), l, l, l, LP, LP, eb);
       std::copy(eb.begin(), eb.end(), hEall.begin() + (size_t)b * LP * LP);
     }
     HIPCHK(hipMemcpyAsync(Eall, hEall.data(), sizeof(double) * hEall.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -5322,92 +4906,32 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
     std::swap(Zs, Vs);
     CHK(copy_block(Kw, Zs, 0));
     nb = 1;
-    // "converge" (round 6): continue until every WANTED singular value is good to 2e-6 and every gap-separated wanted vector to
-    // |cos| >= 1 - 5e-6 -- inside the parity tolerances (1e-5 on the values against the float64 oracle, |cos| >= 1 - 1e-5 for modes
-    // separated by 2 %) -- or 20 products have been made (lobpcg's own limit under svds).  The error of a Ritz value theta_j of
-    // M = A_op^H A_op (theta = sigma^2) is estimated from its OWN history: Ritz values of a growing Krylov space rise monotonically
-    // towards their eigenvalues and, product after product, geometrically; with D_c the rise between two checks d products apart and
-    // rho = D_c / D_{c-1} the ratio of two successive rises, the distance still to go is D_c rho / (1 - rho) (first estimate,
-    // without a ratio: D_c).  Round 5 asked for a residual |M x - theta x| <= 1e-5 theta instead: values were then good to 1e-8 and
-    // a field whose last wanted modes sit a per cent above a flat bulk always paid the full 20 products; a residual bound with
-    // the gap to the nearest Ritz value (tried first this round) is 250 times too pessimistic there
-    // (profiles/r06_r9_evidence*.txt).  A check is a host Rayleigh-Ritz solve (0.6 ms at order 120, 5 at 240, 16 at 360 ~ one
-    // product): every third product from three before scikit-learn's count on (a field that "auto" would have served stops there at
-    // the price of two small solves), and none any more once the observed rate says the limit of 20 products comes first (modes
-    // inside a flat bulk: the reference's lobpcg runs into its iteration limit on those as well).
-    const double val_tol = 4e-6, vec_tol = 1e-5, sep_rel = 0.04;
-    const int check_every = 3;
-    int next_check = std::max(std::max(auto_count, it_min) - check_every, it_min);
-    double worst_prev = -1.0;
-    std::vector<double> th_prev, rise_prev;
+    // "converge" (round 6): the Ritz values' own history (hostla::RitzHistory) decides when to stop, or 20 products (lobpcg's limit under svds)
+    hostla::RitzHistory history(auto_count, it_min);
     while (ctx->last_iters < n_iter && !exhausted) {
       if (nb == nbmax) CHK(compress());
       CHK(lanczos_step());
-      if (adaptive && !exhausted && ctx->last_iters >= next_check && ctx->last_iters < n_iter) {
+      if (adaptive && !exhausted && ctx->last_iters >= history.next_check && ctx->last_iters < n_iter) {
         CHK(rayleigh_ritz(nb - 1, false, nullptr));
-        double worst = th_prev.empty() ? 1e300 : 0.0;       // largest (estimate / tolerance) over the wanted modes: <= 1 = converged
-        std::vector<double> rise(k, 0.0);
-        for (int j = 0; j < k && !th_prev.empty(); ++j) {
-          const double th = std::max(wv[j], 1e-300);
-          rise[j] = std::fabs(wv[j] - th_prev[j]) / th;
-          double rho = 0.5;                                 // no ratio yet: the rise itself is the estimate
-          if (!rise_prev.empty() && rise_prev[j] > 0.0) rho = std::min(0.7, std::max(0.02, rise[j] / rise_prev[j]));
-          const double est = rise[j] * rho / (1.0 - rho);
-          double score = est / val_tol;
-          double gap = 1e300;                               // relative gap to the nearest other Ritz value
-          if (j > 0) gap = std::min(gap, (wv[j - 1] - wv[j]) / th);
-          if (j + 1 < l) gap = std::min(gap, (wv[j] - wv[j + 1]) / th);
-          if (gap >= sep_rel && gap < 1e300) score = std::max(score, est / gap / vec_tol);     // sin^2 of the vector's angle ~ error / gap
-          worst = std::max(worst, score);
-        }
-        if (trace) fprintf(stderr, "[eofx_rsvd_c64] after %d products: worst (error estimate / tolerance) over the leading %d Ritz values %.3e\n", ctx->last_iters, k, worst);
-        if (worst <= 1.0) break;
-        next_check = ctx->last_iters + check_every;
-        if (!rise_prev.empty() && worst_prev > 0.0 && worst < 1e299) {      // two estimates: will the limit come first?
-          const double f = worst / worst_prev;                               // factor per check interval
-          const double checks_needed = f < 1.0 ? std::log(worst) / std::log(1.0 / f) : 1e9;
-          if ((double)ctx->last_iters + checks_needed * check_every > (double)n_iter + check_every) {
-            next_check = n_iter + 1;
-            if (trace) fprintf(stderr, "[eofx_rsvd_c64] at this rate (x %.3g per %d products) the limit of %d products comes first: no further checks\n", f, check_every, n_iter);
-          }
-        }
-        if (!th_prev.empty()) {
-          rise_prev = rise;
-          worst_prev = worst;
-        }
-        th_prev.assign(wv.begin(), wv.begin() + k);
+        const bool stop = history.feed(wv.data(), k, l, ctx->last_iters, n_iter);
+        if (trace) fprintf(stderr, "[eofx_rsvd_c64] after %d products: worst (error estimate / tolerance) over the leading %d Ritz values %.3e\n", ctx->last_iters, k, history.worst);
+        if (stop) break;
+        if (trace && history.factor > 0.0)
+          fprintf(stderr, "[eofx_rsvd_c64] at this rate (x %.3g per %d products) the limit of %d products comes first: no further checks\n", history.factor, hostla::RitzHistory::check_every, n_iter);
       }
     }
     bool with_last = false;
     if (!exhausted) {          // the newest block's panel: its diagonal block of H is P^H P
-      const int b = nb - 1;
-      float* slot = Pt + (size_t)b * tall_pad * LP;
-      Rf[b].clear();
-      if (orth_rest || ctx->last_iters == 0) {
-        CHK(fwd(Zs, Yt, pp));
-        CHK(gram_h(Yt, tall_pad, true));
-        Hqq = H;
-        host_zchol_rinv(H, l, T, 1e-13, &Rf[b]);
-        CHK(right_mul(Yt, tall_pad, T, l, LP, slot));
-      } else {
-        CHK(fwd(Zs, slot, pp));
-        CHK(gram_h(slot, tall_pad, true));
-        Hqq = H;
-      }
+      CHK(multiply_newest(&Hqq));
       with_last = true;
     }
     CHK(rayleigh_ritz(nb, with_last, nullptr));
     if (trace) fprintf(stderr, "[eofx_rsvd_c64] Rayleigh-Ritz over %d blocks (order %d) after %d products: leading Ritz values %.6e %.6e ... %.6e\n", nb, nb * l, ctx->last_iters, wv[0], l > 1 ? wv[1] : 0.0, wv[l - 1]);
     CHK(coeff_stack(nb, true));
     CHK(launch_matmul_gen(ctx, Pt, LP, tall_pad * LP, LP / 64, tall_pad, nb * LP, Eall, LP, nullptr, Yt));   // A_op K y
-    CHK(orth(Yt, tall_pad, Qt, true));
-    CHK(orth(Qt, tall_pad, Yt, true));                     // Q in Yt (CholeskyQR2)
-    CHK(bwd(Yt, Ws, pf));                            // B^H, B = Q^H A_op
-    CHK(gram_h(Ws, small_pad));                      // B B^H
-    if (host_heigh(H, l, w, Uh) != EOFX_OK) return set_err(ctx, EOFX_ERR_LINALG, "complex SVD: Hermitian eigen-solver failed");
   } else {
-    bool orth_rest = orth_always;
-    std::vector<double> ritz_prev;
+    std::vector<double> ritz_prev, w0;
+    std::vector<zdouble> V0;
     int calm = 0;
     for (int it = 0; it < n_iter; ++it) {
       CHK(fwd(Zs, Yt, pp));
@@ -5419,51 +4943,40 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
       }
       CHK(gram_h(Ws, small_pad));
       ctx->last_iters = it + 1;
-      if (it == 0 && !orth_always && n_iter > 1) {   // peaked spectrum?  the Hermitian Gram matrix is on the host already
-        std::vector<zdouble> V0;
-        std::vector<double> w0;
-        orth_rest = host_heigh(H, l, w0, V0) != EOFX_OK || !(w0[l - 1] > 0.0) || std::sqrt(w0[0] / w0[l - 1]) > EOFX_PEAKED_RATIO;
-      }
+      if (it == 0 && !orth_always && n_iter > 1)     // peaked spectrum?  the Hermitian Gram matrix is on the host already
+        orth_rest = hosteig::heigh(H, l, w0, V0) != 0 || hostla::peaked_spectrum(w0.data(), l);      // (a failed solve keeps the step)
       bool done = false;
-      if (adaptive) {
-        std::vector<zdouble> V0;
-        std::vector<double> w0;
-        if (host_heigh(H, l, w0, V0) == EOFX_OK) {
-          double worst = 0.0;
-          if (ritz_prev.size() == (size_t)k)
-            for (int j = 0; j < k; ++j) worst = std::max(worst, std::fabs(w0[j] - ritz_prev[j]) / std::max(w0[j], 1e-300));
-          else
-            worst = 1.0;
-          ritz_prev.assign(w0.begin(), w0.begin() + k);
-          calm = worst <= 1e-6 ? calm + 1 : 0;
-          if (trace) fprintf(stderr, "[eofx_rsvd_c64] iteration %d: max relative change of the leading %d Ritz values %.3e\n", it + 1, k, worst);
-          done = calm >= 2 && it + 1 >= it_min;
-        }
+      if (adaptive && hosteig::heigh(H, l, w0, V0) == 0) {
+        double worst = 0.0;
+        if (ritz_prev.size() == (size_t)k)
+          for (int j = 0; j < k; ++j) worst = std::max(worst, std::fabs(w0[j] - ritz_prev[j]) / std::max(w0[j], 1e-300));
+        else
+          worst = 1.0;
+        ritz_prev.assign(w0.begin(), w0.begin() + k);
+        calm = worst <= 1e-6 ? calm + 1 : 0;
+        if (trace) fprintf(stderr, "[eofx_rsvd_c64] iteration %d: max relative change of the leading %d Ritz values %.3e\n", it + 1, k, worst);
+        done = calm >= 2 && it + 1 >= it_min;
       }
-      host_zchol_rinv(H, l, T, 1e-13);
+      hostla::chol_rinv(H.data(), l, l, T, 1e-13);
       CHK(right_mul(Ws, small_pad, T, l, LP, Zs));
       if (done) break;
     }
     CHK(fwd(Zs, Yt, pp));
-    CHK(orth(Yt, tall_pad, Qt, true));
-    CHK(orth(Qt, tall_pad, Yt, true));                     // Q in Yt (CholeskyQR2)
-    CHK(bwd(Yt, Ws, pf));                            // B^H, B = Q^H A_op
-    CHK(gram_h(Ws, small_pad));                      // B B^H
-    if (host_heigh(H, l, w, Uh) != EOFX_OK) return set_err(ctx, EOFX_ERR_LINALG, "complex SVD: Hermitian eigen-solver failed");
   }
-  std::vector<zdouble> M1((size_t)l * k), M2((size_t)l * k);
+  CHK(orth(Yt, tall_pad, Qt, true));
+  CHK(orth(Qt, tall_pad, Yt, true));                     // Q in Yt (CholeskyQR2: the final stage starts from the tall panel in Yt)
+  CHK(bwd(Yt, Ws, pf));                            // B^H, B = Q^H A_op
+  CHK(gram_h(Ws, small_pad));                      // B B^H
+  if (hosteig::heigh(H, l, w, Uh) != 0) return set_err(ctx, EOFX_ERR_LINALG, "complex SVD: Hermitian eigen-solver failed");
   std::vector<float> hs(k);
+  std::vector<double> inv(k);
   for (int j = 0; j < k; ++j) {
     const double sv = std::sqrt(std::max(w[j], 0.0));
     hs[j] = (float)sv;
-    const double inv = sv > 0.0 ? 1.0 / sv : 0.0;
-    for (int i = 0; i < l; ++i) {
-      M1[(size_t)i * k + j] = Uh[(size_t)i * l + j];
-      M2[(size_t)i * k + j] = Uh[(size_t)i * l + j] * inv;
-    }
+    inv[j] = sv > 0.0 ? 1.0 / sv : 0.0;
   }
-  CHK(right_mul(Yt, tall_pad, M1, k, Lo, Tv));     // A_op = Tall diag(s) Small^H
-  CHK(right_mul(Ws, small_pad, M2, k, Lo, Sv));
+  CHK(right_mul(Yt, tall_pad, Uh, k, Lo, Tv));     // A_op = Tall diag(s) Small^H: Tall = Q Uh[:, :k], Small = B^H Uh[:, :k] / s
+  CHK(right_mul(Ws, small_pad, Uh, k, Lo, Sv, inv.data()));
   // Numerically null modes (more modes asked for than the matrix has rank: the analytic signal of a short series has about
   // n / 2 + 1 independent rows): B^H u / s is rounding noise there.  The reference's solver ends with a dense SVD of A V
   // (scipy svds, _svds.py), whose left vectors are orthonormal whatever the values; here such columns of the small-side factor
@@ -5476,48 +4989,7 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
       std::vector<float> hp((size_t)small * Lo);
       HIPCHK(hipMemcpy2DAsync(hp.data(), sizeof(float) * Lo, Sv, sizeof(float) * Lo, sizeof(float) * Lo, (size_t)small, hipMemcpyDeviceToHost, ctx->stream));
       HIPCHK(hipStreamSynchronize(ctx->stream));
-      auto col = [&](int j, std::vector<zdouble>& v) {
-        v.resize((size_t)small);
-        for (int64_t r = 0; r < small; ++r) v[(size_t)r] = zdouble(hp[(size_t)r * Lo + j], hp[(size_t)r * Lo + ko + j]);
-      };
-      std::vector<std::vector<zdouble>> basis((size_t)k);
-      for (int j = 0; j < first_null; ++j) col(j, basis[(size_t)j]);
-      auto project_out = [&](std::vector<zdouble>& v, int upto) {
-        for (int round = 0; round < 2; ++round)
-          for (int c = 0; c < upto; ++c) {
-            zdouble dot(0.0, 0.0);
-            for (int64_t r = 0; r < small; ++r) dot += std::conj(basis[(size_t)c][(size_t)r]) * v[(size_t)r];
-            for (int64_t r = 0; r < small; ++r) v[(size_t)r] -= dot * basis[(size_t)c][(size_t)r];
-          }
-        double nn = 0.0;
-        for (int64_t r = 0; r < small; ++r) nn += std::norm(v[(size_t)r]);
-        return std::sqrt(nn);
-      };
-      int64_t next_unit = 0;
-      for (int j = first_null; j < k; ++j) {
-        std::vector<zdouble> v;
-        col(j, v);
-        double nn0 = 0.0;
-        for (const zdouble& x : v) nn0 += std::norm(x);
-        double nn = std::isfinite(nn0) && nn0 > 0.0 ? project_out(v, j) / std::sqrt(nn0) : 0.0;
-        while (!(nn > 1e-3) && next_unit < small) {          // inside the span of the others (or not finite): a unit vector instead
-          v.assign((size_t)small, zdouble(0.0, 0.0));
-          v[(size_t)next_unit++] = zdouble(1.0, 0.0);
-          nn = project_out(v, j);
-          if (nn > 0.1) break;
-          nn = 0.0;
-        }
-        double nrm = 0.0;
-        for (const zdouble& x : v) nrm += std::norm(x);
-        nrm = std::sqrt(nrm);
-        for (int64_t r = 0; r < small; ++r) {
-          const zdouble x = nrm > 0.0 ? v[(size_t)r] / nrm : zdouble(0.0, 0.0);
-          v[(size_t)r] = x;
-          hp[(size_t)r * Lo + j] = (float)x.real();
-          hp[(size_t)r * Lo + ko + j] = (float)x.imag();
-        }
-        basis[(size_t)j] = v;
-      }
+      hostla::null_repair_c(hp.data(), small, Lo, ko, first_null, k);
       HIPCHK(hipMemcpy2DAsync(Sv, sizeof(float) * Lo, hp.data(), sizeof(float) * Lo, sizeof(float) * Lo, (size_t)small, hipMemcpyHostToDevice, ctx->stream));
       HIPCHK(hipStreamSynchronize(ctx->stream));
     }

@@ -17,10 +17,12 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <complex>
 #include <cstdint>
 #include <vector>
 
 namespace hosteig {
+typedef std::complex<double> zdouble;
 
 // p += conj(A[k, :]) v_k  (the column-oriented Hermitian product on full row storage), rows/cols [j0, m)
 template <int DUMMY>
@@ -313,6 +315,193 @@ static int zheigh_top(const double* Hr, const double* Hi, int m, int nev, double
     }
   }
   return 0;
+}
+
+// ---- the general-purpose solvers (the l x l problems of the final stage of every decomposition: eofx_host_eigh_f64) ----
+// sqrt(a^2 + b^2): the plain form unless it over- or underflows (std::hypot's care costs 20-40 ns a call, and the QL iteration
+// makes two per rotation)
+static inline double hypot_fast(double a, double b) {
+  const double q = a * a + b * b;
+  if (q > 1e-280 && q < 1e280) return std::sqrt(q);
+  return std::hypot(a, b);
+}
+// Symmetric eigen-decomposition: Householder tridiagonalisation followed by the implicit-shift
+// QL iteration, eigenvectors accumulated (the classic tred2/tql2 scheme), float64.
+// A: n x n row-major (symmetrised on entry) -> w[n] descending, Vec: n x n row-major, eigenvectors in columns.  0 on success.
+static int eigh(const double* Ain, int n, double* w, double* Vec) {
+  if (!Ain || !w || !Vec || n <= 0) return -1;
+  std::vector<double> z((size_t)n * n), d(n), e(n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) z[(size_t)i * n + j] = 0.5 * (Ain[(size_t)i * n + j] + Ain[(size_t)j * n + i]);
+#define Z(i, j) z[(size_t)(i) * n + (j)]
+  // --- Householder reduction to tridiagonal form, accumulating the transformation in z
+  for (int i = n - 1; i >= 1; --i) {
+    const int l = i - 1;
+    double h = 0.0, scale = 0.0;
+    if (l > 0) {
+      for (int k = 0; k <= l; ++k) scale += std::fabs(Z(i, k));
+      if (scale == 0.0) {
+        e[i] = Z(i, l);
+      } else {
+        for (int k = 0; k <= l; ++k) {
+          Z(i, k) /= scale;
+          h += Z(i, k) * Z(i, k);
+        }
+        double f = Z(i, l);
+        double g = (f >= 0.0) ? -std::sqrt(h) : std::sqrt(h);
+        e[i] = scale * g;
+        h -= f * g;
+        Z(i, l) = f - g;
+        f = 0.0;
+        for (int j = 0; j <= l; ++j) {
+          Z(j, i) = Z(i, j) / h;
+          g = 0.0;
+          for (int k = 0; k <= j; ++k) g += Z(j, k) * Z(i, k);
+          for (int k = j + 1; k <= l; ++k) g += Z(k, j) * Z(i, k);
+          e[j] = g / h;
+          f += e[j] * Z(i, j);
+        }
+        const double hh = f / (h + h);
+        for (int j = 0; j <= l; ++j) {
+          f = Z(i, j);
+          e[j] = g = e[j] - hh * f;
+          for (int k = 0; k <= j; ++k) Z(j, k) -= (f * e[k] + g * Z(i, k));
+        }
+      }
+    } else {
+      e[i] = Z(i, l);
+    }
+    d[i] = h;
+  }
+  d[0] = 0.0;
+  e[0] = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const int l = i - 1;
+    if (d[i] != 0.0) {
+      for (int j = 0; j <= l; ++j) {
+        double g = 0.0;
+        for (int k = 0; k <= l; ++k) g += Z(i, k) * Z(k, j);
+        for (int k = 0; k <= l; ++k) Z(k, j) -= g * Z(k, i);
+      }
+    }
+    d[i] = Z(i, i);
+    Z(i, i) = 1.0;
+    for (int j = 0; j <= l; ++j) Z(j, i) = Z(i, j) = 0.0;
+  }
+  // --- implicit QL on the tridiagonal (d, e).  The rotations touch two COLUMNS of the accumulated transformation at a time: they
+  // run on its transpose, where those are two contiguous rows (vectorised; 247 -> ~150 us for the 60 x 60 problem a fit waits for)
+  std::vector<double> zt((size_t)n * n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) zt[(size_t)j * n + i] = z[(size_t)i * n + j];
+  for (int i = 1; i < n; ++i) e[i - 1] = e[i];
+  e[n - 1] = 0.0;
+  for (int l = 0; l < n; ++l) {
+    int iter = 0, m;
+    do {
+      for (m = l; m < n - 1; ++m) {
+        const double dd = std::fabs(d[m]) + std::fabs(d[m + 1]);
+        if (std::fabs(e[m]) <= 2.220446049250313e-16 * dd) break;
+      }
+      if (m != l) {
+        if (iter++ == 200) return -2;
+        double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
+        double r = hypot_fast(g, 1.0);
+        g = d[m] - d[l] + e[l] / (g + (g >= 0.0 ? std::fabs(r) : -std::fabs(r)));
+        double s = 1.0, c = 1.0, p = 0.0;
+        int i;
+        for (i = m - 1; i >= l; --i) {
+          double f = s * e[i];
+          const double b = c * e[i];
+          e[i + 1] = (r = hypot_fast(f, g));
+          if (r == 0.0) {
+            d[i + 1] -= p;
+            e[m] = 0.0;
+            break;
+          }
+          s = f / r;
+          c = g / r;
+          g = d[i + 1] - p;
+          r = (d[i] - g) * s + 2.0 * c * b;
+          d[i + 1] = g + (p = s * r);
+          g = c * r - b;
+          {
+            double* __restrict__ ri = zt.data() + (size_t)i * n;
+            double* __restrict__ rj = zt.data() + (size_t)(i + 1) * n;
+            for (int k = 0; k < n; ++k) {
+              const double fk = rj[k], zk = ri[k];
+              rj[k] = s * zk + c * fk;
+              ri[k] = c * zk - s * fk;
+            }
+          }
+        }
+        if (r == 0.0 && i >= l) continue;
+        d[l] -= p;
+        e[l] = g;
+        e[m] = 0.0;
+      }
+    } while (m != l);
+  }
+#undef Z
+  std::vector<int> idx(n);
+  for (int i = 0; i < n; ++i) idx[i] = i;
+  std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return d[a] > d[b]; });
+  for (int j = 0; j < n; ++j) {
+    w[j] = d[idx[j]];
+    for (int i = 0; i < n; ++i) Vec[(size_t)i * n + j] = zt[(size_t)idx[j] * n + i];
+  }
+  return 0;
+}
+
+// Hermitian eigen-decomposition through the real symmetric embedding [[Hr, -Hi], [Hi, Hr]] (every eigenvalue twice,
+// eigenvectors (x; y) <-> x + i y) and the real tridiagonal QL solver; complex Gram-Schmidt inside clusters removes the
+// duplicates.  -> w descending, V columns (row-major l x l).  0 on success.
+static int heigh(const std::vector<zdouble>& H, int l, std::vector<double>& w, std::vector<zdouble>& V) {
+  const int m = 2 * l;
+  std::vector<double> E((size_t)m * m), ew(m), ev((size_t)m * m);
+  for (int i = 0; i < l; ++i)
+    for (int j = 0; j < l; ++j) {
+      const zdouble v = H[(size_t)i * l + j];
+      E[(size_t)i * m + j] = v.real();
+      E[(size_t)(l + i) * m + l + j] = v.real();
+      E[(size_t)i * m + l + j] = -v.imag();
+      E[(size_t)(l + i) * m + j] = v.imag();
+    }
+  const int rc = eigh(E.data(), m, ew.data(), ev.data());   // descending eigenvalues, columns
+  if (rc != 0) return rc;
+  w.assign(l, 0.0);
+  V.assign((size_t)l * l, zdouble(0.0, 0.0));
+  int got = 0;
+  const double scale = std::max(std::fabs(ew[0]), std::fabs(ew[m - 1]));
+  for (int c = 0; c < m && got < l; ++c) {
+    std::vector<zdouble> v(l);
+    for (int i = 0; i < l; ++i) v[i] = zdouble(ev[(size_t)i * m + c], ev[(size_t)(l + i) * m + c]);
+    for (int pass = 0; pass < 2; ++pass)
+      for (int g = 0; g < got; ++g) {
+        if (std::fabs(w[g] - ew[c]) > 1e-6 * scale + 1e-300) continue;    // other clusters are orthogonal already
+        zdouble dot(0.0, 0.0);
+        for (int i = 0; i < l; ++i) dot += std::conj(V[(size_t)i * l + g]) * v[i];
+        for (int i = 0; i < l; ++i) v[i] -= dot * V[(size_t)i * l + g];
+      }
+    double nrm = 0.0;
+    for (int i = 0; i < l; ++i) nrm += std::norm(v[i]);
+    nrm = std::sqrt(nrm);
+    if (nrm < 0.5) continue;             // the partner (i v) of an accepted vector
+    for (int i = 0; i < l; ++i) V[(size_t)i * l + got] = v[i] / nrm;
+    w[got] = ew[c];
+    ++got;
+  }
+  return got == l ? 0 : -5;
+}
+// zheigh_top through that general-purpose route: slower, no assumptions (same arguments)
+static int zheigh_top_embedded(const double* Hr, const double* Hi, int m, int nev, double* w, double* Xr, double* Xi) {
+  std::vector<zdouble> Hz((size_t)m * m), Vz;
+  std::vector<double> wz;
+  for (size_t e = 0; e < Hz.size(); ++e) Hz[e] = zdouble(Hr[e], Hi[e]);
+  const int rc = heigh(Hz, m, wz, Vz);
+  for (int i = 0; i < m && rc == 0; ++i)
+    for (int j = 0; j < nev; ++j) Xr[(size_t)i * nev + j] = Vz[(size_t)i * m + j].real(), Xi[(size_t)i * nev + j] = Vz[(size_t)i * m + j].imag();
+  if (rc == 0) std::copy(wz.begin(), wz.begin() + nev, w);
+  return rc;
 }
 
 }  // namespace hosteig
