@@ -6154,7 +6154,14 @@ extern "C" int eofx_spca_loop_f64(eofx_ctx* ctx, const double* V, int64_t p, int
   HIPCHK(hipMemsetAsync(st, 0, nst * 8, ctx->stream));
   HIPCHK(hipMemcpy2DAsync(B, (size_t)k * 8, V, (size_t)l * 8, (size_t)k * 8, (size_t)p, hipMemcpyDeviceToDevice, ctx->stream));
   const size_t lds = ((size_t)lk + (size_t)SPCA_R * (l + k) + 512) * 8;
-  if (lds > (64u << 10)) (void)hipFuncSetAttribute((const void*)spca_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > (64u << 10)) {                              // beyond the default dynamic LDS limit: ask, and say so if refused
+    const hipError_t e = hipFuncSetAttribute((const void*)spca_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return set_err(ctx, EOFX_ERR_HIP, "the sparse PCA update kernel needs %zu bytes of dynamic LDS for l = %d, k = %d: %s", lds, l, k,
+                     hipGetErrorString(e));
+    }
+  }
   double* W = st + 2 * lk + 2;
   auto update = [&](int apply) {
     hipLaunchKernelGGL(spca_update_kernel, dim3((unsigned)G), dim3(256), lds, ctx->stream, V, p, l, k, B, (const double*)W, nu,
