@@ -513,6 +513,18 @@ int eofx_spca_prox_f64(eofx_ctx *ctx, const double *X, const double *Y, double s
  * beyond.  Float64 arithmetic, no atomics, fixed summation order.  EOFX_ERR_ARG unless n >= 2, 1 <= ntau <= n - 1 (the
  * largest lag leaves two samples) and p >= 1; EOFX_ERR_SHAPE for p > 1024.                                             */
 int eofx_lagcov_f64(eofx_ctx *ctx, const float *S, int64_t n, int p, int64_t ld, const double *w, int ntau, double *M);
+/* ---- low-pass covariance of low-frequency component analysis (Wills et al. 2018; csrc/eofx_lowpass.hpp) -----------------
+ * For the float32 device panel S [n x p] (row stride ld >= p), the float64 weights w [h + 1] (host|device) of a symmetric
+ * filter of half-width h and the optional linear trend [2 x p] (host|device; a_j then b_j, NULL for none):
+ *   d(u, j) = S[u, j] - (a_j + b_j u),   Y[t, j] = sum_{k = -h .. h} w[|k|] d(refl(t + k), j) + (a_j + b_j t),
+ * refl the mirror about the first and the last sample (refl(u) = -u below 0, 2 (n - 1) - u above n - 1).
+ * R [p x p] (device, row-major) = Y^T Y and / or Y [n x p] (device, tight); either may be NULL, not both.  Y is float64 and
+ * summed over k ascending from -h; R runs on the fp64 matrix cores, only the tiles on or above its diagonal are computed and
+ * every value is written with its mirror image: R equals its transpose bit for bit.  Y is written once (into the arena when
+ * the caller wants R alone) and read back by the product.  No atomics, fixed summation order.
+ * h = 0 (w = [1]) gives Y = S.  EOFX_ERR_ARG unless n >= 2, 0 <= h <= n - 1 and p >= 1; EOFX_ERR_SHAPE for p > 1024.        */
+int eofx_lowpass_cov_f64(eofx_ctx *ctx, const float *S, int64_t n, int p, int64_t ld, const double *w, int h,
+                         const double *trend, double *R, double *Y);
 /* ---- PC-space product of principal oscillation pattern analysis (xeofs/single/pop.py:185-198, csrc/eofx_pcmul.hpp) ---
  * Y [rows x b] = X [rows x a] M [a x b]: X a device panel of float32 or float64 (x_dtype) with row stride ldx >= a, M
  * float64 row-major (host|device), Y a device panel of float64 or float32 (y_dtype) with row stride ldy >= b.  Accumulated

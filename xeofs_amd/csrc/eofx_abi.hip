@@ -13,6 +13,7 @@
 #include "eofx_gw.hpp"
 #include "eofx_spca.hpp"
 #include "eofx_lagcov.hpp"
+#include "eofx_lowpass.hpp"
 #include "eofx_pcmul.hpp"
 #include "eofx_viewcov.hpp"
 #include "eofx_lrfill.hpp"
@@ -6286,6 +6287,66 @@ extern "C" int eofx_lagcov_f64(eofx_ctx* ctx, const float* S, int64_t n, int p, 
                      (int64_t)pp, G);
   KCHK();
   HIPCHK(hipStreamSynchronize(ctx->stream));       // (w may be a pageable host buffer; the arena is handed back)
+  return EOFX_OK;
+}
+
+// ---- low-pass covariance of low-frequency component analysis (csrc/eofx_lowpass.hpp) -----------------------------------
+extern "C" int eofx_lowpass_cov_f64(eofx_ctx* ctx, const float* S, int64_t n, int p, int64_t ld, const double* w, int h,
+                                    const double* trend, double* R, double* Y) {
+  if (!ctx || !S || !w || (!R && !Y)) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (n < 2 || ld < p) return set_err(ctx, EOFX_ERR_ARG, "n must be >= 2 and ld >= p (n = %lld, p = %d, ld = %lld)", (long long)n, p, (long long)ld);
+  if (p < 1) return set_err(ctx, EOFX_ERR_ARG, "p must be >= 1, got %d", p);
+  if (p > LAGCOV_PMAX) return set_err(ctx, EOFX_ERR_SHAPE, "the low-pass covariance kernels take p <= %d, got %d", LAGCOV_PMAX, p);
+  if (h < 0 || (int64_t)h > n - 1)
+    return set_err(ctx, EOFX_ERR_ARG, "h must be in [0, n - 1 = %lld] (one reflection about either end), got %d", (long long)(n - 1), h);
+  if (!is_device_ptr(S) || (R && !is_device_ptr(R)) || (Y && !is_device_ptr(Y))) return set_err(ctx, EOFX_ERR_ARG, "S, R and Y must be device buffers");
+  ENTER(ctx);
+  // the symmetric, zero-padded copy of the weights (host)
+  std::vector<double> wh((size_t)h + 1);
+  if (is_device_ptr(w)) {
+    HIPCHK(hipMemcpyAsync(wh.data(), w, wh.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  } else {
+    std::copy(w, w + h + 1, wh.begin());
+  }
+  const size_t nw = (size_t)2 * h + 1 + 2 * LOWPASS_PADW, pp = (size_t)p * p;
+  std::vector<double> wsh(nw, 0.0);
+  for (int k = -h; k <= h; ++k) wsh[(size_t)(LOWPASS_PADW + h + k)] = wh[(size_t)(k < 0 ? -k : k)];
+  const bool own_y = !Y;                           // a caller who wants R alone: Y lives in the arena
+  const int nb = (p + 63) / 64, ny = nb * (nb + 1) / 2;
+  const int64_t ntiles = (n + LOWPASS_R - 1) / LOWPASS_R;
+  const int64_t gmax = std::max<int64_t>(1, std::min<int64_t>(LOWPASS_WGS / ny, LOWPASS_PART_MAX / (int64_t)pp));
+  const int G = (int)std::min<int64_t>(ntiles, gmax);                               // a function of the shape alone
+  CHK(arena_reserve(ctx, (nw + (trend ? 2 * (size_t)p : 0) + (R ? pp * G : 0) + (own_y ? (size_t)n * p : 0)) * 8 + 4 * 256));
+  ArenaScope scope(ctx);
+  ARENA(double, wsym, nw);
+  HIPCHK(hipMemcpyAsync(wsym, wsh.data(), nw * 8, hipMemcpyHostToDevice, ctx->stream));
+  double* td = nullptr;
+  if (trend) {
+    td = arena_alloc<double>(ctx, 2 * (size_t)p);
+    if (!td) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (trend)");
+    HIPCHK(hipMemcpyAsync(td, trend, 2 * (size_t)p * 8, is_device_ptr(trend) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+  }
+  double* Yd = Y;
+  if (own_y) {
+    Yd = arena_alloc<double>(ctx, (size_t)n * p);
+    if (!Yd) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (Y)");
+  }
+  const int64_t threads = (n + LOWPASS_WIN - 1) / LOWPASS_WIN * p;
+  hipLaunchKernelGGL(lowpass_fir_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, S, n, p, ld,
+                     (const double*)wsym, h, (const double*)td, Yd);
+  KCHK();
+  if (R) {
+    ARENA(double, part, pp * G);
+    HIPCHK(hipFuncSetAttribute((const void*)lowpass_gram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LOWPASS_LDS_Y));
+    hipLaunchKernelGGL(lowpass_gram_kernel, dim3((unsigned)G, (unsigned)ny), dim3(256), LOWPASS_LDS_Y, ctx->stream,
+                       (const double*)Yd, n, p, part);
+    KCHK();
+    hipLaunchKernelGGL(f64_reduce_kernel, dim3((unsigned)((pp + 63) / 64)), dim3(256), 0, ctx->stream, (const double*)part, R,
+                       (int64_t)pp, G);
+    KCHK();
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // (the staged weights are a pageable host buffer; the arena is handed back)
   return EOFX_OK;
 }
 

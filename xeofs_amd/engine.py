@@ -1381,6 +1381,42 @@ def lagcov(ctx: Context, S, w):
 
 
 # --------------------------------------------------------------------------- #
+# low-pass covariance of low-frequency component analysis (eofx_lowpass_cov_f64, csrc/eofx_lowpass.hpp)   #
+# --------------------------------------------------------------------------- #
+def _lowpass(ctx: Context, S, w, trend, want_r: bool, want_y: bool):
+    torch = _torch()
+    S = device_panel(ctx, S, "S", (torch.float32,))
+    n, p = S.shape
+    w = np.ascontiguousarray(w.detach().cpu().numpy() if hasattr(w, "detach") else w, dtype=np.float64)
+    if w.ndim != 1 or w.size < 1:
+        raise ValueError(f"w must be a vector of the h + 1 weights w_0 .. w_h, got shape {w.shape}")
+    if trend is not None:
+        trend = np.ascontiguousarray(trend.detach().cpu().numpy() if hasattr(trend, "detach") else trend, dtype=np.float64)
+        if trend.shape != (2, p):
+            raise ValueError(f"trend must have shape (2, {p}): the intercepts, then the slopes, got {trend.shape}")
+    R = torch.empty((p, p), dtype=torch.float64, device=S.device) if want_r else None
+    Y = torch.empty((n, p), dtype=torch.float64, device=S.device) if want_y else None
+    raise_for(ctx.lib.eofx_lowpass_cov_f64(ctx.handle, ptr(S), n, p, S.stride(0), ptr(w), w.size - 1, ptr(trend), ptr(R),
+                                           ptr(Y)), ctx.handle)
+    return R, Y
+
+
+def lowpass_cov(ctx: Context, S, w, trend=None, return_filtered: bool = False):
+    """R [p x p] = Y^T Y (float64 device tensor, equal to its transpose bit for bit) of the low-passed panel
+    Y[t, j] = sum_{k = -h .. h} w[|k|] d(refl(t + k), j) + (a_j + b_j t), d(u, j) = S[u, j] - (a_j + b_j u): S [n x p] a
+    float32 panel -- a host array or a device tensor, whose row stride may exceed p --, w [h + 1] the weights of a symmetric
+    filter (h <= n - 1), refl the mirror about the first and the last sample, `trend` [2 x p] the intercepts a and slopes b
+    of a line removed before the filter and added back after it (None: no trend).  `return_filtered`: -> (R, Y)."""
+    R, Y = _lowpass(ctx, S, w, trend, True, return_filtered)
+    return (R, Y) if return_filtered else R
+
+
+def lowpass(ctx: Context, S, w, trend=None):
+    """Y [n x p] (float64 device tensor), the low-passed panel of `lowpass_cov`"""
+    return _lowpass(ctx, S, w, trend, False, True)[1]
+
+
+# --------------------------------------------------------------------------- #
 # PC-space product of principal oscillation pattern analysis (eofx_pcmul_f64, csrc/eofx_pcmul.hpp)   #
 # --------------------------------------------------------------------------- #
 PCMUL_AMAX = 1024         # inner length the kernel takes (the PCA modes)
