@@ -21,8 +21,8 @@ at its edges, case by case against float64.  The rules are those of tests/test_g
   size          every matrix is at most 64 MB
 
 CASES are the shapes (n, p, E, tau, L) that reach each edge; `lag_groupsize`, `lag_groups`, `n_emb`, `tmul_nt_ok` restate
-the host rules of csrc/eofx_abi.hip ONLY to choose shapes and to prove (tests/test_lag_model_host.py, no GPU needed) that
-the list reaches them.  p is used as given for an owned matrix and rounded up to a multiple of 4 for an in-place or raw
+the host rules of csrc/eofx_plans.hpp ONLY to choose shapes and to prove (tests/test_lag_model_host.py, no GPU needed) that
+the list reaches them; tests/test_plans_cpu.py compares them with the header itself.  p is used as given for an owned matrix and rounded up to a multiple of 4 for an in-place or raw
 one (a field stays in place when its feature count is a multiple of 4).
 
 The sample-contiguous source (LagSrc.mode == 2): no public call yields a matrix with that layout alone from a real field
@@ -83,7 +83,7 @@ def n_emb(n, E, tau):
 
 
 def lag_groupsize(E, L):
-    """lag_groupsize of csrc/eofx_abi.hip"""
+    """lag_groupsize of csrc/eofx_plans.hpp"""
     return max(1, min(E, LAG_GROUP_COLS // max(L, 1)))
 
 

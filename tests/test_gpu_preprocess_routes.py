@@ -3,8 +3,9 @@
 reference     `reference()` below: numpy, np.longdouble, two passes over the float32 field (mean, then the squares of the
               deviations).  Never another path of the engine, never a max-norm over the features.
 routes        `colstats_plan`, `summary_blocks`, `apply_plan`, `fit_plan` restate the choices of run_colstats,
-              run_feature_summary, sanitize_and_apply and the fused fit (csrc/eofx_abi.hip).  They only choose shapes and
-              say which layout a case must end in; tests/test_preprocess_model_host.py proves without a GPU that CASES,
+              run_feature_summary, sanitize_and_apply and the fused fit (the plans of the same names and atb_plan in
+              csrc/eofx_plans.hpp; tests/test_plans_cpu.py compares them with the header itself).  They only choose shapes
+              and say which layout a case must end in; tests/test_preprocess_model_host.py proves without a GPU that CASES,
               FIT_CASES and RESAMPLE_CASES reach every route listed there.
 
 Error model (u = 2^-53, e = 2^-24 the unit roundoff of float32, k valid samples of the feature; a = mean |x|,

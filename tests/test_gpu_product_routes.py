@@ -11,7 +11,7 @@ Every case follows the same rules:
   padding       the padding rows of the output are exact zeros afterwards
   size          every matrix is at most 64 MB
 
-Tile decomposition of a panel of L columns (launch_atb in csrc/eofx_abi.hip; "P96" is the partial 96-of-128 tile):
+Tile decomposition of a panel of L columns (atb_tiles in csrc/eofx_plans.hpp; "P96" is the partial 96-of-128 tile):
 
     L     f16x3 (XᵀZ, X·Y over a written matrix)   other precisions, in-place X·Y (axb)
     32    32                                         32
@@ -24,9 +24,9 @@ Tile decomposition of a panel of L columns (launch_atb in csrc/eofx_abi.hip; "P9
     256   128 + 128                                  4 x 64
     288   128 + 128 + 32                             4 x 64 + 32
 
-`tiles()` below restates that rule, `atb_splits()` / `axb_splits()` the split-K plans (atb_plan / axb_plan): they are used
-ONLY to choose shapes and to prove (tests/test_product_model_host.py, no GPU needed) that the shape lists reach S == 1 and
-S > 1 on every launcher.
+`tiles()` below restates that rule, `atb_splits()` / `axb_splits()` the split-K plans (atb_plan / axb_plan of the same
+header): they are used ONLY to choose shapes and to prove (tests/test_product_model_host.py, no GPU needed) that the shape
+lists reach S == 1 and S > 1 on every launcher; tests/test_plans_cpu.py compares them with the header itself.
 """
 
 import math

@@ -1,27 +1,28 @@
 """Host-side checks behind tests/test_gpu_lag_routes.py (no GPU needed).
 
-1. A restatement of the grouping rule of the lag operator (lag_groupsize in csrc/eofx_abi.hip: EOFX_LAG_GROUP_COLS = 1024,
+1. A restatement of the grouping rule of the lag operator (lag_groupsize in csrc/eofx_plans.hpp: EOFX_LAG_GROUP_COLS = 1024,
    G = max(1, min(E, 1024 // L))) and of n' / n'_pad proves that the GPU test's case list reaches every edge it is there
    for.  When a constant of the rule moves, this test says which case has to move with it.
 2. The float64 reference of the uncentred field, recomputed in long double, stays far inside the bounds the GPU test
    asserts: those bounds judge the kernel, not the reference.
 """
 
-import re
-from pathlib import Path
-
 import numpy as np
 
+import plans_shim
 import test_gpu_lag_routes as lag
-
-ROOT = Path(__file__).resolve().parent.parent
 
 
 def test_restated_constants_match_the_source():
-    src = (ROOT / "xeofs_amd" / "csrc" / "eofx_abi.hip").read_text()
-    assert int(re.search(r"constexpr int EOFX_LAG_GROUP_COLS = (\d+);", src).group(1)) == lag.LAG_GROUP_COLS
-    assert "std::max(1, std::min(E, EOFX_LAG_GROUP_COLS / std::max(L, 1)))" in src
-    assert [lag.lag_groupsize(E, L) for E, L in [(1, 32), (40, 32), (11, 96), (5, 256), (3, 544), (3, 2048)]] == [1, 32, 10, 4, 1, 1]
+    """the restated grouping rule against the header itself (csrc/eofx_plans.hpp through tests/plans_shim.cpp, compiled with the
+    host compiler) -- the constant, the group size and the groups in launch order; tests/test_plans_cpu.py sweeps the rest"""
+    lib = plans_shim.lib()
+    assert plans_shim.constants(lib)["LAG_GROUP_COLS"] == lag.LAG_GROUP_COLS
+    shapes = [(1, 32), (40, 32), (11, 96), (5, 256), (3, 544), (3, 2048)]
+    assert [lib.pl_lag_groupsize(E, L) for E, L in shapes] == [lag.lag_groupsize(E, L) for E, L in shapes] == [1, 32, 10, 4, 1, 1]
+    for E, L in shapes + [(21, 96)]:
+        out = np.zeros(E, np.int32)
+        assert out[:lib.pl_lag_groups(E, L, out.ctypes.data)].tolist() == lag.lag_groups(E, L)
     assert lag.lag_groups(11, 96) == [10, 1] and lag.lag_groups(40, 32) == [32, 8] and lag.lag_groups(3, 544) == [1, 1, 1]
 
 

@@ -1,0 +1,292 @@
+"""The launch plans of xeofs_amd/csrc/eofx_plans.hpp without a GPU: the header is plain C++, so tests/plans_shim.cpp (extern "C"
+wrappers and nothing else) is compiled with the host C++ compiler and loaded through ctypes (tests/plans_shim.py).
+
+1. The Python restatements that the GPU route tests choose their shapes with (tests/test_gpu_product_routes.py,
+   test_gpu_preprocess_routes.py, test_gpu_lag_routes.py) equal the header's functions -- on the GPU tests' own case lists and
+   on a seeded sweep of a few thousand shapes per rule.  A changed constant in the header fails here instead of silently moving
+   the GPU tests off the routes they exist to cover.
+2. Invariants of the split plans; the block-covariance plan against a numpy brute force; the padded weight vectors of the filter
+   plans against np.pad."""
+import ctypes
+import itertools
+
+import numpy as np
+import pytest
+
+import plans_shim
+import test_gpu_lag_routes as lag
+import test_gpu_preprocess_routes as pr
+import test_gpu_product_routes as routes
+
+PREC_F16X3 = 3          # include/eofx.h
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return plans_shim.lib()
+
+
+# --------------------------------------------------------------------------- #
+# the header's functions as the restatements return them                        #
+# --------------------------------------------------------------------------- #
+def c_tiles(lib, L, wide):
+    w = np.zeros(64, np.int32)
+    k = lib.pl_tiles(L, int(wide), w.ctypes.data)
+    assert k > 0, (L, wide)
+    return ["P96" if t == 96 else t for t in w[:k].tolist()]
+
+
+def c_atb(lib, M, K, L, wide):
+    kps = ctypes.c_int64()
+    return lib.pl_atb_plan(M, K, L, int(wide), ctypes.addressof(kps)), kps.value
+
+
+def c_axb(lib, rows_pad, K):
+    kps = ctypes.c_int64()
+    return lib.pl_axb_plan(rows_pad, K, ctypes.addressof(kps)), kps.value
+
+
+def c_colstats(lib, n, P, aligned=True, ld=None, sample_raw=False, row_map=False):
+    out = np.zeros(5, np.int64)
+    lib.pl_colstats_plan(n, P, ld or P, int(aligned), int(sample_raw), int(row_map), out.ctypes.data)
+    kernel, RS, rps = ("scalar", "vec4", "tr")[out[0]], int(out[1]), int(out[2])
+    return dict(kernel=kernel, RS=RS, rps=rps, last=n - (RS - 1) * rps)
+
+
+def c_apply(lib, n, P, pv, ns, mode, aligned=True):
+    out = np.zeros(5, np.int32)
+    lib.pl_apply_plan(n, P, pv, ns, min(mode, 2), int(mode == 3), 1, int(aligned), out.ctypes.data)
+    raw, masked, in_place, col_map, vec = (bool(x) for x in out)
+    if in_place:
+        return dict(layout="masked" if masked else "in_place", apply=None)
+    return dict(layout="raw" if raw else "written", apply="vec" if vec else "scalar")
+
+
+def c_fit(lib, n, P, l):
+    assert lib.pl_fit_first_eligible(2, PREC_F16X3, 1, n, P, l) == 1
+    L, K = pr._up(l, 32), pr._up(n, routes.ATB_KG)
+    S, kps = c_atb(lib, pr._up(P, routes.ATB_BM), K, L, False)
+    return dict(NB=L // 32, S=S, kps=kps, extra=K - n)
+
+
+def c_lag_groups(lib, E, L):
+    out = np.zeros(max(E, 1), np.int32)
+    k = lib.pl_lag_groups(E, L, out.ctypes.data)
+    return out[:k].tolist()
+
+
+def c_wide(lib, L, prec):
+    return prec == "f16x3" and bool(lib.pl_atb_wide(L))
+
+
+# --------------------------------------------------------------------------- #
+# 1. restatements against the header                                            #
+# --------------------------------------------------------------------------- #
+def test_restated_constants(lib):
+    c = plans_shim.constants(lib)
+    assert (c["ATB_BM"], c["ATB_KG"], c["AXB_BM"], c["AXB_KG"]) == (routes.ATB_BM, routes.ATB_KG, routes.AXB_BM, routes.AXB_KG)
+    assert c["LAG_GROUP_COLS"] == lag.LAG_GROUP_COLS
+
+
+def test_product_restatements_on_the_gpu_case_lists(lib):
+    for L in routes.WIDTHS:
+        for prec in routes.TOL:
+            assert routes.tiles(L, prec) == c_tiles(lib, L, c_wide(lib, L, prec)), (L, prec)
+        for n, p in routes.TMUL_SHAPES:
+            for prec in ("f16x3", "f32"):
+                assert routes.tmul_splits(n, p, L, prec) == c_atb(lib, routes._up(p, 512), routes._up(n, 32), L, c_wide(lib, L, prec))[0]
+        for n, p in routes.MUL_SHAPES:
+            for prec in ("f16x3", "f32"):
+                assert routes.mul_splits(n, p, L, prec) == c_atb(lib, routes._up(n, 512), routes._up(p, 32), L, c_wide(lib, L, prec))[0]
+    for n, p in routes.AXB_SHAPES + [c[:2] for c in lag.CASES + lag.EXTRA_CASES] + [(333, 2100)]:
+        assert routes.in_place_mul_splits(n, p) == c_axb(lib, routes._up(n, 512), routes._up(p, 64))[0], (n, p)
+
+
+def test_product_restatements_on_a_sweep(lib):
+    rng = np.random.default_rng(2024)
+    Ls = list(range(32, 545, 32))
+    Ms = [512, 512 * 1024] + [512 * int(x) for x in rng.integers(1, 300, 40)]
+    Ks = [32] + [32 * int(x) for x in rng.integers(1, 4000, 40)]
+    count = 0
+    for L in Ls:
+        for wide in (False, True):
+            assert routes.tiles(L, "f16x3" if wide else "f32") == c_tiles(lib, L, wide and L >= 96)
+        for M, K in zip(rng.permutation(Ms * 3)[:100], rng.permutation(Ks * 3)[:100]):
+            for wide in (False, True):
+                assert routes.atb_splits(int(M), int(K), L, wide) == c_atb(lib, int(M), int(K), L, wide)[0], (M, K, L, wide)
+                count += 1
+    for M, K in itertools.product([512, 512 * 1024], [32, 64, 40032]):
+        for L in Ls:
+            assert routes.atb_splits(M, K, L, L >= 96) == c_atb(lib, M, K, L, L >= 96)[0]
+    assert count >= 3000
+    rts = [1, 2, 1023, 1024, 1025] + [int(x) for x in rng.integers(1, 1100, 60)]
+    units = [1, 15, 16, 17, 255, 256, 257] + [int(x) for x in rng.integers(1, 20000, 60)]
+    for rt, u in itertools.product(rts, units):
+        assert routes.axb_splits(256 * rt, 64 * u) == c_axb(lib, 256 * rt, 64 * u)[0], (rt, u)
+    assert len(rts) * len(units) >= 3000
+
+
+def _preprocess_calls():
+    """the arguments with which the GPU tests and their host model call the restated statistics plans"""
+    for c in pr.CASES:
+        aligned = c.inp != "misaligned"
+        yield (c.n, c.P, aligned, None, False, False)
+        yield (c.n, c.P, aligned, None, c.hilbert, False)
+        yield (c.n, c.P, True, None, True, False)
+    for c in pr.RESAMPLE_CASES:
+        yield (c.n_rows, c.P, True, pr._up(c.P, 64), False, True)
+    for n in pr.CANCEL_N:
+        yield (n, pr.CANCEL_P, True, None, False, False)
+        yield (n, pr.CANCEL_P - 1, True, None, False, False)
+
+
+def test_statistics_restatements_on_the_gpu_case_lists(lib):
+    for args in _preprocess_calls():
+        assert pr.colstats_plan(*args) == c_colstats(lib, *args), args
+    for c in pr.CASES:
+        aligned = c.inp != "misaligned"
+        pv, ns = c.P - pr.dead_features(c).size, c.n - pr.missing_rows(c).size
+        assert pr.apply_plan(c.n, c.P, pv, ns, c.mode, aligned) == c_apply(lib, c.n, c.P, pv, ns, c.mode, aligned), c.id
+        assert pr.summary_blocks(c.P) == lib.pl_summary_blocks(c.P)
+    for route, n, P, family, mode, *_ in pr.APPLY_CASES:
+        for pv in (P, P - 1, (6 * P + 9) // 10, P // 2):
+            assert pr.apply_plan(n, P, pv, n, mode) == c_apply(lib, n, P, pv, n, mode), (route, pv)
+    for c in pr.FIT_CASES:
+        assert pr.fit_plan(c.n, c.P, c.k + c.over) == c_fit(lib, c.n, c.P, c.k + c.over), c.id
+    for n, P in zip(pr.CANCEL_FUSED_N, (128, 5004)):
+        assert pr.fit_plan(n, P, 16) == c_fit(lib, n, P, 16)
+
+
+def test_statistics_restatements_on_a_sweep(lib):
+    rng = np.random.default_rng(7)
+    ns = [1, 2, 63, 64, 65, 127, 128, 8192, 8193] + [int(x) for x in rng.integers(1, 70000, 40)]
+    Ps = [1, 3, 4, 5, 1023, 1024, 1025, 4096, 4097] + [int(x) for x in rng.integers(1, 600000, 40)]
+    count = 0
+    for n, P in itertools.product(ns, Ps):
+        for aligned, pad, sample_raw, row_map in ((True, 0, False, False), (False, 0, False, False), (True, 0, True, False),
+                                                  (True, 3, False, True), (True, 64, True, True)):
+            args = (n, P, aligned, P + pad if pad else None, sample_raw, row_map)
+            assert pr.colstats_plan(*args) == c_colstats(lib, *args), args
+            count += 1
+        assert pr.summary_blocks(P) == lib.pl_summary_blocks(P)
+        for mode, aligned in itertools.product(range(4), (True, False)):
+            for pv, ns_ in ((P, n), (P, max(n - 1, 1)), (max(P - 1, 1), n), ((6 * P + 9) // 10, n), (max((6 * P - 1) // 10, 1), n),
+                            (min(n, P), n), (min(n + 1, P), n)):
+                assert pr.apply_plan(n, P, pv, ns_, mode, aligned) == c_apply(lib, n, P, pv, ns_, mode, aligned), (n, P, pv, ns_, mode, aligned)
+    assert count >= 3000
+    fits = 0
+    for n, P4, l in zip(rng.integers(3, 20000, 4000), rng.integers(1, 40000, 4000), rng.integers(1, 64, 4000)):
+        n, P, l = int(n), 4 * int(P4), int(l)
+        if n < P and l < n and l % 32:
+            assert pr.fit_plan(n, P, l) == c_fit(lib, n, P, l), (n, P, l)
+            fits += 1
+    assert fits >= 1000
+
+
+def test_lag_restatements(lib):
+    """the grouping rule of the lag operator and the shape part of tmul_nt_ok, on the GPU case list and on a sweep (this is what
+    test_lag_model_host.py::test_restated_constants_match_the_source stands on)"""
+    for n, p, E, tau, L in lag.CASES + lag.EXTRA_CASES:
+        assert lag.lag_groupsize(E, L) == lib.pl_lag_groupsize(E, L)
+        assert lag.lag_groups(E, L) == c_lag_groups(lib, E, L)
+        for g in lag.lag_groups(E, L):
+            assert lag.tmul_nt_ok(n, g * L) == bool(lib.pl_tmul_nt_ok(n, lag._up(p, 512), 1, g * L))
+    count = 0
+    for E, L in itertools.product(list(range(1, 70)) + [100, 1000], list(range(32, 545, 32)) + [1024, 2048]):
+        assert lag.lag_groupsize(E, L) == lib.pl_lag_groupsize(E, L) and lag.lag_groups(E, L) == c_lag_groups(lib, E, L), (E, L)
+        count += 1
+    rng = np.random.default_rng(3)
+    for n, Lw in itertools.product([511, 512, 513] + [int(x) for x in rng.integers(2, 40000, 60)], [480, 511, 512, 513, 544, 1024]):
+        assert lag.tmul_nt_ok(n, Lw) == bool(lib.pl_tmul_nt_ok(n, 2560, 1, Lw)), (n, Lw)
+        count += 1
+    assert count >= 1500
+    assert not lib.pl_tmul_nt_ok(1037, 2560, 0, 512)            # (no layout the route can read)
+
+
+# --------------------------------------------------------------------------- #
+# 2. invariants, the block-covariance plan, the filter plans                    #
+# --------------------------------------------------------------------------- #
+def test_split_plan_invariants(lib):
+    """S * kps >= K, (S - 1) * kps < K (no empty split) and kps a multiple of the granularity"""
+    rng = np.random.default_rng(11)
+    for L in range(32, 545, 32):
+        for M, K in zip([512, 512 * 1024] + [512 * int(x) for x in rng.integers(1, 300, 30)],
+                        [32, 32] + [32 * int(x) for x in rng.integers(1, 4000, 30)]):
+            for wide in (False, True):
+                S, kps = c_atb(lib, M, K, L, wide)
+                assert 1 <= S <= 128 and S * kps >= K and (S - 1) * kps < K and kps % routes.ATB_KG == 0, (M, K, L, wide, S, kps)
+    for rt, u in itertools.product([1, 2, 40, 1023, 1024], [1, 15, 16, 17, 100, 255, 256, 257, 5000, 16200]):
+        S, kps = c_axb(lib, 256 * rt, 64 * u)
+        assert S >= 1 and S * kps >= 64 * u and (S - 1) * kps < 64 * u and kps % routes.AXB_KG == 0, (rt, u, S, kps)
+        assert S == 1 or (rt < 1024 and u >= 16)
+
+
+def _viewcov(lib, n, p, off, keep_diag):
+    view, tiles, out3 = np.zeros(p, np.int32), np.zeros((33 * 17, 2), np.int32), np.zeros(3, np.int64)
+    off = np.asarray(off, np.int32)
+    k = lib.pl_viewcov_plan(n, p, off.ctypes.data, len(off) - 1, int(keep_diag), view.ctypes.data, tiles.ctypes.data, len(tiles),
+                            out3.ctypes.data)
+    return k, view, tiles[:max(k, 0)], out3
+
+
+def _view_offsets(p, m, T):
+    """m views over p columns: one boundary exactly on a tile edge and one inside a tile where p and m leave room"""
+    if m == 1:
+        return [[0, p]]
+    if m > p:
+        return []
+    rng = np.random.default_rng(p + m)
+    outs = []
+    for forced in ([T] if p > T else [], [T // 2 + 1] if p > T // 2 + 1 else [], [T, T + T // 2 + 1] if p > 2 * T else []):
+        forced = forced[:m - 1]
+        rest = [c for c in rng.permutation(np.arange(1, p)).tolist() if c not in forced][:m - 1 - len(forced)]
+        outs.append([0] + sorted(forced + rest) + [p])
+    return outs
+
+
+@pytest.mark.parametrize("p", [1, 127, 128, 129, 300, 4096])
+def test_block_covariance_plan(lib, p):
+    """Against a numpy brute force over all p x p entries: a 128-tile (bi, bj), bi <= bj, is listed iff it holds an entry (i, j)
+    with i <= j and (keep_diag or different views), in row-major order.  No split of the samples is empty, and the partial
+    blocks of a split run stay within VIEWCOV_WGS: G * ntiles <= VIEWCOV_WGS wherever the samples are split at all (p = 4096 with
+    every tile wanted has 528 tiles, more than VIEWCOV_WGS: there G = 1 and no partial block exists)."""
+    c = plans_shim.constants(lib)
+    T, WGS = c["VIEWCOV_T"], c["VIEWCOV_WGS"]
+    nb = (p + T - 1) // T
+    for m in (1, 2, 5, 64):
+        for off in _view_offsets(p, m, T):
+            v = np.repeat(np.arange(m), np.diff(off))
+            differ = v[:, None] != v[None, :]
+            for keep_diag in (False, True):
+                wanted = np.triu(differ | keep_diag)
+                brute = [(bi, bj) for bi in range(nb) for bj in range(bi, nb) if wanted[bi * T:(bi + 1) * T, bj * T:(bj + 1) * T].any()]
+                for n in (2, 4095, 4096, 100000):
+                    k, view, tiles, (G, chunk, nslabs) = _viewcov(lib, n, p, off, keep_diag)
+                    assert k >= 0 and np.array_equal(view, v)
+                    assert [tuple(t) for t in tiles.tolist()] == brute, (p, off, keep_diag)
+                    assert nslabs == (n + 15) // 16 and G >= 1 and chunk * G >= nslabs and chunk * (G - 1) < nslabs
+                    assert G == 1 or G * k <= WGS
+                    assert G > 1 or k == 0 or WGS // k < 2 or nslabs // 16 < 2      # (a split wherever the rule allows two)
+    assert _viewcov(lib, 500, p, [0, p + 1], True)[0] == -1 and _viewcov(lib, 500, p, [1, p], True)[0] == -1       # the ends of off
+    if p > 2:
+        assert _viewcov(lib, 500, p, [0, 2, 2, p], True)[0] == -2 and _viewcov(lib, 500, p, [0, 2, 1, p], True)[0] == -2
+
+
+@pytest.mark.parametrize("ntau", [1, 65, 66])
+def test_lag_covariance_weights(lib, ntau):
+    c = plans_shim.constants(lib)
+    w = np.random.default_rng(ntau).standard_normal(ntau)
+    out, nyG = np.full(ntau + 2 * c["LAGCOV_PADW"] + 3, 7.0), np.zeros(2, np.int32)
+    k = lib.pl_lagcov_plan(700, 130, w.ctypes.data, ntau, out.ctypes.data, nyG.ctypes.data)
+    assert c["LAGCOV_PADW"] == 15 and k == ntau + 30 and np.array_equal(out[:k], np.pad(w, 15)) and np.all(out[k:] == 7.0)
+    assert nyG.tolist() == [3, 11]          # 3 column blocks of 64 in groups of 4: 3 tile pairs; min(11 row tiles, 512 // 3)
+
+
+@pytest.mark.parametrize("h", [0, 1, 40])
+def test_low_pass_weights(lib, h):
+    c = plans_shim.constants(lib)
+    w = np.random.default_rng(h).standard_normal(h + 1)
+    out, nyG = np.full(2 * h + 1 + 2 * c["LOWPASS_PADW"] + 3, 7.0), np.zeros(2, np.int32)
+    k = lib.pl_lowpass_plan(700, 130, w.ctypes.data, h, out.ctypes.data, nyG.ctypes.data)
+    assert c["LOWPASS_PADW"] == 15 and k == 2 * h + 31 and np.array_equal(out[:k], np.pad(np.concatenate([w[:0:-1], w]), 15))
+    assert np.all(out[k:] == 7.0) and nyG.tolist() == [6, 11]       # 3 (3 + 1) / 2 tile pairs; min(11 row tiles, 512 // 6)

@@ -17,13 +17,14 @@
 #include "eofx_pcmul.hpp"
 #include "eofx_viewcov.hpp"
 #include "eofx_lrfill.hpp"
+#include "eofx_plans.hpp"
+#include "eofx_sketch.hpp"
+#include "eofx_hilbert_host.hpp"
+#include "eofx_gwplan.hpp"
 #ifndef EOFX_AXB_DMA_DEFAULT
 #define EOFX_AXB_DMA_DEFAULT 1
 #endif
 
-#if !defined(__HIP_DEVICE_COMPILE__)
-#include <immintrin.h>
-#endif
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -218,7 +219,6 @@ static int set_err(eofx_ctx* ctx, int code, const char* fmt, ...) {
   } while (0)
 #define KCHK() HIPCHK(hipGetLastError())
 
-static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 static bool is_device_ptr(const void* p) {
   if (!p) return false;
@@ -537,78 +537,6 @@ extern "C" int eofx_host_eigh_f64(const double* Ain, int n, double* w, double* V
 // ------------------------------------------------------------------------------------
 // kernel launchers
 // ------------------------------------------------------------------------------------
-struct AtbPlan {
-  int S;
-  int64_t kps;
-};
-// split-K factor from a small cost model: 512 resident workgroups, ~10 GB/s of A per
-// workgroup slot, partial-sum traffic at ~4 TB/s.
-// 128-column tiles (atb_f16_kernel<4>, one workgroup per CU): the wide products (Gram matrices, PCA panels) and the
-// two-matrix form of a 128-column complex panel (33-64 complex columns: Re and Im are then streamed ONCE per pass)
-// (round 3: also the single-matrix passes of sketches of 65 columns and more -- EOF with 55+ modes: one 128-column launch at
-// 4.3 TB/s beats two 64-column launches at 6.5 TB/s: 229.7 -> 205.6 ms per rSVD at k = 100, config-4 size)
-static bool atb_wide(int L, bool two_matrix = false) {
-  (void)two_matrix;
-  if (const char* ev = std::getenv("EOFX_ATB_WIDE_MIN")) return L >= atoi(ev);   // tuning hook (tools/wide_sketch_probe.py)
-  return L >= 96;       // (96 columns: one partial 128-column tile, see launch_atb)
-}
-static AtbPlan atb_plan(int64_t M, int64_t K, int L, bool wide = false) {
-  const int bx = (int)(M / ATB_BM);
-  const int bz = wide ? (L + 127) / 128 : (L + 63) / 64;
-  const double resident = wide ? 256.0 : 512.0;
-  AtbPlan best{1, K};
-  double best_t = 1e30;
-  for (int S = 1; S <= 128; ++S) {
-    const int64_t kps = round_up((K + S - 1) / S, ATB_KG);
-    const int s_eff = (int)((K + kps - 1) / kps);
-    if (s_eff != S) continue;
-    const double blocks = (double)bx * bz * s_eff;
-    const double rounds = std::ceil(blocks / resident);
-    double t = rounds * (double)kps * 2048.0 / 1.0e10;
-    if (s_eff > 1) t += (2.0 * s_eff + 1.0) * (double)M * L * 4.0 / 4.0e12;
-    if (t < best_t * 0.98) {
-      best_t = t;
-      best = {s_eff, kps};
-    }
-  }
-  return best;
-}
-// axb_f16_kernel (the in-place sample-side product): rows_pad / 256 row tiles x S feature splits.  S = 1 when the row
-// tiles alone fill the chip, otherwise a multiple of 8 (one split per XCD at a time) from the same kind of cost model.
-static AtbPlan axb_plan(int64_t rows_pad, int64_t K) {
-  const int64_t rt = rows_pad / AXB_BM;
-  const int64_t units = K / AXB_KG;
-  if (rt >= 1024 || units < 16) return {1, K};
-  if (const char* ev = std::getenv("EOFX_AXB_SPLITS")) {   // tuning hook (tools/atb_probe.py)
-    const int want = std::max(8, atoi(ev) / 8 * 8);
-    const int64_t kps = round_up((units + want - 1) / want, 1) * AXB_KG;
-    return {(int)((K + kps - 1) / kps), kps};
-  }
-  AtbPlan best{1, K};
-  double best_t = 1e30;
-  for (int s8 = 1; s8 <= 32 && 8 * s8 <= units; ++s8) {
-    const int S = 8 * s8;
-    const int64_t kps = (units + S - 1) / S * AXB_KG;
-    const int s_eff = (int)((K + kps - 1) / kps);
-    if (s_eff > S || s_eff <= S - 8) continue;
-    const double rounds = std::ceil((double)rt * s8 / 64.0);          // 64 resident workgroups per XCD
-    double t = rounds * (double)kps * 1024.0 / 1.25e10;               // 256 rows x 4 B per feature, ~12.5 GB/s per slot
-    t += (2.0 * s_eff + 1.0) * (double)rows_pad * 64.0 * 4.0 / 4.0e12;
-    if (t < best_t * 0.98) {
-      best_t = t;
-      best = {s_eff, kps};
-    }
-  }
-  return best;
-}
-static size_t atb_scratch_bytes(int64_t M, int64_t K, int L) {
-  const AtbPlan pl = atb_plan(M, K, L), plw = atb_plan(M, K, L, true);
-  const int smax = std::max(pl.S, atb_wide(L, true) ? plw.S : 1);
-  size_t b = smax > 1 ? (size_t)smax * M * L * (sizeof(float) + sizeof(double)) + 4096 : 4096;   // f32 or f64 partials
-  const AtbPlan px = axb_plan(M, round_up(K, AXB_KG));      // in case M is the sample side of an in-place matrix
-  if (px.S > 1) b = std::max(b, (size_t)px.S * M * round_up(L, 64) * sizeof(float) + 4096);
-  return b;
-}
 
 // C[M x L] = A[K x M]^T B[K x L]; M multiple of 512, K multiple of 16, L multiple of 32.
 // raw view of A (atb_f16_kernel<NB, true>): the raw field with the affine preprocessing map applied on the fly
@@ -664,14 +592,9 @@ static int launch_atb(eofx_ctx* ctx, const float* A, int64_t lda, int64_t K, int
                    (long long)K, L);
   const int bx = (int)(M / ATB_BM);
   // wide products (Gram matrices, PCA panels) in 128-column tiles of the split-fp16 kernel, then 64 / 32-column rests
-  const bool wide = atb_wide(L, A2 != nullptr) && prec == EOFX_PREC_F16X3;
+  const bool wide = atb_wide(L) && prec == EOFX_PREC_F16X3;
   if (sym && !(wide && !aff && L == M)) sym = 0;
-  // wide panels: full 128-column tiles, then -- when 96 columns are left (panels of 96 / 224 columns) -- ONE partial wide tile
-  // instead of a 64- and a 32-column launch (each launch reads the field once)
-  const int n4 = wide ? L / 128 : 0;
-  const int part4 = (wide && L - 128 * n4 == 96) ? 96 : 0;
-  const int cb4 = 128 * n4 + part4;
-  const int nfull = (L - cb4) / 64, rem = (L - cb4) % 64;
+  const ColTiles tiles = atb_tiles(L, wide);
   const AtbPlan plan = atb_plan(M, K, L, wide);
   int best_s = plan.S;
   int64_t best_kps = plan.kps;
@@ -721,21 +644,21 @@ static int launch_atb(eofx_ctx* ctx, const float* A, int64_t lda, int64_t K, int
       outd = arena_alloc<double>(ctx, (size_t)best_s * M * L);
       if (!outd) return set_err(ctx, EOFX_ERR_NOMEM, "arena exhausted (float64 partials)");
     }
-    if (nfull > 0) {
-      hipLaunchKernelGGL(atb_f64_kernel<2>, dim3(bx, best_s, nfull), dim3(512), 0, ctx->stream, A, lda, B, ldb, C, outd, L, M, K,
-                         best_kps, 0);
-      KCHK();
-    }
-    if (rem) {
-      hipLaunchKernelGGL(atb_f64_kernel<1>, dim3(bx, best_s, 1), dim3(512), 0, ctx->stream, A, lda, B, ldb, C, outd, L, M, K,
-                         best_kps, nfull * 64);
+    for (int i = 0; i < tiles.n; ++i) {      // (not wide: 64-column tiles and one of 32)
+      const ColTile& t = tiles.t[i];
+      if (t.width == 64)
+        hipLaunchKernelGGL(atb_f64_kernel<2>, dim3(bx, best_s, t.count), dim3(512), 0, ctx->stream, A, lda, B, ldb, C, outd, L, M, K,
+                           best_kps, t.col_base);
+      else
+        hipLaunchKernelGGL(atb_f64_kernel<1>, dim3(bx, best_s, t.count), dim3(512), 0, ctx->stream, A, lda, B, ldb, C, outd, L, M, K,
+                           best_kps, t.col_base);
       KCHK();
     }
     if (ctx->profile) {
       HIPCHK(hipEventRecord(ev1, ctx->stream));
       ctx->prof_events.emplace_back(ev0, ev1);
       ctx->prof_flops += 2.0 * (double)K * (double)M * (double)L;
-      ctx->prof_bytes += (double)K * (double)M * 4.0 * (nfull + (rem ? 1 : 0));
+      ctx->prof_bytes += (double)K * (double)M * 4.0 * tiles.columns();
     }
     if (outd) {
       const int64_t count = M * L;
@@ -746,32 +669,25 @@ static int launch_atb(eofx_ctx* ctx, const float* A, int64_t lda, int64_t K, int
     return EOFX_OK;
   }
   unsigned* amax_direct = best_s == 1 ? amax_out : nullptr;   // single split: the kernels' own epilogues take the maximum
-  if (n4 > 0) {
-    dim3 grid(bx, best_s, n4);
-    launch_atb_variant<4>(prec, grid, ctx->stream, A, lda, B, ldb, out, L, M, K, best_kps, 0, a_scale, b_absmax_dev, aff, A2, B2, s_half, sym, amax_direct);
-    KCHK();
-  }
-  if (part4) {
-    dim3 grid(bx, best_s, 1);
-    launch_atb_variant<4>(prec, grid, ctx->stream, A, lda, B, ldb, out, L, M, K, best_kps, 128 * n4, a_scale, b_absmax_dev, aff, A2, B2, s_half, sym,
-                          amax_direct, part4);
-    KCHK();
-  }
-  if (nfull > 0) {
-    dim3 grid(bx, best_s, nfull);
-    launch_atb_variant<2>(prec, grid, ctx->stream, A, lda, B, ldb, out, L, M, K, best_kps, cb4, a_scale, b_absmax_dev, aff, A2, B2, s_half, sym, amax_direct);
-    KCHK();
-  }
-  if (rem) {
-    dim3 grid(bx, best_s, 1);
-    launch_atb_variant<1>(prec, grid, ctx->stream, A, lda, B, ldb, out, L, M, K, best_kps, cb4 + nfull * 64, a_scale, b_absmax_dev, aff, A2, B2, s_half, sym, amax_direct);
+  for (int i = 0; i < tiles.n; ++i) {
+    const ColTile& t = tiles.t[i];
+    const dim3 grid(bx, best_s, t.count);
+    if (t.width >= 96)       // a 128-column tile, or the partial one with 96 valid columns
+      launch_atb_variant<4>(prec, grid, ctx->stream, A, lda, B, ldb, out, L, M, K, best_kps, t.col_base, a_scale, b_absmax_dev, aff, A2, B2, s_half,
+                            sym, amax_direct, t.width);
+    else if (t.width == 64)
+      launch_atb_variant<2>(prec, grid, ctx->stream, A, lda, B, ldb, out, L, M, K, best_kps, t.col_base, a_scale, b_absmax_dev, aff, A2, B2, s_half,
+                            sym, amax_direct);
+    else
+      launch_atb_variant<1>(prec, grid, ctx->stream, A, lda, B, ldb, out, L, M, K, best_kps, t.col_base, a_scale, b_absmax_dev, aff, A2, B2, s_half,
+                            sym, amax_direct);
     KCHK();
   }
   if (ctx->profile) {
     HIPCHK(hipEventRecord(ev1, ctx->stream));
     ctx->prof_events.emplace_back(ev0, ev1);
     ctx->prof_flops += 2.0 * (double)K * (double)M * (double)L * (A2 ? 2 : 1);
-    ctx->prof_bytes += (double)K * (double)M * 4.0 * (n4 + (part4 ? 1 : 0) + nfull + (rem ? 1 : 0)) * (A2 ? 2 : 1);
+    ctx->prof_bytes += (double)K * (double)M * 4.0 * tiles.columns() * (A2 ? 2 : 1);
   }
   if (best_s > 1) {
     const int64_t count4 = M * L / 4;
@@ -807,7 +723,7 @@ static int launch_axb(eofx_ctx* ctx, const float* raw, int64_t ld, int64_t rows,
     return set_err(ctx, EOFX_ERR_ARG, "axb: bad geometry rows=%lld cols=%lld L=%d", (long long)rows, (long long)cols, L);
   const AtbPlan plan = axb_plan(rows_pad, K);
   const int rt = (int)(rows_pad / AXB_BM);
-  const int nfull = L / 64, rem = L % 64;
+  const ColTiles tiles = atb_tiles(L, false);
   ArenaScope scope(ctx);
   float* out = W;
   if (plan.S > 1) {
@@ -847,7 +763,7 @@ static int launch_axb(eofx_ctx* ctx, const float* raw, int64_t ld, int64_t rows,
   // about 16 GB of field per pass on (config 4 and 5; measured on one box each: 10000 x 1 036 800 -2.8 %, 10000 x 129 600
   // +0.9 %, 5000 x 259 200 +4.4 %, profiles/r04_axb_dma_ab.txt)
   bool dma = ctx->axb_dma == 2 || (ctx->axb_dma == 1 && (double)rows_pad * (double)K_all >= 4.0e9);
-  const int ncb = nfull + (rem ? 1 : 0);
+  const int ncb = tiles.columns();
   if (dma) {            // the panel's fp16 planes: one grow-only buffer per context (K_all x 64 ncb x 4 bytes)
     const size_t need = (size_t)ncb * (size_t)(K_all / AXB_KG) * AXB_PAIR_BYTES;
     if (ctx->axb_planes_bytes < need) {
@@ -864,54 +780,41 @@ static int launch_axb(eofx_ctx* ctx, const float* raw, int64_t ld, int64_t rows,
       }
     }
   }
+  const int64_t pairs_all = K_all / AXB_KG;
   if (dma) {   // the B panel as fp16 planes, moved by LDS-DMA (eofx_axb_dma.hpp); same bits in W
     hipLaunchKernelGGL(axb_bsplit_kernel, dim3((unsigned)((K_all + 31) / 32), ncb), dim3(256), 0, ctx->stream, Y, L, L, K_all, bmax,
                        ctx->axb_planes);
     KCHK();
-    const int64_t pairs_all = K_all / AXB_KG;
-    if (nfull > 0) {
-      if (masked)
-        hipLaunchKernelGGL((axb_f16_dma_kernel<4, 0, true>), dim3(gx, nfull), dim3(256), 0, ctx->stream, raw, ld, (int)rows, cols, aff,
-                           aff_ld, ctx->axb_planes, pairs_all, out, L, rows_pad, K, plan.kps, plan.S, rt, 0, a_scale, bmax, act);
-      else
-        hipLaunchKernelGGL((axb_f16_dma_kernel<4, 0, false>), dim3(gx, nfull), dim3(256), 0, ctx->stream, raw, ld, (int)rows, cols, aff,
-                           aff_ld, ctx->axb_planes, pairs_all, out, L, rows_pad, K, plan.kps, plan.S, rt, 0, a_scale, bmax,
-                           (const int*)nullptr);
-      KCHK();
-    }
-    if (rem) {
-      if (masked)
-        hipLaunchKernelGGL((axb_f16_dma_kernel<2, 0, true>), dim3(gx, 1), dim3(256), 0, ctx->stream, raw, ld, (int)rows, cols, aff,
-                           aff_ld, ctx->axb_planes, pairs_all, out, L, rows_pad, K, plan.kps, plan.S, rt, nfull * 64, a_scale, bmax, act);
-      else
-        hipLaunchKernelGGL((axb_f16_dma_kernel<2, 0, false>), dim3(gx, 1), dim3(256), 0, ctx->stream, raw, ld, (int)rows, cols, aff,
-                           aff_ld, ctx->axb_planes, pairs_all, out, L, rows_pad, K, plan.kps, plan.S, rt, nfull * 64, a_scale, bmax,
-                           (const int*)nullptr);
-      KCHK();
-    }
-  } else if (nfull > 0) {
-    if (masked)
-      hipLaunchKernelGGL((axb_f16_kernel<4, 0, true>), dim3(gx, nfull), dim3(256), 0, ctx->stream, raw, ld, (int)rows, cols, aff, aff_ld, Y,
-                         L, out, L, rows_pad, K, plan.kps, plan.S, rt, 0, a_scale, bmax, act);
-    else
-      hipLaunchKernelGGL(axb_f16_kernel<4>, dim3(gx, nfull), dim3(256), 0, ctx->stream, raw, ld, (int)rows, cols, aff, aff_ld, Y, L, out,
-                         L, rows_pad, K, plan.kps, plan.S, rt, 0, a_scale, bmax);
-    KCHK();
   }
-  if (!dma && rem) {
-    if (masked)
-      hipLaunchKernelGGL((axb_f16_kernel<2, 0, true>), dim3(gx, 1), dim3(256), 0, ctx->stream, raw, ld, (int)rows, cols, aff, aff_ld, Y, L,
-                         out, L, rows_pad, K, plan.kps, plan.S, rt, nfull * 64, a_scale, bmax, act);
-    else
-      hipLaunchKernelGGL(axb_f16_kernel<2>, dim3(gx, 1), dim3(256), 0, ctx->stream, raw, ld, (int)rows, cols, aff, aff_ld, Y, L, out,
-                         L, rows_pad, K, plan.kps, plan.S, rt, nfull * 64, a_scale, bmax);
+  const int* const no_act = nullptr;
+  for (int i = 0; i < tiles.n; ++i) {      // 64-column tiles (NB = 4), then one of 32 (NB = 2)
+    const ColTile& t = tiles.t[i];
+    const dim3 grid(gx, t.count);
+#define EOFX_AXB_ARGS(B, LDB) \
+  grid, dim3(256), 0, ctx->stream, raw, ld, (int)rows, cols, aff, aff_ld, B, LDB, out, L, rows_pad, K, plan.kps, plan.S, rt, t.col_base, a_scale, bmax
+    if (dma) {
+      if (t.width == 64) {
+        if (masked) hipLaunchKernelGGL((axb_f16_dma_kernel<4, 0, true>), EOFX_AXB_ARGS(ctx->axb_planes, pairs_all), act);
+        else hipLaunchKernelGGL((axb_f16_dma_kernel<4, 0, false>), EOFX_AXB_ARGS(ctx->axb_planes, pairs_all), no_act);
+      } else {
+        if (masked) hipLaunchKernelGGL((axb_f16_dma_kernel<2, 0, true>), EOFX_AXB_ARGS(ctx->axb_planes, pairs_all), act);
+        else hipLaunchKernelGGL((axb_f16_dma_kernel<2, 0, false>), EOFX_AXB_ARGS(ctx->axb_planes, pairs_all), no_act);
+      }
+    } else if (t.width == 64) {
+      if (masked) hipLaunchKernelGGL((axb_f16_kernel<4, 0, true>), EOFX_AXB_ARGS(Y, L), act);
+      else hipLaunchKernelGGL(axb_f16_kernel<4>, EOFX_AXB_ARGS(Y, L));
+    } else {
+      if (masked) hipLaunchKernelGGL((axb_f16_kernel<2, 0, true>), EOFX_AXB_ARGS(Y, L), act);
+      else hipLaunchKernelGGL(axb_f16_kernel<2>, EOFX_AXB_ARGS(Y, L));
+    }
+#undef EOFX_AXB_ARGS
     KCHK();
   }
   if (ctx->profile) {
     HIPCHK(hipEventRecord(ev1, ctx->stream));
     ctx->prof_events.emplace_back(ev0, ev1, 1);
     ctx->prof_flops += 2.0 * (double)K * (double)rows_pad * (double)L;
-    ctx->prof_bytes += (double)K * (double)rows * 4.0 * (nfull + (rem ? 1 : 0));
+    ctx->prof_bytes += (double)K * (double)rows * 4.0 * tiles.columns();
   }
   if (plan.S > 1) {
     const int64_t count4 = rows_pad * L / 4;
@@ -920,20 +823,6 @@ static int launch_axb(eofx_ctx* ctx, const float* raw, int64_t ld, int64_t rows,
     KCHK();
   }
   return EOFX_OK;
-}
-
-// number of row-strided partial Gram matrices: >= 4 slabs of 32 rows per workgroup for the narrow
-// (sketch-width) panels; wide panels already expose (L/64)^2 sub-blocks, so fewer partials (<= 64 MB)
-static int gram_parts(int64_t rows, int L) {
-  // workgroups along the rows; every workgroup writes one partial (L x L float64):
-  // >= 8 k-steps (32 rows) per wave, <= 128 MB of partials (a 130 000 x 1536 panel, 300 sub-blocks: 3 row parts 8.9 ms,
-  // 6 .. 24 parts 7.1 ms -- tools/wide_small_probe.py)
-  // (one workgroup per CU: the products run at the fp64 MFMA rate either way -- ~45 TFLOP/s here -- and every further
-  // partial is 8 L^2 bytes written and read again: 194 / 210 / 243 us for 256 / 512 / 1024 partials of a 1M x 64 panel)
-  const int64_t by_rows = std::min<int64_t>((rows + 127) / 128, 256);
-  const int64_t by_mem = ((int64_t)128 << 20) / ((int64_t)L * L * 8);
-  if (const char* ev = std::getenv("EOFX_GRAM_PARTS")) return std::max(1, atoi(ev));   // tuning hook (tools/small_kernel_probe.py)
-  return (int)std::max<int64_t>(1, std::min(by_rows, std::max<int64_t>(by_mem, 1)));
 }
 
 static int launch_gram(eofx_ctx* ctx, const float* P, int64_t rows, int L, double* G) {
@@ -1001,7 +890,6 @@ static int launch_xgram(eofx_ctx* ctx, const float* Pa, int64_t lda, int La, con
 // out = P R^-1 with G = R^T R (leading l x l block)
 static int launch_rinv(eofx_ctx* ctx, const double* G, int L, int l, double* Rinv);
 static size_t rinv_blocked_bytes(int l);
-static bool matmul_nt_ok(int64_t rows, int L, int Lo);
 static size_t matmul_nt_scratch(eofx_ctx* ctx, int64_t rows, int L, int Lo);
 static int launch_matmul_nt(eofx_ctx* ctx, const float* P, int64_t rows, int L, const double* Mx, int Lo, float* out);
 static int launch_cholqr(eofx_ctx* ctx, const float* P, int64_t rows, int L, int l, const double* G,
@@ -1241,7 +1129,7 @@ static int launch_apply(eofx_ctx* ctx, const float* Xsrc, int64_t ld_src, const 
                         const int64_t* col_map, const double* shift, const double* scale, eofx_mat* m,
                         int* nan_flag, const unsigned* absmax_src = nullptr) {
   dim3 grid((int)(m->p_pad / 64), (int)(m->n_pad / 64));
-  const bool vec = !col_map && (ld_src % 4 == 0) && ((uintptr_t)Xsrc % 16 == 0);
+  const bool vec = apply_vec(col_map != nullptr, ld_src, (uintptr_t)Xsrc % 16 == 0);
   if (vec)
     hipLaunchKernelGGL(apply_kernel<true>, grid, dim3(256), 0, ctx->stream, Xsrc, ld_src, row_map, col_map,
                        shift, scale, m->n, m->p, m->X, m->p_pad, m->Xt, m->n_pad, nan_flag, (const float*)nullptr, (int64_t)0);
@@ -1424,14 +1312,10 @@ struct PreState {  // device arrays of length P
 static int run_colstats(eofx_ctx* ctx, const float* Xd, int64_t n, int64_t P, int center, int standardize,
                         const double* w_dev, PreState& ps, int64_t ld = 0, const int64_t* row_map = nullptr) {
   if (ld == 0) ld = P;
-  const bool vec4 = P % 4 == 0 && ld % 4 == 0 && ((uintptr_t)Xd % 16) == 0;     // four features per thread, 16-byte loads
-  const int gxs = (int)((P + 255) / 256);                    // workgroups of the finalize kernel (one thread per feature)
-  const int gx = vec4 ? (int)((P / 4 + 255) / 256) : gxs;
-  int64_t RS = std::max<int64_t>(1, (2048 + gx - 1) / gx);
-  RS = std::min<int64_t>(RS, std::max<int64_t>(1, n / 64));
-  int64_t rps = (n + RS - 1) / RS;
-  if (ctx->want_rawT && ctx->keep_raw == 2 && !row_map) rps = round_up(rps, 64);   // (the transposing variant moves 64 x 64 tiles)
-  RS = (n + rps - 1) / rps;
+  const ColstatsPlan pl = colstats_plan(n, P, ld, ((uintptr_t)Xd % 16) == 0, ctx->want_rawT && ctx->keep_raw == 2, row_map != nullptr);
+  const bool vec4 = pl.vec4;
+  const int gxs = pl.gxs, gx = pl.gx;
+  const int64_t RS = pl.RS, rps = pl.rps;
   ArenaScope scope(ctx);
   ARENA(int, cnt_p, (size_t)RS * P);
   ARENA(double, sum_p, (size_t)RS * P);
@@ -1439,9 +1323,7 @@ static int run_colstats(eofx_ctx* ctx, const float* Xd, int64_t n, int64_t P, in
   ARENA(float, mn_p, (size_t)RS * P);
   ARENA(float, mx_p, (size_t)RS * P);
   ARENA(float, csh, (size_t)round_up(P, 4));   // provisional shift of the sums (colstats_shift_kernel)
-  // the Hilbert stage follows (eofx_ctx_set_sample_raw) and its one-kernel route takes this length two features at a time:
-  // the pass also writes the raw field in the sample-contiguous layout (instead of a separate transposing copy behind the statistics pass)
-  if (vec4 && !row_map && ctx->want_rawT && ctx->keep_raw == 2 && !ctx->pending_rawT && round_up(n, ATB_BM) <= 8192 && rps % 64 == 0) {
+  if (pl.tr && !ctx->pending_rawT) {     // the pass also writes the raw field in the sample-contiguous layout
     const int64_t n_pad_t = round_up(n, ATB_BM), p_pad_t = round_up(P, ATB_BM);
     const size_t tb = (size_t)n_pad_t * p_pad_t * sizeof(float);
     if (pool_malloc(ctx, (void**)&ctx->pending_rawT, tb) == hipSuccess) ctx->pending_rawT_bytes = tb;
@@ -1476,7 +1358,7 @@ struct FeatSummary {
   double tv = 0.0;     // total variance of the transformed valid features (ddof = 1)
 };
 static int run_feature_summary(eofx_ctx* ctx, const PreState& ps, int64_t P, FeatSummary& fs) {
-  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((P + 4095) / 4096, 256));
+  const int nb = summary_blocks(P);
   ArenaScope scope(ctx);
   ARENA(double, tvp, nb);
   ARENA(int, ip, 3 * nb);
@@ -1498,12 +1380,6 @@ static int run_feature_summary(eofx_ctx* ctx, const PreState& ps, int64_t P, Fea
   return EOFX_OK;
 }
 
-static size_t colstats_scratch(int64_t n, int64_t P) {
-  const int64_t gx = std::max<int64_t>(1, (P / 4 + 255) / 256);   // the four-features-per-thread kernel: fewer workgroups, more row splits
-  int64_t RS = std::max<int64_t>(1, (2048 + gx - 1) / gx);      // (fewer than four features: gx was 0 -- a division by zero, round 5)
-  RS = std::min<int64_t>(RS, std::max<int64_t>(1, n / 64));
-  return (size_t)(RS + 1) * P * 32 + (size_t)P * 72 + (size_t)n * 16 + (1 << 20);
-}
 
 // shared tail of preprocess/apply: NaN policy, maps, allocation, apply kernel
 static int sanitize_and_apply(eofx_ctx* ctx, const float* Xd, int64_t n, int64_t P, PreState& ps,
@@ -1570,17 +1446,10 @@ static int sanitize_and_apply(eofx_ctx* ctx, const float* Xd, int64_t n, int64_t
   if (p_out) *p_out = pv;
   if (!out) return EOFX_OK;
 
-  // raw mode (eofx_ctx_set_layout): nothing is dropped or reordered, so the raw field itself -- read through the
-  // affine map -- is the feature-contiguous layout; only the sample-contiguous one is written.  P < 2^31 rows: int.
-  const bool raw_ok = ctx->keep_raw && ns == n && P % 4 == 0 && ((uintptr_t)Xd % 16) == 0 && n < ((int64_t)1 << 31);
-  // masked in place (layout mode 3): all-NaN grid points (sanitizer.py:80-126 would drop them) stay in the matrix as zero
-  // columns -- scale 0 in the map, bits ANDed to +0 by the MASK kernels -- when they are a minority and the sketch lives
-  // on the sample side; a zero column changes no product, Gram matrix or norm, so the factors are those of the compacted
-  // matrix with zero rows in V at the masked features (the caller drops them).  1x the field in HBM instead of 3x.
-  const bool masked_mode = raw_ok && ctx->keep_raw == 2 && ctx->allow_masked && stats_absmax && pv < P && 10 * pv >= 6 * P && n < pv;
-  const bool raw_mode = (raw_ok && pv == P) || masked_mode;
+  // raw mode (eofx_ctx_set_layout) / masked in place (layout mode 3): apply_plan
+  const ApplyPlan ap = apply_plan(n, P, pv, ns, ctx->keep_raw, ctx->allow_masked, stats_absmax, ((uintptr_t)Xd % 16) == 0);
+  const bool masked_mode = ap.masked, raw_mode = ap.raw, in_place = ap.in_place;
   eofx_mat* m = nullptr;
-  const bool in_place = raw_mode && ctx->keep_raw == 2;
   CHK(mat_alloc(ctx, ns, masked_mode ? P : pv, &m, !raw_mode, !in_place));
   m->p_valid = pv;
   m->masked = masked_mode;
@@ -1607,7 +1476,7 @@ static int sanitize_and_apply(eofx_ctx* ctx, const float* Xd, int64_t n, int64_t
     int64_t* dcol = nullptr;
     int64_t* drow = nullptr;
     int* flag = arena_alloc<int>(ctx, 1);
-    if (pv < P && !masked_mode) {
+    if (ap.col_map) {
       std::vector<int64_t> col_map;
       col_map.reserve(pv);
       for (int64_t c = 0; c < P; ++c)
@@ -1625,7 +1494,7 @@ static int sanitize_and_apply(eofx_ctx* ctx, const float* Xd, int64_t n, int64_t
         rc = EOFX_ERR_HIP;
       if (rc == EOFX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = EOFX_ERR_HIP;
     }
-    if (!flag || (pv < P && !masked_mode && !dcol) || (ns < n && !drow)) rc = set_err(ctx, EOFX_ERR_NOMEM, "arena exhausted (maps)");
+    if (!flag || (ap.col_map && !dcol) || (ns < n && !drow)) rc = set_err(ctx, EOFX_ERR_NOMEM, "arena exhausted (maps)");
     if (rc == EOFX_OK && hipMemsetAsync(flag, 0, sizeof(int), ctx->stream) != hipSuccess) rc = EOFX_ERR_HIP;
     if (rc == EOFX_OK && in_place && !stats_absmax) rc = set_err(ctx, EOFX_ERR_ARG, "in-place layout needs the column statistics");
     if (rc == EOFX_OK && in_place) {   // nothing to write: max |x'| comes from the column statistics
@@ -1988,27 +1857,7 @@ struct RsvdOut {
   int64_t tall_pad = 0, small_pad = 0;   // padded row counts of the two panels
 };
 
-static int rsvd_auto_iters(int k, int64_t n, int64_t p) {
-  // sklearn extmath._randomized_svd: n_iter = 7 if n_components < 0.1 * min(M.shape) else 4
-  return ((double)k < 0.1 * (double)std::min(n, p)) ? 7 : 4;
-}
-
 // All panels are carved from the arena by the caller-visible drivers (reserve first).
-constexpr size_t EOFX_ORTH_TALL_BYTES = (size_t)16 << 20;
-// Is the tall panel re-normalised between the two products of a power iteration?  scikit-learn normalises after EVERY
-// product; leaving that step out is exact in exact arithmetic, but one iteration then squares sigma_1 / sigma_l inside
-// the float32 panel and the Cholesky-QR that follows squares it again: modes more than ~500x below the leading one
-// drift from the float64 reference (6e-5 at 1370x, lost beyond 4000x; with the step 8e-6 at 41000x, tests
-// test_peaked_spectrum_*).  The step costs 0.85 ms per iteration at config 4 (4 % of a fit), so:
-//   * always: small tall panels (<= 16 MiB: microseconds), the float64 mode, and the FIRST iteration of every fit;
-//   * afterwards only where it matters: after the first iteration the small-side Gram matrix W^T W is a Rayleigh
-//     quotient of X X^T on an orthonormal basis; if the square root of the ratio of its extreme eigenvalues
-//     (~ sigma_1 / sigma_l) exceeds hostla::PEAKED_RATIO the remaining iterations keep the step.
-// ONE rule (eofx_orth_tall_rule / eofx_peaked_spectrum) for the C++ drivers and the panel-level (sharded) driver.
-static bool orth_tall_rule(int64_t tall_pad, int L, int prec_power) {
-  if (std::getenv("EOFX_FORCE_ORTH_TALL")) return true;    // experiments (tools/cond_study.py)
-  return prec_power == EOFX_PREC_F64 || (size_t)tall_pad * L * sizeof(float) <= EOFX_ORTH_TALL_BYTES;
-}
 extern "C" int eofx_orth_tall_rule(int64_t tall_rows_pad, int L, int prec_power) {
   return orth_tall_rule(tall_rows_pad, L, prec_power) ? 1 : 0;
 }
@@ -2697,8 +2546,7 @@ struct FitFirst {
 };
 
 static bool fit_first_eligible(const eofx_ctx* ctx, const float* Xdev, int64_t n, int64_t P, int l) {
-  return ctx->keep_raw == 2 && ctx->prec_power == EOFX_PREC_F16X3 && n < P && l > 0 && l < n && round_up(l, 32) <= 64 &&
-         l % 32 != 0 && P % 4 == 0 && ((uintptr_t)Xdev % 16) == 0 && n < ((int64_t)1 << 31) && !std::getenv("EOFX_NO_FUSED_FIT");
+  return fit_first_eligible(ctx->keep_raw, ctx->prec_power, ((uintptr_t)Xdev % 16) == 0, n, P, l);
 }
 
 // ------------------------------------------------------------------------------------
@@ -3321,7 +3169,6 @@ static int mat_gram(eofx_ctx* ctx, const eofx_mat* m, int side, float* G) {
 static int sample_gram(eofx_ctx* ctx, const eofx_mat* m, float* G) { return mat_gram(ctx, m, 0, G); }
 
 // ---- sample-space Gram matrix on the fp16 matrix cores (eofx_gram.hpp): planes once, then the tiled NT product ------
-constexpr int64_t EOFX_GRAM_MAX_SIDE = 32768;
 static int gram_plan_get(eofx_ctx* ctx, int nti, int ntj, bool sym, int nst, const eofx_ctx::GramPlanDev** out) {
   for (auto* g : ctx->gram_plans)
     if (g->nti == nti && g->ntj == ntj && g->sym == sym && g->nst == nst) {
@@ -3351,11 +3198,8 @@ static int gram_plan_get(eofx_ctx* ctx, int nti, int ntj, bool sym, int nst, con
   return EOFX_OK;
 }
 static int64_t gram_kpad(const eofx_mat* m) { return round_up(m->p, 2 * GR_BK); }
-// does the fast route take this matrix?  (sample side up to 32768; the 32-bit row offsets of the LDS-DMA loads)
-static bool gram_fast_ok(const eofx_mat* m) {
-  return m->n_pad % GR_BM == 0 && m->n_pad <= EOFX_GRAM_MAX_SIDE && (m->X || (m->raw && m->aff) || m->Xt) &&
-         gram_kpad(m) * 4 * GR_BM < ((int64_t)1 << 32) && !std::getenv("EOFX_NO_FAST_GRAM");
-}
+// does the fast route take this matrix?
+static bool gram_fast_ok(const eofx_mat* m) { return gram_fast_ok(m->n_pad, m->p, m->X || (m->raw && m->aff) || m->Xt); }
 static size_t gram_fast_scratch(eofx_ctx* ctx, const eofx_mat* m) {
   const eofx_ctx::GramPlanDev* g = nullptr;
   const int nt = (int)(m->n_pad / GR_BM);
@@ -3405,14 +3249,8 @@ static int mat_gram_fast(eofx_ctx* ctx, const eofx_mat* m, float* G) {
   return EOFX_OK;
 }
 
-// ---- wide feature-side products Yp [p_pad x L] = X'^T Zn through the same NT kernel (L in the hundreds: the PCA
-// pre-reduction's 1500-column panel took 83 ms through the 128-column streaming tiles, the field re-read 12 times at a third of
-// the matrix cores' rate; here: transposed planes of the field once, planes of Zn^T, one MFMA-bound product)
-static bool tmul_nt_ok(const eofx_mat* m, int L) {
-  const int64_t kpad = round_up(m->n, 2 * GR_BK);
-  return L >= 512 && m->p_pad % GR_BM == 0 && (m->X || (m->raw && m->aff)) && kpad * 4 * GR_BM < ((int64_t)1 << 32) &&
-         m->n >= 512 && !std::getenv("EOFX_NO_TMUL_NT");
-}
+// ---- wide feature-side products Yp [p_pad x L] = X'^T Zn through the same NT kernel (eofx_plans.hpp: tmul_nt_ok)
+static bool tmul_nt_ok(const eofx_mat* m, int L) { return tmul_nt_ok(m->n, m->p_pad, m->X || (m->raw && m->aff), L); }
 // (the partial tiles follow the plan's split-K factor S -- as matmul_nt_scratch and gram_fast_scratch count them; the estimate
 // p_pad Lp 4 of round 4 covered S = 1 only: 700 x 3000 with L = 512 plans S = 3, and a fresh context ran out of arena)
 static size_t tmul_nt_scratch(eofx_ctx* ctx, const eofx_mat* m, int L) {
@@ -3482,11 +3320,6 @@ static int mat_tmul_nt(eofx_ctx* ctx, const eofx_mat* m, const float* Zn, float*
 // out[rows x Lo] = P[rows x L] Mx[L x Lo] for WIDE operands, on the fp16 matrix cores: both operands as {hi, lo} fp16 planes
 // (22 bits, exact power-of-two scales from their maxima), the tiled NT kernel, float32 accumulation -- the arithmetic of
 // every other pass.  Mx (float64 on the device) is rounded to float32 first.
-static bool matmul_nt_ok(int64_t rows, int L, int Lo) {
-  const int64_t kpad = round_up(L, 2 * GR_BK);
-  return L >= 512 && Lo >= 256 && Lo % 4 == 0 && L % 4 == 0 && rows >= 1024 && rows % GR_BM == 0 &&
-         kpad * 4 * GR_BM < ((int64_t)1 << 32) && !std::getenv("EOFX_NO_MATMUL_NT");
-}
 static size_t matmul_nt_scratch(eofx_ctx* ctx, int64_t rows, int L, int Lo) {
   const int64_t kpad = round_up(L, 2 * GR_BK), Lop = round_up(Lo, GR_BM);
   const eofx_ctx::GramPlanDev* g = nullptr;
@@ -3889,18 +3722,6 @@ extern "C" int eofx_ctx_comm_allreduce_f64(eofx_ctx* ctx, double* host_buf, int6
     }                                                                                           \
   } while (0)
 
-// impulse response of Im(analytic-signal filter) of period N at integer lag d (0 at d = 0 mod N):
-// N even: (2/N) cot(pi d/N) for odd d, 0 for even d;  N odd: (cot(pi d/N) - (-1)^d / sin(pi d/N)) / N
-static double hilbert_kappa(int64_t N, int64_t d) {
-  int64_t m = d % N;
-  if (m < 0) m += N;
-  if (m == 0) return 0.0;
-  const double x = M_PI * (double)d / (double)N;
-  if (N % 2 == 0) return (m % 2) ? (2.0 / (double)N) / std::tan(x) : 0.0;
-  const double sgn = (std::llabs(d) % 2) ? -1.0 : 1.0;
-  return (1.0 / std::tan(x) - sgn / std::sin(x)) / (double)N;
-}
-
 static int get_fft_plans(eofx_ctx* ctx, int64_t P, int64_t ldw, int64_t nh, int64_t batch, hipfftHandle& pf,
                          hipfftHandle& pb) {
   for (auto& e : ctx->fft_plans)
@@ -3922,69 +3743,6 @@ static int get_fft_plans(eofx_ctx* ctx, int64_t P, int64_t ldw, int64_t nh, int6
   return EOFX_OK;
 }
 
-// forward transform of a power-of-two length, float64, in place (host; filter table of the one-kernel Hilbert route)
-static void host_fft_f64(std::vector<std::complex<double>>& a) {
-  const size_t N = a.size();
-  for (size_t i = 1, j = 0; i < N; ++i) {
-    size_t bit = N >> 1;
-    for (; j & bit; bit >>= 1) j ^= bit;
-    j ^= bit;
-    if (i < j) std::swap(a[i], a[j]);
-  }
-  for (size_t len = 2; len <= N; len <<= 1) {
-    std::vector<std::complex<double>> w(len / 2);
-    for (size_t k = 0; k < len / 2; ++k) {
-      const double ang = -2.0 * M_PI * (double)k / (double)len;
-      w[k] = std::complex<double>(std::cos(ang), std::sin(ang));
-    }
-    for (size_t i = 0; i < N; i += len)
-      for (size_t k = 0; k < len / 2; ++k) {
-        const std::complex<double> x = a[i + k], y = a[i + k + len / 2] * w[k];
-        a[i + k] = x + y;
-        a[i + k + len / 2] = x - y;
-      }
-  }
-}
-
-// circular length of the convolution behind the Hilbert stage: power of two >= 2 n, and >= 1024 so that half of it
-// covers the padded series length (n_pad = round_up(n, 512) <= P / 2: the one-kernel route writes samples [0, P / 2));
-// that route (eofx_hfft.hpp) holds 2^14 complex points in LDS: circular lengths up to 2^15
-static int64_t hilbert_length(int64_t n, int* log2_out) {
-  int L = 10;
-  while (((int64_t)1 << L) < 2 * n) ++L;
-  if (log2_out) *log2_out = L;
-  return (int64_t)1 << L;
-}
-static const int HFFT_MAX_LOG2 = 15;   // 2^14 complex points in LDS: two features up to P = 2^14, one feature (even / odd samples) at P = 2^15
-
-// The four correction vectors of the padded transform, float64 [4][n] (threaded):
-// u1 = K_pre e_rev, u2 = K_pos e, u3 = (K_pre + K_pos) 1, u4 = K_pre (t - n) + K_pos (t + n)
-// with K_pre[t][s] = kappa((n + t) - s), K_pos[t][s] = kappa((n + t) - (2n + s)), e[t] = exp(-t / n / decay)
-static void hilbert_pad_vectors(int64_t n, int64_t N, double decay, std::vector<double>& u) {
-  std::vector<double> e((size_t)n), kap((size_t)(4 * n + 1));
-  for (int64_t t = 0; t < n; ++t) e[t] = std::exp(-(double)t / (double)n / decay);
-  for (int64_t d = -2 * n; d <= 2 * n; ++d) kap[(size_t)(d + 2 * n)] = hilbert_kappa(N, d);
-  u.assign((size_t)4 * n, 0.0);
-  auto work = [&](int64_t lo, int64_t hi) {
-    for (int64_t t = lo; t < hi; ++t) {
-      double a1 = 0, a2 = 0, a3 = 0, a4 = 0;
-      for (int64_t sidx = 0; sidx < n; ++sidx) {
-        const double kp = kap[(size_t)((n + t - sidx) + 2 * n)];
-        const double kq = kap[(size_t)((t - n - sidx) + 2 * n)];
-        a1 += kp * e[n - 1 - sidx];
-        a2 += kq * e[sidx];
-        a3 += kp + kq;
-        a4 += kp * (double)(sidx - n) + kq * (double)(sidx + n);
-      }
-      u[(size_t)t] = a1; u[(size_t)(n + t)] = a2; u[(size_t)(2 * n + t)] = a3; u[(size_t)(3 * n + t)] = a4;
-    }
-  };
-  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(16, n / 256));
-  std::vector<std::thread> th;
-  const int64_t step = (n + nt - 1) / nt;
-  for (int t = 0; t < nt; ++t) th.emplace_back(work, t * step, std::min<int64_t>(n, (t + 1) * step));
-  for (auto& t : th) t.join();
-}
 
 // kernel spectrum and correction vectors for series length n (cached per context)
 static int get_hilbert_setup(eofx_ctx* ctx, int64_t n, int padding, double decay, int64_t P, bool fused,
@@ -4003,32 +3761,11 @@ static int get_hilbert_setup(eofx_ctx* ctx, int64_t n, int padding, double decay
   int L = 0;
   while (((int64_t)1 << L) < P) ++L;
   if (fused) {
-    // the kernel is real and odd, so its spectrum is i h[k] with h real: one float per frequency, stored in the order
-    // the forward stages leave the spectrum in LDS; 1/P of the unnormalised inverse folded in
-    std::vector<std::complex<double>> c((size_t)P, 0.0);
-    for (int64_t d = -(n - 1); d <= n - 1; ++d) c[(size_t)((d % P + P) % P)] = hilbert_kappa(N, d) / (double)P;
-    host_fft_f64(c);
-    std::vector<float> hp((size_t)P);
-    if (L <= 14) {
-      for (int64_t pos = 0; pos < P; ++pos) hp[(size_t)pos] = (float)c[(size_t)hfft::position_frequency(L, pos)].imag();
-    } else {
-      // one feature per workgroup through the half-length transform (M = P/2 positions): the two tables of the
-      // split-filter-merge step, hm = h[k] - h[M-k] and hp2 = (h[k] + h[M-k]) / 2  (h[M] = 0)
-      const int64_t M = P / 2;
-      for (int64_t pos = 0; pos < M; ++pos) {
-        const int64_t k = hfft::position_frequency(L - 1, pos);
-        const double hk = c[(size_t)k].imag(), hkp = k ? c[(size_t)(M - k)].imag() : 0.0;
-        hp[(size_t)pos] = (float)(hk - hkp);
-        hp[(size_t)(M + pos)] = (float)(0.5 * (hk + hkp));
-      }
-    }
+    const std::vector<float> hp = hilbert_fused_table(n, N, L);
     HIPCHK(hipMalloc((void**)&hs.hperm, sizeof(float) * P));
     HIPCHK(hipMemcpy(hs.hperm, hp.data(), sizeof(float) * P, hipMemcpyHostToDevice));
   } else {
-    // circular embedding of the Toeplitz kernel, lags -(n-1) .. n-1, scaled by 1/P (unnormalised inverse)
-    std::vector<float> c((size_t)ldw, 0.f);
-    for (int64_t d = -(n - 1); d <= n - 1; ++d)
-      c[(size_t)((d % P + P) % P)] = (float)(hilbert_kappa(N, d) / (double)P);
+    const std::vector<float> c = hilbert_circular_kernel(n, N, P);      // ldw floats
     float* cdev = nullptr;
     HIPCHK(hipMalloc((void**)&cdev, sizeof(float) * ldw));
     HIPCHK(hipMalloc(&hs.chat, sizeof(cfloat) * nh));
@@ -4041,21 +3778,7 @@ static int get_hilbert_setup(eofx_ctx* ctx, int64_t n, int padding, double decay
     (void)hipFree(cdev);
   }
   if (padding) {
-    std::vector<double> ud;
-    hilbert_pad_vectors(n, N, decay, ud);
-    std::vector<float> hu((size_t)4 * n + 4, 0.f);   // (+ the four means over the samples, one-kernel route)
-    for (int64_t t = 0; t < n; ++t)
-      for (int k = 0; k < 4; ++k) {
-        const float v = (float)ud[(size_t)k * n + t];
-        if (fused) hu[(size_t)(4 * t + k)] = v;      // the one-kernel route reads the four vectors interleaved per sample
-        else hu[(size_t)k * n + t] = v;
-      }
-    if (fused)       // means of the (float32-rounded) vectors: the kernel adds coefficient * mean to the output's mean
-      for (int k = 0; k < 4; ++k) {
-        double m = 0.0;
-        for (int64_t t = 0; t < n; ++t) m += (double)hu[(size_t)(4 * t + k)];
-        hu[(size_t)(4 * n + k)] = (float)(m / (double)n);
-      }
+    const std::vector<float> hu = hilbert_pad_table(n, N, decay, fused);      // 4 n + 4 floats
     HIPCHK(hipMalloc((void**)&hs.u, sizeof(float) * (4 * n + 4)));
     HIPCHK(hipMemcpy(hs.u, hu.data(), sizeof(float) * (4 * n + 4), hipMemcpyHostToDevice));
   }
@@ -4339,14 +4062,13 @@ static int panel_colargminmax(eofx_ctx* ctx, const float* P, int64_t rows, int L
 // ------------------------------------------------------------------------------------
 using hostla::zdouble;
 
-// The Hilbert stage as ONE linear map along the samples: for a series y [n] (padding "exp": linear fit, exponential pads,
-// transform of the 3n-long series, middle third -- reference utils/hilbert_transform.py:47-92; no padding: the circular
-// transform of the series itself), minus the mean over the samples,
-//   Im = Hc y,   Hc = C (T + u1 (e_0 - a0)^T + u2 (e_{n-1} - a0 - (n-1) a1)^T + u3 a0^T + u4 a1^T),   C = I - 1 1^T / n
-// with T[t][s] = kappa(N, t - s), a0^T y = c0 and a1^T y = c1 the coefficients of the linear fit, and u1..u4 the
-// correction vectors of get_hilbert_setup.  Built in float64 on the host, held as a resident n x n matrix (both layouts)
-// per (n, padding, decay): eofx_rsvd_hilbert_c64 applies it to the SAMPLE-side panels instead of materialising Im.
-static int build_hilbert_operator_host(eofx_ctx* ctx, int64_t n, int padding, double decay, std::vector<float>& hc);
+// The Hilbert stage as ONE linear map along the samples (build_hilbert_operator_host, eofx_hilbert_host.hpp), held as a resident
+// n x n matrix (both layouts) per (n, padding, decay): eofx_rsvd_hilbert_c64 applies it to the SAMPLE-side panels instead of
+// materialising Im.
+static int hilbert_operator_host(eofx_ctx* ctx, int64_t n, int padding, double decay, std::vector<float>& hc) {
+  if (build_hilbert_operator_host(n, padding, decay, hc)) return EOFX_OK;
+  return set_err(ctx, EOFX_ERR_NOMEM, "cannot allocate the %lld x %lld Hilbert operator on the host", (long long)n, (long long)n);
+}
 static int get_hilbert_operator(eofx_ctx* ctx, int64_t n, int padding, double decay, const eofx_mat** out) {
   for (auto& h : ctx->hops)
     if (h.n == n && h.padding == padding && (!padding || h.decay == decay)) {
@@ -4354,7 +4076,7 @@ static int get_hilbert_operator(eofx_ctx* ctx, int64_t n, int padding, double de
       return EOFX_OK;
     }
   std::vector<float> hc;
-  CHK(build_hilbert_operator_host(ctx, n, padding, decay, hc));
+  CHK(hilbert_operator_host(ctx, n, padding, decay, hc));
   eofx_mat* m = nullptr;
   CHK(eofx_mat_from_dense_f32(ctx, hc.data(), n, n, n, &m));
   eofx_ctx::HilbertOp h;
@@ -4367,65 +4089,13 @@ static int get_hilbert_operator(eofx_ctx* ctx, int64_t n, int padding, double de
   *out = m;
   return EOFX_OK;
 }
-// Hc [n x n] row-major float32 on the host: Im = Hc A for the Hilbert stage of eofx_hilbert_f32 along the samples (built in float64)
-static int build_hilbert_operator_host(eofx_ctx* ctx, int64_t n, int padding, double decay, std::vector<float>& hc) {
-  const int64_t N = padding ? 3 * n : n;
-  std::vector<double> kap((size_t)(2 * n + 1)), pre((size_t)(2 * n + 2), 0.0);   // kappa(N, d), d = -n .. n, and its prefix sums
-  for (int64_t d = -n; d <= n; ++d) kap[(size_t)(d + n)] = hilbert_kappa(N, d);
-  for (size_t i = 0; i < kap.size(); ++i) pre[i + 1] = pre[i] + kap[i];
-  std::vector<double> u, rowv((size_t)4 * n, 0.0), ubar(4, 0.0);
-  if (padding) {
-    hilbert_pad_vectors(n, N, decay, u);
-    const double tbar = 0.5 * (double)(n - 1), stt = (double)n * ((double)n * (double)n - 1.0) / 12.0;
-    for (int64_t sidx = 0; sidx < n; ++sidx) {
-      const double a1 = n > 1 ? ((double)sidx - tbar) / stt : 0.0, a0 = 1.0 / (double)n - tbar * a1;
-      rowv[(size_t)sidx] = (sidx == 0 ? 1.0 : 0.0) - a0;                                      // amp_pre = y[0] - c0
-      rowv[(size_t)(n + sidx)] = (sidx == n - 1 ? 1.0 : 0.0) - a0 - (double)(n - 1) * a1;    // amp_pos = y[n-1] - fit(n-1)
-      rowv[(size_t)(2 * n + sidx)] = a0;
-      rowv[(size_t)(3 * n + sidx)] = a1;
-    }
-    for (int k = 0; k < 4; ++k) {
-      double m = 0.0;
-      for (int64_t t = 0; t < n; ++t) m += u[(size_t)k * n + t];
-      ubar[k] = m / (double)n;
-    }
-  }
-  try {
-    hc.resize((size_t)n * n);
-  } catch (const std::bad_alloc&) {
-    return set_err(ctx, EOFX_ERR_NOMEM, "cannot allocate the %lld x %lld Hilbert operator on the host", (long long)n, (long long)n);
-  }
-  auto work = [&](int64_t lo, int64_t hi) {
-    for (int64_t t = lo; t < hi; ++t) {
-      float* row = hc.data() + (size_t)t * n;
-      double ut[4] = {0, 0, 0, 0};
-      if (padding)
-        for (int k = 0; k < 4; ++k) ut[k] = u[(size_t)k * n + t] - ubar[k];
-      for (int64_t sidx = 0; sidx < n; ++sidx) {
-        // column mean of T: (1/n) sum_t kappa(t - s) = (pre[n - s + n] - pre[-s + n]) / n
-        const double cm = (pre[(size_t)(2 * n - sidx)] - pre[(size_t)(n - sidx)]) / (double)n;
-        double v = kap[(size_t)(t - sidx + n)] - cm;
-        if (padding)
-          v += ut[0] * rowv[(size_t)sidx] + ut[1] * rowv[(size_t)(n + sidx)] + ut[2] * rowv[(size_t)(2 * n + sidx)] +
-               ut[3] * rowv[(size_t)(3 * n + sidx)];
-        row[sidx] = (float)v;
-      }
-    }
-  };
-  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(16, n / 256));
-  std::vector<std::thread> th;
-  const int64_t step = (n + nt - 1) / nt;
-  for (int t = 0; t < nt; ++t) th.emplace_back(work, t * step, std::min<int64_t>(n, (t + 1) * step));
-  for (auto& t : th) t.join();
-  return EOFX_OK;
-}
 extern "C" int eofx_hilbert_operator_f32(eofx_ctx* ctx, int64_t n, int padding, double decay_factor, float* out) {
   if (!ctx || !out || n <= 0) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
   if (padding && !(decay_factor > 0.0)) return set_err(ctx, EOFX_ERR_ARG, "decay_factor must be positive");
   if (n > EOFX_HILBERT_OP_MAX_N) return set_err(ctx, EOFX_ERR_ARG, "the Hilbert operator is limited to %d samples", EOFX_HILBERT_OP_MAX_N);
   if (is_device_ptr(out)) return set_err(ctx, EOFX_ERR_ARG, "out must be a host pointer");
   std::vector<float> hc;
-  CHK(build_hilbert_operator_host(ctx, n, padding ? 1 : 0, decay_factor, hc));
+  CHK(hilbert_operator_host(ctx, n, padding ? 1 : 0, decay_factor, hc));
   std::memcpy(out, hc.data(), sizeof(float) * hc.size());
   return EOFX_OK;
 }
@@ -5143,333 +4813,10 @@ extern "C" int eofx_mat_sumsq_f64(eofx_ctx* ctx, const eofx_mat* m, double* out)
   return EOFX_OK;
 }
 
-// ------------------------------------------------------------------------------------
-// Gaussian sketch matrix, bit-identical to numpy's legacy stream
-//   np.random.RandomState(seed).normal(size=(rows, cols)).astype(np.float32)
-// which is what scikit-learn draws for randomized_svd (extmath.py _randomized_range_finder), so
-// `random_state` keeps its meaning.  MT19937 (init_genrand seeding), 53-bit doubles, Marsaglia
-// polar method with the cached second deviate (numpy legacy_gauss).  The uniform stream and the
-// accept/reject decisions are inherently sequential; the log/sqrt transforms of the accepted pairs
-// are independent and run on worker threads (same libm, same results).
-// ------------------------------------------------------------------------------------
-namespace {
-struct MT19937 {
-  uint32_t mt[624];
-  int idx;
-  explicit MT19937(uint32_t seed) {
-    mt[0] = seed;
-    for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
-    idx = 624;
-  }
-  void refill() {
-    int k = 0;
-    for (; k < 624 - 397; ++k) {
-      const uint32_t y = (mt[k] & 0x80000000u) | (mt[k + 1] & 0x7fffffffu);
-      mt[k] = mt[k + 397] ^ (y >> 1) ^ (-(int32_t)(y & 1u) & 0x9908b0dfu);
-    }
-    for (; k < 623; ++k) {
-      const uint32_t y = (mt[k] & 0x80000000u) | (mt[k + 1] & 0x7fffffffu);
-      mt[k] = mt[k + (397 - 624)] ^ (y >> 1) ^ (-(int32_t)(y & 1u) & 0x9908b0dfu);
-    }
-    const uint32_t y = (mt[623] & 0x80000000u) | (mt[0] & 0x7fffffffu);
-    mt[623] = mt[396] ^ (y >> 1) ^ (-(int32_t)(y & 1u) & 0x9908b0dfu);
-    idx = 0;
-  }
-  inline uint32_t next() {
-    if (idx >= 624) refill();
-    uint32_t y = mt[idx++];
-    y ^= (y >> 11);
-    y ^= (y << 7) & 0x9d2c5680u;
-    y ^= (y << 15) & 0xefc60000u;
-    y ^= (y >> 18);
-    return y;
-  }
-  inline double next_double() {
-    const uint32_t a = next() >> 5, b = next() >> 6;
-    return (a * 67108864.0 + b) / 9007199254740992.0;
-  }
-};
-}  // namespace
-
-// Parallel, still bit-identical.  Every candidate pair of the polar method consumes exactly four MT19937 words whether
-// it is accepted or not, so candidate i always sits at words 4i..4i+3 of the stream.  Only the raw MT recurrence is
-// sequential -- written as ONE linear recurrence x[i] = x[i-227] ^ f(x[i-624], x[i-623]) over the whole stream (no
-// 624-word refill blocks, no copies), eight words per AVX2 step where the host has it: 0.55 ns per word on the GPU box,
-// bound by one core's store bandwidth (40 MB for a 129 600 x 30 sketch).  Tempering, the conversion to doubles, the accept test and the log / sqrt of the accepted
-// pairs are data-parallel over candidates: every worker thread turns its contiguous share of the candidates into its
-// own list of deviates in ONE pass, and the lists are concatenated in order.
-namespace {
-#define EOFX_MT_FILL_BODY                                                                                     \
-  for (int64_t i = from; i < count; ++i) {                                                                     \
-    const uint32_t y = (x[i - 624] & 0x80000000u) | (x[i - 623] & 0x7fffffffu);                               \
-    x[i] = x[i - 227] ^ (y >> 1) ^ ((uint32_t)(-(int32_t)(y & 1u)) & 0x9908b0dfu);                            \
-  }
-#if !defined(__HIP_DEVICE_COMPILE__)
-// eight words per step: every load lies at least 220 words behind the eight words being written.  [from, count): the
-// words [0, from) are final (from >= 624), so the stream can be extended chunk by chunk.
-__attribute__((target("avx2"))) void mt_fill_avx2_range(uint32_t* __restrict__ x, int64_t from, int64_t count) {
-  const __m256i upper = _mm256_set1_epi32((int)0x80000000u), lower = _mm256_set1_epi32(0x7fffffff);
-  const __m256i one = _mm256_set1_epi32(1), matrix = _mm256_set1_epi32((int)0x9908b0dfu), zero = _mm256_setzero_si256();
-  int64_t i = from;
-  for (; i + 8 <= count; i += 8) {
-    const __m256i a = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(x + i - 624));
-    const __m256i b = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(x + i - 623));
-    const __m256i c = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(x + i - 227));
-    const __m256i y = _mm256_or_si256(_mm256_and_si256(a, upper), _mm256_and_si256(b, lower));
-    const __m256i mag = _mm256_and_si256(_mm256_sub_epi32(zero, _mm256_and_si256(y, one)), matrix);
-    _mm256_storeu_si256(reinterpret_cast<__m256i*>(x + i), _mm256_xor_si256(_mm256_xor_si256(c, _mm256_srli_epi32(y, 1)), mag));
-  }
-  for (; i < count; ++i) {
-    const uint32_t y = (x[i - 624] & 0x80000000u) | (x[i - 623] & 0x7fffffffu);
-    x[i] = x[i - 227] ^ (y >> 1) ^ ((uint32_t)(-(int32_t)(y & 1u)) & 0x9908b0dfu);
-  }
-}
-#else
-inline void mt_fill_avx2_range(uint32_t*, int64_t, int64_t) {}   // (device pass of the single-source compile: host code only)
-#endif
-void mt_fill_generic_range(uint32_t* __restrict__ x, int64_t from, int64_t count) { EOFX_MT_FILL_BODY }
-#undef EOFX_MT_FILL_BODY
-inline uint32_t mt_temper(uint32_t y) {
-  y ^= (y >> 11);
-  y ^= (y << 7) & 0x9d2c5680u;
-  y ^= (y << 15) & 0xefc60000u;
-  y ^= (y >> 18);
-  return y;
-}
-}  // namespace
-
-namespace {
-// A small persistent pool for the data-parallel half of the sketch generator (starting a std::thread costs ~40 us; a
-// 10000 x 60 sketch is ~1.5 ms of work in total, so eighteen fresh threads per call were a third of its wall time).
-struct SketchPool {
-  std::mutex mu;
-  std::condition_variable cv_work, cv_done;
-  std::vector<std::thread> threads;
-  std::deque<std::function<void()>> tasks;
-  int pending = 0;
-  bool stop = false;
-  void ensure(int n) {
-    std::lock_guard<std::mutex> lk(mu);
-    while ((int)threads.size() < n) threads.emplace_back([this] { loop(); });
-  }
-  // Keep the workers on the cores that share the calling thread's L3 (EOFX_SKETCH_PIN=1; Linux): the stream buffer then moves
-  // between the producer and its consumers inside one cache instead of across the socket.
-  int pinned_cpu = -1;
-  int domain_threads = 0;     // hardware threads that share the caller's L3 (0: unknown / not pinned)
-  void pin_near_caller() {
-#if defined(__linux__) && !defined(__HIP_DEVICE_COMPILE__)
-    const int cpu = sched_getcpu();
-    if (cpu < 0 || cpu == pinned_cpu) return;
-    char path[128];
-    snprintf(path, sizeof(path), "/sys/devices/system/cpu/cpu%d/cache/index3/shared_cpu_list", cpu);
-    FILE* f = fopen(path, "r");
-    if (!f) return;
-    char buf[512] = {0};
-    const bool ok = fgets(buf, sizeof(buf), f) != nullptr;
-    fclose(f);
-    if (!ok) return;
-    cpu_set_t set;
-    CPU_ZERO(&set);
-    int count = 0;
-    for (char* tok = strtok(buf, ",\n"); tok; tok = strtok(nullptr, ",\n")) {
-      int a = 0, b = 0;
-      const int got = sscanf(tok, "%d-%d", &a, &b);
-      if (got == 1) b = a;
-      if (got < 1) continue;
-      for (int c = a; c <= b && c < CPU_SETSIZE; ++c) { CPU_SET(c, &set); ++count; }
-    }
-    if (count < 2) return;
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& t : threads) (void)pthread_setaffinity_np(t.native_handle(), sizeof(set), &set);
-    pinned_cpu = cpu;
-    domain_threads = count;
-#endif
-  }
-  void loop() {
-    for (;;) {
-      std::function<void()> job;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv_work.wait(lk, [this] { return stop || !tasks.empty(); });
-        if (stop && tasks.empty()) return;
-        job = std::move(tasks.front());
-        tasks.pop_front();
-      }
-      job();
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        if (--pending == 0) cv_done.notify_all();
-      }
-    }
-  }
-  void submit(std::function<void()> f) {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      tasks.push_back(std::move(f));
-      ++pending;
-    }
-    cv_work.notify_one();
-  }
-  void wait() {
-    std::unique_lock<std::mutex> lk(mu);
-    cv_done.wait(lk, [this] { return pending == 0; });
-  }
-  ~SketchPool() {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      stop = true;
-    }
-    cv_work.notify_all();
-    for (auto& t : threads) t.join();
-  }
-};
-SketchPool& sketch_pool() {
-  static SketchPool* pool = new SketchPool();     // leaked on purpose: worker threads must not be joined at exit order
-  return *pool;
-}
-std::mutex g_sketch_call;    // one generation at a time (the pool's completion counter is per call)
-// spin politely: a few thousand pauses (the waits here are microseconds), then give the core away -- on a host with fewer free
-// cores than workers a pure spin would keep the producer off its core
-struct SpinWait {
-  int spins = 0;
-  void operator()() {
-#if !defined(__HIP_DEVICE_COMPILE__)
-    if (++spins < 4000) _mm_pause();
-    else std::this_thread::yield();
-#endif
-  }
-};
-}  // namespace
-
+// the Gaussian sketch matrix of scikit-learn's randomized_svd, bit for bit (eofx_sketch.hpp)
 extern "C" int eofx_sketch_gaussian_f32(uint32_t seed, int64_t rows, int64_t cols, float* out) {
   if (!out || rows < 0 || cols < 0) return EOFX_ERR_ARG;
-  const int64_t total = rows * cols;
-  if (total == 0) return EOFX_OK;
-  const int64_t npairs = (total + 1) / 2;
-  const int hw = (int)std::thread::hardware_concurrency();
-  // eight workers: the producer thread is the bound from four on (profiles/r04_sketch_probe.txt), and eight fit the physical cores
-  // of one L3 domain, where the workers are kept (SketchPool::pin_near_caller)
-  int max_threads = std::max(1, std::min(8, hw > 1 ? hw - 1 : 1));
-  if (const char* ev = getenv("EOFX_SKETCH_THREADS")) max_threads = std::max(1, atoi(ev));
-  static const bool have_avx2 = __builtin_cpu_supports("avx2");
-  std::lock_guard<std::mutex> call_lock(g_sketch_call);
-  // x[0..623]: the generator state (init_genrand seeding); x[624 + w]: raw (untempered) output word w of the stream
-  uint32_t state[624];
-  {
-    const MT19937 g(seed);
-    std::memcpy(state, g.mt, sizeof(state));
-  }
-  int64_t done_pairs = 0;
-  while (done_pairs < npairs) {
-    const int64_t need = npairs - done_pairs;
-    // acceptance probability pi/4: ask for slightly more candidates than expected, at least a few
-    const int64_t ncand = (int64_t)((double)need / 0.7853981633974483 * 1.01) + 64;
-    const int64_t nwords = 4 * ncand;
-    // ONE grow-only buffer for the process (calls are serialised by g_sketch_call): 40 MB of fresh pages per call cost
-    // more than the recurrence itself -- and a buffer per calling THREAD meant exactly that for callers that draw on a
-    // short-lived worker thread (engine.SketchFuture: 12 ms instead of 5.8 for the 129 600 x 30 sketch of config 3)
-    static std::unique_ptr<uint32_t[]> xbuf;
-    static size_t xcap = 0;
-    if (xcap < (size_t)(624 + nwords)) {
-      xbuf.reset(new uint32_t[(size_t)(624 + nwords)]);   // uninitialised on purpose
-      xcap = (size_t)(624 + nwords);
-    }
-    uint32_t* x = xbuf.get();
-    std::memcpy(x, state, sizeof(state));
-    const uint32_t* raw = x + 624;
-    // The raw recurrence is sequential and runs on this thread, chunk by chunk.  The workers are woken ONCE per call and
-    // then claim chunks from an atomic counter, spinning (politely) for the few microseconds until the chunk they hold has
-    // been produced: a mutex + condition-variable hand-over per 16 K-word chunk cost more than the chunk's recurrence.
-    // Deviates go to one grow-only buffer at their chunk's place; once every chunk is done the same workers copy them to
-    // their final offsets.
-    const int64_t chunk = 4096;                                     // candidates per chunk (16 K words): the deviate work of the LAST chunk is the tail of the call
-    const int64_t nchunks = (ncand + chunk - 1) / chunk;
-    static std::unique_ptr<float[]> dbuf;                          // [nchunks][2 chunk]: (f b, f a) per accepted pair, in stream order
-    static size_t dcap = 0;
-    if (dcap < (size_t)(2 * chunk * nchunks)) {
-      dbuf.reset(new float[(size_t)(2 * chunk * nchunks)]);
-      dcap = (size_t)(2 * chunk * nchunks);
-    }
-    float* const dev = dbuf.get();
-    std::vector<int64_t> cnt((size_t)nchunks, 0), off((size_t)nchunks + 1, 0);
-    std::atomic<int64_t> produced{0}, claim{0}, finished{0}, claim2{0};
-    std::atomic<int> phase2{0};
-    auto work = [&](int64_t c) {
-      const int64_t lo = c * chunk, hi = std::min<int64_t>(ncand, lo + chunk);
-      float* d = dev + 2 * chunk * c;
-      int64_t q = 0;
-      for (int64_t i = lo; i < hi; ++i) {
-        const uint32_t w0 = mt_temper(raw[4 * i]) >> 5, w1 = mt_temper(raw[4 * i + 1]) >> 6;
-        const uint32_t w2 = mt_temper(raw[4 * i + 2]) >> 5, w3 = mt_temper(raw[4 * i + 3]) >> 6;
-        const double a = 2.0 * ((w0 * 67108864.0 + w1) / 9007199254740992.0) - 1.0;
-        const double b = 2.0 * ((w2 * 67108864.0 + w3) / 9007199254740992.0) - 1.0;
-        const double r = a * a + b * b;
-        if (r >= 1.0 || r == 0.0) continue;
-        const double f = std::sqrt(-2.0 * std::log(r) / r);
-        d[q++] = (float)(f * b);      // returned first
-        d[q++] = (float)(f * a);      // the cached deviate
-      }
-      cnt[(size_t)c] = q;
-    };
-    const int64_t obase = 2 * done_pairs;
-    auto copy_out = [&](int64_t c) {     // deviates beyond `total` belong to later draws of the stream and are dropped
-      const int64_t o = obase + off[(size_t)c];
-      if (o >= total) return;
-      const int64_t take = std::min<int64_t>(cnt[(size_t)c], total - o);
-      std::memcpy(out + o, dev + 2 * chunk * c, sizeof(float) * (size_t)take);
-    };
-    auto worker = [&] {
-      for (;;) {
-        const int64_t c = claim.fetch_add(1, std::memory_order_relaxed);
-        if (c >= nchunks) break;
-        for (SpinWait sw; produced.load(std::memory_order_acquire) <= c;) sw();
-        work(c);
-        finished.fetch_add(1, std::memory_order_release);
-      }
-      for (SpinWait sw; !phase2.load(std::memory_order_acquire);) sw();
-      for (;;) {
-        const int64_t c = claim2.fetch_add(1, std::memory_order_relaxed);
-        if (c >= nchunks) break;
-        copy_out(c);
-      }
-    };
-    const int nworkers = (max_threads > 1 && nchunks > 1) ? (int)std::min<int64_t>(max_threads, nchunks) : 0;
-    SketchPool& pool = sketch_pool();
-    if (nworkers) {
-      pool.ensure(nworkers);
-      static const bool pin = !(getenv("EOFX_SKETCH_PIN") && atoi(getenv("EOFX_SKETCH_PIN")) == 0);
-      if (pin) pool.pin_near_caller();
-      for (int w = 0; w < nworkers; ++w) pool.submit(worker);
-    }
-    int64_t filled = 624;                                            // words of x that hold final values
-    for (int64_t c = 0; c < nchunks; ++c) {
-      const int64_t upto = 624 + 4 * std::min<int64_t>(ncand, (c + 1) * chunk);
-      // the recurrence reads up to 624 words back and writes only beyond `filled`: extending the buffer in place
-      if (have_avx2) mt_fill_avx2_range(x, filled, upto);
-      else mt_fill_generic_range(x, filled, upto);
-      filled = upto;
-      produced.store(c + 1, std::memory_order_release);
-    }
-    for (;;) {                                                        // this thread takes chunks too once the stream stands
-      const int64_t c = claim.fetch_add(1, std::memory_order_relaxed);
-      if (c >= nchunks) break;
-      work(c);
-      finished.fetch_add(1, std::memory_order_release);
-    }
-    for (SpinWait sw; finished.load(std::memory_order_acquire) < nchunks;) sw();
-    for (int64_t c = 0; c < nchunks; ++c) off[(size_t)c + 1] = off[(size_t)c] + cnt[(size_t)c];
-    phase2.store(1, std::memory_order_release);
-    for (;;) {
-      const int64_t c = claim2.fetch_add(1, std::memory_order_relaxed);
-      if (c >= nchunks) break;
-      copy_out(c);
-    }
-    if (nworkers) pool.wait();
-    std::memcpy(state, x + nwords, sizeof(state));     // the state after these words (a rare second round continues here)
-    const int64_t o = std::min<int64_t>(total, obase + off[(size_t)nchunks]);
-    done_pairs = (o + 1) / 2;
-    if (o >= total) break;
-  }
+  eofx_sketch::gaussian_f32(seed, rows, cols, out);
   return EOFX_OK;
 }
 
@@ -5583,14 +4930,6 @@ extern "C" int eofx_panel_rot_step_f64(eofx_ctx* ctx, const float* X, int64_t ro
 // ------------------------------------------------------------------------------------
 // delay embedding of Extended EOF analysis as an operator on the resident field (eofx_lag.hpp)
 // ------------------------------------------------------------------------------------
-// Lags are processed in groups whose side-by-side sample panel is at most this many columns wide: the wide product then
-// stays on the wide-panel kernels (the MFMA NT kernel of eofx_gram.hpp from 512 columns, the 128-column streaming tiles
-// below) while E = 100 lags of a 64-column panel do not ask for a 6400-column intermediate.  The field is read once
-// per group.
-constexpr int EOFX_LAG_GROUP_COLS = 1024;
-
-static int lag_groupsize(int E, int L) { return std::max(1, std::min(E, EOFX_LAG_GROUP_COLS / std::max(L, 1))); }
-
 static int lag_check(eofx_ctx* ctx, const eofx_mat* m, int tau, int E, int64_t* nprime) {
   if (!m || tau < 1 || E < 1) return set_err(ctx, EOFX_ERR_ARG, "bad argument (tau >= 1, embedding >= 1)");
   if (m->masked) return set_err(ctx, EOFX_ERR_ARG, "the lag operator needs a compacted matrix (no masked in-place layout)");
@@ -5621,8 +4960,6 @@ static int lag_source(eofx_ctx* ctx, const eofx_mat* m, LagSrc& s) {
   }
   return EOFX_OK;
 }
-
-static int lag_blocks(int64_t total4) { return (int)std::max<int64_t>(1, std::min<int64_t>((total4 + 255) / 256, 8192)); }
 
 extern "C" int eofx_lag_stats_f64(eofx_ctx* ctx, const eofx_mat* m, int tau, int embedding, double* mean,
                                   double* total_variance) {
@@ -5679,7 +5016,7 @@ extern "C" int eofx_lag_tmul_f32(eofx_ctx* ctx, const eofx_mat* m, int tau, int 
   CHK(lag_check(ctx, m, tau, embedding, &np));
   if (!is_device_ptr(mean)) return set_err(ctx, EOFX_ERR_ARG, "mean must be a device buffer (eofx_lag_stats_f64)");
   ENTER(ctx);
-  const int E = embedding, G = lag_groupsize(E, L), Gl = E - (E - 1) / G * G;   // full groups of G lags, the last of Gl
+  const int E = embedding, G = lag_groupsize(E, L), Gl = lag_last_group(E, G);   // full groups of G lags, the last of Gl
   const int Lg = G * L;
   const int NPART = 64;
   size_t need = (size_t)m->n_pad * Lg * sizeof(float) + (size_t)m->p_pad * Lg * sizeof(float) + (size_t)(NPART + 1) * L * 8 + 8192;
@@ -5715,7 +5052,7 @@ extern "C" int eofx_lag_mul_f32(eofx_ctx* ctx, const eofx_mat* m, int tau, int e
   CHK(lag_check(ctx, m, tau, embedding, &np));
   if (!is_device_ptr(mean)) return set_err(ctx, EOFX_ERR_ARG, "mean must be a device buffer (eofx_lag_stats_f64)");
   ENTER(ctx);
-  const int E = embedding, G = lag_groupsize(E, L), Gl = E - (E - 1) / G * G;
+  const int E = embedding, G = lag_groupsize(E, L), Gl = lag_last_group(E, G);
   const int Lg = G * L;
   const int64_t np_pad = round_up(np, ATB_BM);
   const bool grouped = G < E;
@@ -5770,171 +5107,6 @@ extern "C" int eofx_lag_embed_f32(eofx_ctx* ctx, const eofx_mat* m, int tau, int
 // ---- geographically weighted PCA (csrc/eofx_gw.hpp) ------------------------------------------------------------------
 namespace {
 
-// One set of locations cut into tiles of GW_T in Morton order of their (normalised) coordinates, with a bound per tile
-// and per group of 16 tiles: for haversine the unit-vector centre and angular radius (handles the dateline and the
-// poles), for euclidean the bounding box.
-struct GwTiles {
-  std::vector<int64_t> perm;   // sorted position -> row of X
-  std::vector<double> geo;     // [3 x sorted position] (eofx_gw.hpp gw_weight)
-  std::vector<std::array<double, 4>> tile, group;
-  int64_t count = 0, ntiles = 0;
-};
-
-static double gw_angle(const double* a, const double* b) {
-  const double cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
-  return std::atan2(std::sqrt(cx * cx + cy * cy + cz * cz), a[0] * b[0] + a[1] * b[1] + a[2] * b[2]);
-}
-
-static std::array<double, 4> gw_bound(const std::vector<double>& u, int64_t s0, int64_t s1, int metric) {
-  if (metric == EOFX_GW_METRIC_EUCLIDEAN) {
-    std::array<double, 4> b{u[3 * s0], u[3 * s0], u[3 * s0 + 1], u[3 * s0 + 1]};
-    for (int64_t s = s0 + 1; s < s1; ++s) {
-      b[0] = std::min(b[0], u[3 * s]);
-      b[1] = std::max(b[1], u[3 * s]);
-      b[2] = std::min(b[2], u[3 * s + 1]);
-      b[3] = std::max(b[3], u[3 * s + 1]);
-    }
-    return b;
-  }
-  double c[3] = {0.0, 0.0, 0.0};
-  for (int64_t s = s0; s < s1; ++s)
-    for (int d = 0; d < 3; ++d) c[d] += u[3 * s + d];
-  const double nrm = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-  for (int d = 0; d < 3; ++d) c[d] = nrm > 1e-9 * (double)(s1 - s0) ? c[d] / nrm : u[3 * s0 + d];
-  double rho = 0.0;
-  for (int64_t s = s0; s < s1; ++s) rho = std::max(rho, gw_angle(c, &u[3 * s]));
-  return {c[0], c[1], c[2], rho};
-}
-
-// a lower bound of every distance between two bounded sets (km for haversine, less a margin of 1e-9 rad for rounding)
-static double gw_lower(const std::array<double, 4>& a, const std::array<double, 4>& b, int metric) {
-  if (metric == EOFX_GW_METRIC_EUCLIDEAN) {
-    const double dx = std::max({0.0, a[0] - b[1], b[0] - a[1]}), dy = std::max({0.0, a[2] - b[3], b[2] - a[3]});
-    return std::sqrt(dx * dx + dy * dy);
-  }
-  const double th = gw_angle(a.data(), b.data()) - a[3] - b[3] - 1e-9;
-  return th > 0.0 ? GW_EARTH_RADIUS * th : 0.0;
-}
-
-// true when every weight at a distance >= dlb is exactly 0 in float64 (bisquare: beyond the bandwidth; gaussian and
-// exponential: exp of an argument below -750 underflows to 0)
-static bool gw_zero(double dlb, int kernel, double bw) {
-  const double u = dlb / bw;
-  if (kernel == EOFX_GW_KERNEL_BISQUARE) return dlb > bw;
-  if (kernel == EOFX_GW_KERNEL_GAUSSIAN) return 0.5 * u * u > 750.0;
-  return 0.5 * u > 750.0;
-}
-
-static uint64_t gw_morton(uint32_t x, uint32_t y) {
-  uint64_t k = 0;
-  for (int b = 0; b < 16; ++b) k |= (uint64_t)((x >> b) & 1u) << (2 * b) | (uint64_t)((y >> b) & 1u) << (2 * b + 1);
-  return k;
-}
-
-static void gw_tile(const double* xy, int64_t first, int64_t count, int metric, const double* box, GwTiles& t) {
-  t.count = count;
-  t.ntiles = (count + GW_T - 1) / GW_T;
-  std::vector<std::pair<uint64_t, int64_t>> key((size_t)count);
-  for (int64_t i = 0; i < count; ++i) {
-    const double* c = xy + 2 * (first + i);
-    const double fx = box[1] > box[0] ? (c[0] - box[0]) / (box[1] - box[0]) : 0.0;
-    const double fy = box[3] > box[2] ? (c[1] - box[2]) / (box[3] - box[2]) : 0.0;
-    key[(size_t)i] = {gw_morton((uint32_t)std::min(65535.0, std::max(0.0, fx * 65535.0)),
-                                (uint32_t)std::min(65535.0, std::max(0.0, fy * 65535.0))), first + i};
-  }
-  std::sort(key.begin(), key.end());
-  t.perm.resize((size_t)count);
-  t.geo.resize(3 * (size_t)count);
-  std::vector<double> u(3 * (size_t)count);
-  for (int64_t s = 0; s < count; ++s) {
-    const int64_t i = key[(size_t)s].second;
-    t.perm[(size_t)s] = i;
-    const double x = xy[2 * i], y = xy[2 * i + 1];
-    if (metric == EOFX_GW_METRIC_HAVERSINE) {
-      const double lon = x * (M_PI / 180.0), lat = y * (M_PI / 180.0);
-      t.geo[3 * s] = lon;
-      t.geo[3 * s + 1] = lat;
-      t.geo[3 * s + 2] = std::cos(lat);
-      u[3 * s] = std::cos(lat) * std::cos(lon);
-      u[3 * s + 1] = std::cos(lat) * std::sin(lon);
-      u[3 * s + 2] = std::sin(lat);
-    } else {
-      t.geo[3 * s] = u[3 * s] = x;
-      t.geo[3 * s + 1] = u[3 * s + 1] = y;
-      t.geo[3 * s + 2] = u[3 * s + 2] = 0.0;
-    }
-  }
-  t.tile.clear();
-  t.group.clear();
-  for (int64_t a = 0; a < t.ntiles; ++a) t.tile.push_back(gw_bound(u, a * GW_T, std::min(count, (a + 1) * GW_T), metric));
-  for (int64_t g = 0; g < t.ntiles; g += 16)
-    t.group.push_back(gw_bound(u, g * GW_T, std::min(count, (g + 16) * GW_T), metric));
-}
-
-// Per chunk of centres: its tiles and the CSR list (ascending) of neighbour tiles that hold a weight > 0
-struct GwChunk {
-  int64_t first = 0, count = 0, off_tiles = 0, off_cols = 0;
-  GwTiles c;
-};
-
-struct GwPlan {
-  GwTiles nb;
-  std::vector<GwChunk> chunks;
-  std::vector<int> rowptr, cols;     // concatenated over the chunks (rowptr entries relative to the chunk's off_cols)
-  int64_t visited = 0, possible = 0, ctiles = 0;
-  int64_t first = 0;                 // the location range [first, first + count) of an unsorted plan (0 when sorted)
-  bool sorted = false;
-};
-
-// sorted: the centres are ALL locations in the neighbours' Morton order, cut into chunks of `chunk` (a multiple of GW_T)
-// sorted positions, so a chunk's tiles are the neighbour tiles themselves and spatially compact whatever the input order.
-// Otherwise the centres are the locations [first, first + count) as ONE chunk, tiled among themselves.
-static void gw_plan(const double* xy, int64_t n, int64_t first, int64_t count, int64_t chunk, bool sorted, int metric, int kernel,
-                    double bw, GwPlan& plan) {
-  double box[4] = {xy[0], xy[0], xy[1], xy[1]};
-  for (int64_t i = 0; i < n; ++i) {
-    box[0] = std::min(box[0], xy[2 * i]);
-    box[1] = std::max(box[1], xy[2 * i]);
-    box[2] = std::min(box[2], xy[2 * i + 1]);
-    box[3] = std::max(box[3], xy[2 * i + 1]);
-  }
-  gw_tile(xy, 0, n, metric, box, plan.nb);
-  plan.sorted = sorted;
-  plan.first = sorted ? 0 : first;
-  if (!sorted) chunk = count;
-  const int64_t ng = (int64_t)plan.nb.group.size();
-  const int64_t lo = sorted ? 0 : first, hi = sorted ? n : first + count;
-  for (int64_t c0 = lo; c0 < hi; c0 += chunk) {
-    GwChunk ch;
-    ch.first = c0;
-    ch.count = std::min(chunk, hi - c0);
-    ch.off_tiles = plan.ctiles;
-    ch.off_cols = (int64_t)plan.cols.size();
-    if (sorted) {
-      GwTiles& t = ch.c;
-      t.count = ch.count;
-      t.ntiles = (ch.count + GW_T - 1) / GW_T;
-      t.perm.assign(plan.nb.perm.begin() + c0, plan.nb.perm.begin() + c0 + ch.count);
-      t.geo.assign(plan.nb.geo.begin() + 3 * c0, plan.nb.geo.begin() + 3 * (c0 + ch.count));
-      t.tile.assign(plan.nb.tile.begin() + c0 / GW_T, plan.nb.tile.begin() + c0 / GW_T + t.ntiles);
-    } else {
-      gw_tile(xy, c0, ch.count, metric, box, ch.c);
-    }
-    for (int64_t a = 0; a < ch.c.ntiles; ++a) {
-      plan.rowptr.push_back((int)((int64_t)plan.cols.size() - ch.off_cols));
-      for (int64_t g = 0; g < ng; ++g) {
-        if (gw_zero(gw_lower(ch.c.tile[a], plan.nb.group[g], metric), kernel, bw)) continue;
-        for (int64_t t = g * 16; t < std::min(plan.nb.ntiles, (g + 1) * 16); ++t)
-          if (!gw_zero(gw_lower(ch.c.tile[a], plan.nb.tile[t], metric), kernel, bw)) plan.cols.push_back((int)t);
-      }
-    }
-    plan.rowptr.push_back((int)((int64_t)plan.cols.size() - ch.off_cols));
-    plan.ctiles += ch.c.ntiles;
-    plan.possible += ch.c.ntiles * plan.nb.ntiles;
-    plan.chunks.push_back(std::move(ch));
-  }
-  plan.visited = (int64_t)plan.cols.size();
-}
 
 static int gw_check(eofx_ctx* ctx, const eofx_mat* m, const double* xy, int metric, int kernel, double bw) {
   if (!ctx || !m || !xy) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
@@ -6109,13 +5281,6 @@ namespace {
 
 constexpr int SPCA_BATCH = 16;      // iterations enqueued between two reads of the finished flag
 
-// workgroups of a streaming pass over `rows` rows whose partials hold `entries` doubles each: about 128 rows per
-// workgroup, at most SPCA_GMAX, the partials within 32 MiB (a function of the shape alone: results never depend on the device)
-static int spca_grid(int64_t rows, int64_t entries) {
-  const int64_t g = std::min<int64_t>(SPCA_GMAX, std::max<int64_t>(1, (rows + 127) / 128));
-  const int64_t cap = std::max<int64_t>(1, ((int64_t)4 << 20) / std::max<int64_t>(1, entries));
-  return (int)std::max<int64_t>(1, std::min(g, cap));
-}
 
 }  // namespace
 
@@ -6255,18 +5420,22 @@ extern "C" int eofx_lagcov_f64(eofx_ctx* ctx, const float* S, int64_t n, int p, 
   if (!is_device_ptr(S) || !is_device_ptr(M)) return set_err(ctx, EOFX_ERR_ARG, "S and M must be device buffers");
   ENTER(ctx);
   const bool fused = ntau <= LAGCOV_FUSE_NTAU;
-  const int nb = (p + 63) / 64, ny = nb * ((nb + 3) / 4);
-  const int64_t ntiles = (n + LAGCOV_R - 1) / LAGCOV_R;
-  const int G = (int)std::min<int64_t>(ntiles, std::max(1, LAGCOV_WGS / ny));      // a function of the shape alone
-  const size_t nw = (size_t)ntau + 2 * LAGCOV_PADW, pp = (size_t)p * p;
+  std::vector<double> wh((size_t)ntau);
+  if (is_device_ptr(w)) {
+    HIPCHK(hipMemcpyAsync(wh.data(), w, wh.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  } else {
+    std::copy(w, w + ntau, wh.begin());
+  }
+  const FilterPlan pl = lagcov_plan(n, p, wh.data(), ntau);       // the zero-padded copy of the weights (host)
+  const int ny = pl.ny, G = pl.G;
+  const size_t nw = pl.w.size(), pp = (size_t)p * p;
   CHK(arena_reserve(ctx, (nw + pp * G + (fused ? 0 : (size_t)n * p)) * 8 + 3 * 256));
   ArenaScope scope(ctx);
   ARENA(double, wpad, nw);
   ARENA(double, part, pp * G);
   double* Y = nullptr;
-  HIPCHK(hipMemsetAsync(wpad, 0, nw * 8, ctx->stream));
-  HIPCHK(hipMemcpyAsync(wpad + LAGCOV_PADW, w, (size_t)ntau * 8, is_device_ptr(w) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                        ctx->stream));
+  HIPCHK(hipMemcpyAsync(wpad, pl.w.data(), nw * 8, hipMemcpyHostToDevice, ctx->stream));
   if (fused) {
     const size_t lds = LAGCOV_LDS_Y + LAGCOV_LDS_S;
     HIPCHK(hipFuncSetAttribute((const void*)lagcov_cross_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -6286,7 +5455,7 @@ extern "C" int eofx_lagcov_f64(eofx_ctx* ctx, const float* S, int64_t n, int p, 
   hipLaunchKernelGGL(f64_reduce_kernel, dim3((unsigned)((pp + 63) / 64)), dim3(256), 0, ctx->stream, (const double*)part, M,
                      (int64_t)pp, G);
   KCHK();
-  HIPCHK(hipStreamSynchronize(ctx->stream));       // (w may be a pageable host buffer; the arena is handed back)
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // (the staged weights are a pageable host buffer; the arena is handed back)
   return EOFX_OK;
 }
 
@@ -6309,18 +5478,14 @@ extern "C" int eofx_lowpass_cov_f64(eofx_ctx* ctx, const float* S, int64_t n, in
   } else {
     std::copy(w, w + h + 1, wh.begin());
   }
-  const size_t nw = (size_t)2 * h + 1 + 2 * LOWPASS_PADW, pp = (size_t)p * p;
-  std::vector<double> wsh(nw, 0.0);
-  for (int k = -h; k <= h; ++k) wsh[(size_t)(LOWPASS_PADW + h + k)] = wh[(size_t)(k < 0 ? -k : k)];
+  const FilterPlan pl = lowpass_plan(n, p, wh.data(), h);
+  const int ny = pl.ny, G = pl.G;
+  const size_t nw = pl.w.size(), pp = (size_t)p * p;
   const bool own_y = !Y;                           // a caller who wants R alone: Y lives in the arena
-  const int nb = (p + 63) / 64, ny = nb * (nb + 1) / 2;
-  const int64_t ntiles = (n + LOWPASS_R - 1) / LOWPASS_R;
-  const int64_t gmax = std::max<int64_t>(1, std::min<int64_t>(LOWPASS_WGS / ny, LOWPASS_PART_MAX / (int64_t)pp));
-  const int G = (int)std::min<int64_t>(ntiles, gmax);                               // a function of the shape alone
   CHK(arena_reserve(ctx, (nw + (trend ? 2 * (size_t)p : 0) + (R ? pp * G : 0) + (own_y ? (size_t)n * p : 0)) * 8 + 4 * 256));
   ArenaScope scope(ctx);
   ARENA(double, wsym, nw);
-  HIPCHK(hipMemcpyAsync(wsym, wsh.data(), nw * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(wsym, pl.w.data(), nw * 8, hipMemcpyHostToDevice, ctx->stream));
   double* td = nullptr;
   if (trend) {
     td = arena_alloc<double>(ctx, 2 * (size_t)p);
@@ -6415,28 +5580,15 @@ extern "C" int eofx_viewcov_f64(eofx_ctx* ctx, const float* Z, int64_t n, int p,
   } else {
     std::copy(off, off + m + 1, offh.begin());
   }
-  if (offh[0] != 0 || offh[m] != p) return set_err(ctx, EOFX_ERR_ARG, "off must run from 0 to p = %d, got %d .. %d", p, offh[0], offh[m]);
-  for (int v = 0; v < m; ++v)
-    if (offh[v + 1] <= offh[v]) return set_err(ctx, EOFX_ERR_ARG, "off must be strictly increasing (off[%d] = %d, off[%d] = %d)", v, offh[v], v + 1, offh[v + 1]);
-  // the view of every column, and the tiles on or above the diagonal that hold a wanted output
-  std::vector<int> host((size_t)p);
-  for (int v = 0; v < m; ++v) std::fill(host.begin() + offh[v], host.begin() + offh[v + 1], v);
-  const int nb = (p + VIEWCOV_T - 1) / VIEWCOV_T;
-  auto one_view = [&](int b) { return host[(size_t)b * VIEWCOV_T] == host[(size_t)std::min(p, (b + 1) * VIEWCOV_T) - 1]; };
-  int ntiles = 0;
-  for (int bi = 0; bi < nb; ++bi)
-    for (int bj = bi; bj < nb; ++bj) {
-      if (!keep_diag && one_view(bi) && one_view(bj) && host[(size_t)bi * VIEWCOV_T] == host[(size_t)bj * VIEWCOV_T]) continue;
-      host.push_back(bi);
-      host.push_back(bj);
-      ++ntiles;
-    }
-  // the split of the samples: a function of (n, the tile list) alone
-  const int64_t nslabs = (n + VIEWCOV_K - 1) / VIEWCOV_K;
-  int64_t G = ntiles ? std::min<int64_t>(VIEWCOV_WGS / ntiles, nslabs / VIEWCOV_SPLIT_SLABS) : 1;
-  G = std::max<int64_t>(G, 1);
-  const int64_t chunk = (nslabs + G - 1) / G;
-  G = (nslabs + chunk - 1) / chunk;                // (no empty split)
+  ViewcovPlan pl;      // the view of every column, the tiles that hold a wanted output, the split of the samples
+  int v = 0;
+  const int bad = viewcov_plan(n, p, offh.data(), m, keep_diag != 0, pl, &v);
+  if (bad == VIEWCOV_OFF_ENDS) return set_err(ctx, EOFX_ERR_ARG, "off must run from 0 to p = %d, got %d .. %d", p, offh[0], offh[m]);
+  if (bad == VIEWCOV_OFF_ORDER)
+    return set_err(ctx, EOFX_ERR_ARG, "off must be strictly increasing (off[%d] = %d, off[%d] = %d)", v, offh[v], v + 1, offh[v + 1]);
+  const std::vector<int>& host = pl.host;
+  const int ntiles = pl.ntiles;
+  const int64_t nslabs = pl.nslabs, G = pl.G, chunk = pl.chunk;
   const bool split = G > 1;
   const size_t npart = split ? (size_t)ntiles * G * VIEWCOV_TT : 0;
   CHK(arena_reserve(ctx, host.size() * sizeof(int) + npart * 8 + 2 * 256));

@@ -27,8 +27,6 @@
 
 namespace eofx {
 
-constexpr int GR_BM = 256;                 // tile rows = tile columns
-constexpr int GR_BK = 32;                  // features per stage: one 128-byte line {hi[32], lo[32]} per row
 constexpr int GR_OP_BYTES = GR_BM * 128;   // one operand tile of one stage: 32 KiB
 constexpr int GR_STAGE_BYTES = 2 * GR_OP_BYTES;
 

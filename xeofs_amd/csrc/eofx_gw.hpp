@@ -16,14 +16,13 @@
 #pragma once
 #include "eofx.h"
 #include "eofx_kernels.hpp"
+#include "eofx_gwplan.hpp"    // GW_T, GW_EARTH_RADIUS
 
 namespace eofx {
 
-constexpr int GW_T = 16;          // locations per tile (one weight per thread for a 16 x 16 tile pair)
 constexpr int GW_R = 8;           // accumulators per thread of gw_cov_kernel (256 * GW_R packed entries per workgroup)
 constexpr int GW_PMAX = 256;      // features: the neighbour tile [GW_T x (p + 1)] float64 must fit in LDS
 constexpr int GW_EIG_PMAX = 64;   // gw_syev_kernel: a [64 x 65] matrix and eigenvectors in LDS
-constexpr double GW_EARTH_RADIUS = 6371.0;   // xeofs/utils/constants.py AVG_EARTH_RADIUS, km
 
 // geo[3 s + .]: {lon, lat (radians), cos lat} for haversine, {x, y, 0} for euclidean
 __device__ __forceinline__ double gw_weight(const double* gi, const double* gj, int metric, int kernel, double bw) {

@@ -25,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "eofx_hilbert_host.hpp"    // hfft::position_frequency, HFFT_MAX_LOG2
+
 #ifndef HFFT_WAVES
 #define HFFT_WAVES 4
 #endif
@@ -269,25 +271,6 @@ template <int RL, int DIR> __device__ __forceinline__ void outer_stage(cf* e, co
     HFFT_B8(0) HFFT_B8(1)
 #undef HFFT_B8
   }
-}
-
-// Frequency held by LDS position pos after the forward stages (host side: order of the filter table)
-inline int64_t position_frequency(int L, int64_t pos) {
-  const int rl_bits = L & 3;
-  int64_t k = 0, weight = 1, span = (int64_t)1 << L;
-  if (rl_bits) {
-    span >>= rl_bits;
-    k += (pos / span) * weight;
-    pos %= span;
-    weight <<= rl_bits;
-  }
-  while (span > 1) {
-    span >>= 4;
-    k += (pos / span) * weight;
-    pos %= span;
-    weight <<= 4;
-  }
-  return k;
 }
 
 // L = log2 P in [10, 14].  One workgroup of NT = P/16 threads owns a pair of features (persistent over pairs).

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "eofx_mfma64.hpp"
+#include "eofx_plans.hpp"    // ATB_KG, ATB_BM, AXB_KG, AXB_BM
 
 namespace eofx {
 
@@ -75,9 +76,7 @@ __device__ __forceinline__ void amax_commit(float mx, unsigned* __restrict__ ama
 //   Per wave and 2 k-rows: 1 KiB of A -> 4*NB MFMAs (64 cycles each on its SIMD).
 // ---------------------------------------------------------------------------------
 constexpr int ATB_KC = 16;    // k-rows per pipeline stage (slab)
-constexpr int ATB_KG = 32;    // K granularity: slabs are consumed in pairs
 constexpr int ATB_WM = 128;   // A columns per wave
-constexpr int ATB_BM = 512;   // A columns per workgroup
 
 template <int NB>
 __global__ __launch_bounds__(256, 2) void atb_f32_kernel(const float* __restrict__ A, int64_t lda,
@@ -678,8 +677,6 @@ __global__ __launch_bounds__(256, NB > 2 ? 1 : 2) void atb_f16_kernel(const floa
 //   Rows >= a_rows read the last row and write zeros; 16-byte feature chunks >= a_cols read chunk 0 (their scale is 0).
 // ---------------------------------------------------------------------------------
 constexpr int AXB_KC = 32;    // features per slab
-constexpr int AXB_KG = 64;    // K granularity: slabs are consumed in pairs
-constexpr int AXB_BM = 256;   // rows per workgroup
 constexpr int AXB_LDA = 32;   // halves per staged row: 64 bytes = four 16-byte chunks, chunk c of row r stored at c ^ ((r >> 1) & 3)
 
 // DBG (tools/probes/axb_probe.hip only): 1 no MFMA, 2 no conversion either, 4 no B / map loads, 8 cached A loads,

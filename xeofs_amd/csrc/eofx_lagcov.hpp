@@ -24,14 +24,8 @@
 
 namespace eofx {
 
-constexpr int LAGCOV_PMAX = 1024;        // columns of S (the partials stay within 8 workgroups x 8 MiB at the limit)
-constexpr int LAGCOV_R = 64;             // samples per row tile
-constexpr int LAGCOV_WIN = 16;           // outputs per thread of the sliding window
-constexpr int LAGCOV_PADW = LAGCOV_WIN - 1;
-constexpr int LAGCOV_FUSE_NTAU = 65;     // a row tile and its ntau - 1 halo rows fit the 128 staged rows up to here
 constexpr int LAGCOV_SROWS = LAGCOV_R + LAGCOV_FUSE_NTAU - 1;      // 128 staged rows of 64 float32
 constexpr int LAGCOV_YLD = 80;           // row stride of the Y tile in doubles: rows 4 s + lk, lk = 0, 1 on disjoint banks
-constexpr int LAGCOV_WGS = 512;          // workgroups aimed at (two per CU fit the LDS of the fused kernel)
 constexpr size_t LAGCOV_LDS_Y = (size_t)LAGCOV_R * LAGCOV_YLD * sizeof(double);
 constexpr size_t LAGCOV_LDS_S = (size_t)LAGCOV_SROWS * 64 * sizeof(float);
 

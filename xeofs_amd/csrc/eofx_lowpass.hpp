@@ -30,12 +30,7 @@
 
 namespace eofx {
 
-constexpr int LOWPASS_R = 64;             // samples per row tile
-constexpr int LOWPASS_WIN = 16;           // outputs per thread of the sliding window
-constexpr int LOWPASS_PADW = LOWPASS_WIN - 1;
 constexpr int LOWPASS_YLD = LAGCOV_YLD;   // row stride of a Y tile in doubles
-constexpr int LOWPASS_WGS = 512;          // workgroups aimed at (two per CU)
-constexpr int64_t LOWPASS_PART_MAX = (int64_t)1 << 23;      // doubles of partials (64 MiB)
 constexpr size_t LOWPASS_LDS_Y = (size_t)2 * LOWPASS_R * LOWPASS_YLD * sizeof(double);
 
 // the mirrored sample of u, or -1 where one reflection does not land in 0 .. n - 1 (rows no stored output reads)

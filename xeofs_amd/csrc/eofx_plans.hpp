@@ -1,0 +1,360 @@
+// eofx_plans.hpp -- every launch plan of the engine, stated once: split factors, tile lists, grid sizes, route predicates and the
+// small host tables that go with a launch.  A plan here is a function of the SHAPE alone (plus the documented getenv tuning
+// hooks): plain C++17, no HIP, no context, so the host compiler builds it alone and tests/test_plans_cpu.py runs it without a GPU
+// (tests/plans_shim.cpp) -- next to the Python restatements the GPU route tests choose their shapes with.  eofx_abi.hip keeps the
+// launches, copies, caches and error reporting.  Constants that both a kernel and a plan need are defined here; the kernel
+// headers include this one.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstdlib>
+#include <vector>
+
+#include "eofx.h"
+
+namespace eofx {
+
+// ---- tile sizes shared with the kernels ----------------------------------------------------------------------------------
+constexpr int ATB_KG = 32;    // atb kernels: K granularity (slabs are consumed in pairs)
+constexpr int ATB_BM = 512;   // atb kernels: A columns per workgroup
+constexpr int AXB_KG = 64;    // axb kernels: K granularity (slabs are consumed in pairs)
+constexpr int AXB_BM = 256;   // axb kernels: rows per workgroup
+constexpr int GR_BM = 256;    // NT kernel (eofx_gram.hpp): tile rows = tile columns
+constexpr int GR_BK = 32;     // NT kernel: features per stage, one 128-byte line {hi[32], lo[32]} per row
+constexpr int64_t EOFX_GRAM_MAX_SIDE = 32768;
+constexpr int SPCA_GMAX = 2048;     // workgroups of the streaming passes of eofx_spca.hpp (a function of the shape only)
+constexpr int VIEWCOV_T = 128;           // rows and columns of C per tile (64 per wave)
+constexpr int VIEWCOV_K = 16;            // samples per slab
+constexpr int VIEWCOV_WGS = 512;         // workgroups aimed at; also the bound of the partial blocks
+constexpr int VIEWCOV_SPLIT_SLABS = 16;  // a split takes at least this many slabs (256 samples)
+constexpr int LAGCOV_PMAX = 1024;        // columns of S (the partials stay within 8 workgroups x 8 MiB at the limit)
+constexpr int LAGCOV_R = 64;             // samples per row tile
+constexpr int LAGCOV_WIN = 16;           // outputs per thread of the sliding window
+constexpr int LAGCOV_PADW = LAGCOV_WIN - 1;
+constexpr int LAGCOV_FUSE_NTAU = 65;     // a row tile and its ntau - 1 halo rows fit the 128 staged rows up to here
+constexpr int LAGCOV_WGS = 512;          // workgroups aimed at (two per CU fit the LDS of the fused kernel)
+constexpr int LOWPASS_R = 64;             // samples per row tile
+constexpr int LOWPASS_WIN = 16;           // outputs per thread of the sliding window
+constexpr int LOWPASS_PADW = LOWPASS_WIN - 1;
+constexpr int LOWPASS_WGS = 512;          // workgroups aimed at (two per CU)
+constexpr int64_t LOWPASS_PART_MAX = (int64_t)1 << 23;      // doubles of partials (64 MiB)
+// Lags are processed in groups whose side-by-side sample panel is at most this many columns wide: the wide product then
+// stays on the wide-panel kernels (the MFMA NT kernel of eofx_gram.hpp from 512 columns, the 128-column streaming tiles
+// below) while E = 100 lags of a 64-column panel do not ask for a 6400-column intermediate.  The field is read once
+// per group.
+constexpr int EOFX_LAG_GROUP_COLS = 1024;
+
+inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+// ---- the two streaming products ------------------------------------------------------------------------------------------
+struct AtbPlan {
+  int S;
+  int64_t kps;
+};
+// split-K factor from a small cost model: 512 resident workgroups, ~10 GB/s of A per
+// workgroup slot, partial-sum traffic at ~4 TB/s.
+// 128-column tiles (atb_f16_kernel<4>, one workgroup per CU): the wide products (Gram matrices, PCA panels) and the
+// two-matrix form of a 128-column complex panel (33-64 complex columns: Re and Im are then streamed ONCE per pass)
+// (round 3: also the single-matrix passes of sketches of 65 columns and more -- EOF with 55+ modes: one 128-column launch at
+// 4.3 TB/s beats two 64-column launches at 6.5 TB/s: 229.7 -> 205.6 ms per rSVD at k = 100, config-4 size)
+inline bool atb_wide(int L) {
+  if (const char* ev = std::getenv("EOFX_ATB_WIDE_MIN")) return L >= atoi(ev);   // tuning hook (tools/wide_sketch_probe.py)
+  return L >= 96;       // (96 columns: one partial 128-column tile, see atb_tiles)
+}
+inline AtbPlan atb_plan(int64_t M, int64_t K, int L, bool wide = false) {
+  const int bx = (int)(M / ATB_BM);
+  const int bz = wide ? (L + 127) / 128 : (L + 63) / 64;
+  const double resident = wide ? 256.0 : 512.0;
+  AtbPlan best{1, K};
+  double best_t = 1e30;
+  for (int S = 1; S <= 128; ++S) {
+    const int64_t kps = round_up((K + S - 1) / S, ATB_KG);
+    const int s_eff = (int)((K + kps - 1) / kps);
+    if (s_eff != S) continue;
+    const double blocks = (double)bx * bz * s_eff;
+    const double rounds = std::ceil(blocks / resident);
+    double t = rounds * (double)kps * 2048.0 / 1.0e10;
+    if (s_eff > 1) t += (2.0 * s_eff + 1.0) * (double)M * L * 4.0 / 4.0e12;
+    if (t < best_t * 0.98) {
+      best_t = t;
+      best = {s_eff, kps};
+    }
+  }
+  return best;
+}
+// axb_f16_kernel (the in-place sample-side product): rows_pad / 256 row tiles x S feature splits.  S = 1 when the row
+// tiles alone fill the chip, otherwise a multiple of 8 (one split per XCD at a time) from the same kind of cost model.
+inline AtbPlan axb_plan(int64_t rows_pad, int64_t K) {
+  const int64_t rt = rows_pad / AXB_BM;
+  const int64_t units = K / AXB_KG;
+  if (rt >= 1024 || units < 16) return {1, K};
+  if (const char* ev = std::getenv("EOFX_AXB_SPLITS")) {   // tuning hook (tools/atb_probe.py)
+    const int want = std::max(8, atoi(ev) / 8 * 8);
+    const int64_t kps = round_up((units + want - 1) / want, 1) * AXB_KG;
+    return {(int)((K + kps - 1) / kps), kps};
+  }
+  AtbPlan best{1, K};
+  double best_t = 1e30;
+  for (int s8 = 1; s8 <= 32 && 8 * s8 <= units; ++s8) {
+    const int S = 8 * s8;
+    const int64_t kps = (units + S - 1) / S * AXB_KG;
+    const int s_eff = (int)((K + kps - 1) / kps);
+    if (s_eff > S || s_eff <= S - 8) continue;
+    const double rounds = std::ceil((double)rt * s8 / 64.0);          // 64 resident workgroups per XCD
+    double t = rounds * (double)kps * 1024.0 / 1.25e10;               // 256 rows x 4 B per feature, ~12.5 GB/s per slot
+    t += (2.0 * s_eff + 1.0) * (double)rows_pad * 64.0 * 4.0 / 4.0e12;
+    if (t < best_t * 0.98) {
+      best_t = t;
+      best = {s_eff, kps};
+    }
+  }
+  return best;
+}
+inline size_t atb_scratch_bytes(int64_t M, int64_t K, int L) {
+  const AtbPlan pl = atb_plan(M, K, L), plw = atb_plan(M, K, L, true);
+  const int smax = std::max(pl.S, atb_wide(L) ? plw.S : 1);
+  size_t b = smax > 1 ? (size_t)smax * M * L * (sizeof(float) + sizeof(double)) + 4096 : 4096;   // f32 or f64 partials
+  const AtbPlan px = axb_plan(M, round_up(K, AXB_KG));      // in case M is the sample side of an in-place matrix
+  if (px.S > 1) b = std::max(b, (size_t)px.S * M * round_up(L, 64) * sizeof(float) + 4096);
+  return b;
+}
+
+// Column tiles of a panel of L columns (a multiple of 32), in launch order: `count` adjacent tiles of `width` columns from
+// column `col_base` on are ONE launch (every launch reads the field once).
+// wide (the split-fp16 atb kernel from atb_wide on): full 128-column tiles, then -- when 96 columns are left (panels of
+// 96 / 224 columns) -- ONE partial wide tile (width 96) instead of a 64- and a 32-column launch, then the 64 / 32-column rests;
+// otherwise (other precisions, the in-place X Y of launch_axb): 64-column tiles and one of 32.
+struct ColTile {
+  int width, col_base, count;
+};
+struct ColTiles {
+  int n = 0;
+  ColTile t[4];
+  int columns() const {      // tiles in all: every one of them reads the field once
+    int c = 0;
+    for (int i = 0; i < n; ++i) c += t[i].count;
+    return c;
+  }
+};
+inline ColTiles atb_tiles(int L, bool wide) {
+  ColTiles out;
+  const int n4 = wide ? L / 128 : 0;
+  const int part4 = (wide && L - 128 * n4 == 96) ? 96 : 0;
+  const int cb4 = 128 * n4 + part4;
+  const int nfull = (L - cb4) / 64, rem = (L - cb4) % 64;
+  if (n4 > 0) out.t[out.n++] = {128, 0, n4};
+  if (part4) out.t[out.n++] = {96, 128 * n4, 1};
+  if (nfull > 0) out.t[out.n++] = {64, cb4, nfull};
+  if (rem) out.t[out.n++] = {32, cb4 + nfull * 64, 1};
+  return out;
+}
+
+// ---- further rules -------------------------------------------------------------------------------------------------------
+// number of row-strided partial Gram matrices: >= 4 slabs of 32 rows per workgroup for the narrow
+// (sketch-width) panels; wide panels already expose (L/64)^2 sub-blocks, so fewer partials (<= 64 MB)
+inline int gram_parts(int64_t rows, int L) {
+  // workgroups along the rows; every workgroup writes one partial (L x L float64):
+  // >= 8 k-steps (32 rows) per wave, <= 128 MB of partials (a 130 000 x 1536 panel, 300 sub-blocks: 3 row parts 8.9 ms,
+  // 6 .. 24 parts 7.1 ms -- tools/wide_small_probe.py)
+  // (one workgroup per CU: the products run at the fp64 MFMA rate either way -- ~45 TFLOP/s here -- and every further
+  // partial is 8 L^2 bytes written and read again: 194 / 210 / 243 us for 256 / 512 / 1024 partials of a 1M x 64 panel)
+  const int64_t by_rows = std::min<int64_t>((rows + 127) / 128, 256);
+  const int64_t by_mem = ((int64_t)128 << 20) / ((int64_t)L * L * 8);
+  if (const char* ev = std::getenv("EOFX_GRAM_PARTS")) return std::max(1, atoi(ev));   // tuning hook (tools/small_kernel_probe.py)
+  return (int)std::max<int64_t>(1, std::min(by_rows, std::max<int64_t>(by_mem, 1)));
+}
+
+inline int rsvd_auto_iters(int k, int64_t n, int64_t p) {
+  // sklearn extmath._randomized_svd: n_iter = 7 if n_components < 0.1 * min(M.shape) else 4
+  return ((double)k < 0.1 * (double)std::min(n, p)) ? 7 : 4;
+}
+
+constexpr size_t EOFX_ORTH_TALL_BYTES = (size_t)16 << 20;
+// Is the tall panel re-normalised between the two products of a power iteration?  scikit-learn normalises after EVERY
+// product; leaving that step out is exact in exact arithmetic, but one iteration then squares sigma_1 / sigma_l inside
+// the float32 panel and the Cholesky-QR that follows squares it again: modes more than ~500x below the leading one
+// drift from the float64 reference (6e-5 at 1370x, lost beyond 4000x; with the step 8e-6 at 41000x, tests
+// test_peaked_spectrum_*).  The step costs 0.85 ms per iteration at config 4 (4 % of a fit), so:
+//   * always: small tall panels (<= 16 MiB: microseconds), the float64 mode, and the FIRST iteration of every fit;
+//   * afterwards only where it matters: after the first iteration the small-side Gram matrix W^T W is a Rayleigh
+//     quotient of X X^T on an orthonormal basis; if the square root of the ratio of its extreme eigenvalues
+//     (~ sigma_1 / sigma_l) exceeds hostla::PEAKED_RATIO the remaining iterations keep the step.
+// ONE rule (eofx_orth_tall_rule / eofx_peaked_spectrum) for the C++ drivers and the panel-level (sharded) driver.
+inline bool orth_tall_rule(int64_t tall_pad, int L, int prec_power) {
+  if (std::getenv("EOFX_FORCE_ORTH_TALL")) return true;    // experiments (tools/cond_study.py)
+  return prec_power == EOFX_PREC_F64 || (size_t)tall_pad * L * sizeof(float) <= EOFX_ORTH_TALL_BYTES;
+}
+
+// the lag operator: lags per group (see EOFX_LAG_GROUP_COLS), the lags of the last group, workgroups of its streaming kernels
+inline int lag_groupsize(int E, int L) { return std::max(1, std::min(E, EOFX_LAG_GROUP_COLS / std::max(L, 1))); }
+inline int lag_last_group(int E, int G) { return E - (E - 1) / G * G; }
+inline int lag_blocks(int64_t total4) { return (int)std::max<int64_t>(1, std::min<int64_t>((total4 + 255) / 256, 8192)); }
+
+// workgroups of a streaming pass of eofx_spca.hpp over `rows` rows whose partials hold `entries` doubles each: about 128 rows per
+// workgroup, at most SPCA_GMAX, the partials within 32 MiB (a function of the shape alone: results never depend on the device)
+inline int spca_grid(int64_t rows, int64_t entries) {
+  const int64_t g = std::min<int64_t>(SPCA_GMAX, std::max<int64_t>(1, (rows + 127) / 128));
+  const int64_t cap = std::max<int64_t>(1, ((int64_t)4 << 20) / std::max<int64_t>(1, entries));
+  return (int)std::max<int64_t>(1, std::min(g, cap));
+}
+
+// Shape predicates of the routes through the NT kernel of eofx_gram.hpp (`has_source`: the matrix holds a layout the route can
+// read; the 2^32 bounds are the 32-bit row offsets of the LDS-DMA loads).
+// the fast Gram route of a matrix of n_pad x p (sample side up to 32768)
+inline bool gram_fast_ok(int64_t n_pad, int64_t p, bool has_source) {
+  return n_pad % GR_BM == 0 && n_pad <= EOFX_GRAM_MAX_SIDE && has_source && round_up(p, 2 * GR_BK) * 4 * GR_BM < ((int64_t)1 << 32) &&
+         !std::getenv("EOFX_NO_FAST_GRAM");
+}
+// wide feature-side products Yp [p_pad x L] = X'^T Zn (L in the hundreds: the PCA pre-reduction's 1500-column panel took 83 ms
+// through the 128-column streaming tiles, the field re-read 12 times at a third of the matrix cores' rate; through the NT
+// kernel: transposed planes of the field once, planes of Zn^T, one MFMA-bound product)
+inline bool tmul_nt_ok(int64_t n, int64_t p_pad, bool has_source, int L) {
+  const int64_t kpad = round_up(n, 2 * GR_BK);
+  return L >= 512 && p_pad % GR_BM == 0 && has_source && kpad * 4 * GR_BM < ((int64_t)1 << 32) && n >= 512 &&
+         !std::getenv("EOFX_NO_TMUL_NT");
+}
+// out[rows x Lo] = P[rows x L] Mx[L x Lo] for WIDE operands
+inline bool matmul_nt_ok(int64_t rows, int L, int Lo) {
+  const int64_t kpad = round_up(L, 2 * GR_BK);
+  return L >= 512 && Lo >= 256 && Lo % 4 == 0 && L % 4 == 0 && rows >= 1024 && rows % GR_BM == 0 &&
+         kpad * 4 * GR_BM < ((int64_t)1 << 32) && !std::getenv("EOFX_NO_MATMUL_NT");
+}
+// the statistics-carrying first pass of the fused fit (eofx_fit.hpp): in-place layout, the f16x3 passes, a 16-byte aligned field
+inline bool fit_first_eligible(int keep_raw, int prec_power, bool aligned16, int64_t n, int64_t P, int l) {
+  return keep_raw == 2 && prec_power == EOFX_PREC_F16X3 && n < P && l > 0 && l < n && round_up(l, 32) <= 64 && l % 32 != 0 &&
+         P % 4 == 0 && aligned16 && n < ((int64_t)1 << 31) && !std::getenv("EOFX_NO_FUSED_FIT");
+}
+
+// ---- preprocessing statistics ----------------------------------------------------------------------------------------------
+// The column statistics of an n x P field (row stride ld): four features per thread and 16-byte loads where the field allows
+// (vec4), RS row splits of rps rows so that about 2048 workgroups run.  sample_raw: the Hilbert stage follows on an in-place
+// matrix (the sample-raw request of the context) and its one-kernel route takes this length two features at a time: the pass then also writes
+// the raw field in the sample-contiguous layout (tr, colstats_tr_kernel, which moves 64 x 64 tiles) instead of a separate
+// transposing copy behind the statistics pass.
+struct ColstatsPlan {
+  bool vec4, tr;
+  int gxs, gx;         // workgroups along the features: one thread per feature (shift, finalize) / of the statistics kernel
+  int64_t RS, rps;
+};
+inline ColstatsPlan colstats_plan(int64_t n, int64_t P, int64_t ld, bool aligned16, bool sample_raw, bool row_map) {
+  ColstatsPlan pl;
+  pl.vec4 = P % 4 == 0 && ld % 4 == 0 && aligned16;
+  pl.gxs = (int)((P + 255) / 256);
+  pl.gx = pl.vec4 ? (int)((P / 4 + 255) / 256) : pl.gxs;
+  int64_t RS = std::max<int64_t>(1, (2048 + pl.gx - 1) / pl.gx);
+  RS = std::min<int64_t>(RS, std::max<int64_t>(1, n / 64));
+  pl.rps = (n + RS - 1) / RS;
+  if (sample_raw && !row_map) pl.rps = round_up(pl.rps, 64);
+  pl.RS = (n + pl.rps - 1) / pl.rps;
+  pl.tr = pl.vec4 && !row_map && sample_raw && round_up(n, ATB_BM) <= 8192 && pl.rps % 64 == 0;
+  return pl;
+}
+inline size_t colstats_scratch(int64_t n, int64_t P) {
+  const int64_t gx = std::max<int64_t>(1, (P / 4 + 255) / 256);   // the four-features-per-thread kernel: fewer workgroups, more row splits
+  int64_t RS = std::max<int64_t>(1, (2048 + gx - 1) / gx);      // (fewer than four features: gx was 0 -- a division by zero, round 5)
+  RS = std::min<int64_t>(RS, std::max<int64_t>(1, n / 64));
+  return (size_t)(RS + 1) * P * 32 + (size_t)P * 72 + (size_t)n * 16 + (1 << 20);
+}
+// workgroups of feature_summary_kernel
+inline int summary_blocks(int64_t P) { return (int)std::max<int64_t>(1, std::min<int64_t>((P + 4095) / 4096, 256)); }
+
+// apply_kernel<true> (16-byte loads): no column map, a row stride of whole float4, an aligned source
+inline bool apply_vec(bool col_map, int64_t ld_src, bool aligned16) { return !col_map && ld_src % 4 == 0 && aligned16; }
+
+// The layout a preprocessed matrix ends in (pv of P features and ns of n samples hold data; keep_raw / allow_masked: the layout
+// asked for through the context's layout mode; stats_absmax: the column statistics of THIS field are at hand).
+// raw mode: nothing is dropped or reordered, so the raw field itself -- read through the affine map -- is the feature-contiguous
+// layout; only the sample-contiguous one is written (not even that in place).  P < 2^31 rows: int.
+// masked in place (layout mode 3): all-NaN grid points (sanitizer.py:80-126 would drop them) stay in the matrix as zero
+// columns -- scale 0 in the map, bits ANDed to +0 by the MASK kernels -- when they are a minority and the sketch lives
+// on the sample side; a zero column changes no product, Gram matrix or norm, so the factors are those of the compacted
+// matrix with zero rows in V at the masked features (the caller drops them).  1x the field in HBM instead of 3x.
+struct ApplyPlan {
+  bool raw, masked, in_place;
+  bool col_map, vec;          // the written layouts: features are compacted through a column map / apply_kernel<true>
+};
+inline ApplyPlan apply_plan(int64_t n, int64_t P, int64_t pv, int64_t ns, int keep_raw, bool allow_masked, bool stats_absmax,
+                            bool aligned16) {
+  ApplyPlan pl;
+  const bool raw_ok = keep_raw && ns == n && P % 4 == 0 && aligned16 && n < ((int64_t)1 << 31);
+  pl.masked = raw_ok && keep_raw == 2 && allow_masked && stats_absmax && pv < P && 10 * pv >= 6 * P && n < pv;
+  pl.raw = (raw_ok && pv == P) || pl.masked;
+  pl.in_place = pl.raw && keep_raw == 2;
+  pl.col_map = pv < P && !pl.masked;
+  pl.vec = !pl.in_place && apply_vec(pl.col_map, P, aligned16);
+  return pl;
+}
+
+// ---- block cross-covariance of multi-view CCA (eofx_viewcov.hpp) ---------------------------------------------------------
+// off[0 .. m]: the first column of every view.  host = the view of every column, then (bi, bj) of every 128-tile on or above the
+// diagonal that holds a wanted output (keep_diag, or two different views); the samples are cut into G splits of `chunk` slabs:
+// a function of (n, the tile list) alone, no split empty.
+struct ViewcovPlan {
+  std::vector<int> host;      // [p] views, [2 ntiles] tiles
+  int ntiles = 0;
+  int64_t nslabs = 0, G = 1, chunk = 0;
+};
+enum { VIEWCOV_OFF_OK = 0, VIEWCOV_OFF_ENDS = 1, VIEWCOV_OFF_ORDER = 2 };
+// -> VIEWCOV_OFF_OK, or what is wrong with off (*bad_view: the view v with off[v + 1] <= off[v])
+inline int viewcov_plan(int64_t n, int p, const int* off, int m, bool keep_diag, ViewcovPlan& pl, int* bad_view = nullptr) {
+  if (off[0] != 0 || off[m] != p) return VIEWCOV_OFF_ENDS;
+  for (int v = 0; v < m; ++v)
+    if (off[v + 1] <= off[v]) {
+      if (bad_view) *bad_view = v;
+      return VIEWCOV_OFF_ORDER;
+    }
+  std::vector<int>& host = pl.host;
+  host.assign((size_t)p, 0);
+  for (int v = 0; v < m; ++v) std::fill(host.begin() + off[v], host.begin() + off[v + 1], v);
+  const int nb = (p + VIEWCOV_T - 1) / VIEWCOV_T;
+  auto one_view = [&](int b) { return host[(size_t)b * VIEWCOV_T] == host[(size_t)std::min(p, (b + 1) * VIEWCOV_T) - 1]; };
+  pl.ntiles = 0;
+  for (int bi = 0; bi < nb; ++bi)
+    for (int bj = bi; bj < nb; ++bj) {
+      if (!keep_diag && one_view(bi) && one_view(bj) && host[(size_t)bi * VIEWCOV_T] == host[(size_t)bj * VIEWCOV_T]) continue;
+      host.push_back(bi);
+      host.push_back(bj);
+      ++pl.ntiles;
+    }
+  pl.nslabs = (n + VIEWCOV_K - 1) / VIEWCOV_K;
+  int64_t G = pl.ntiles ? std::min<int64_t>(VIEWCOV_WGS / pl.ntiles, pl.nslabs / VIEWCOV_SPLIT_SLABS) : 1;
+  G = std::max<int64_t>(G, 1);
+  pl.chunk = (pl.nslabs + G - 1) / G;
+  pl.G = (pl.nslabs + pl.chunk - 1) / pl.chunk;                // (no empty split)
+  return VIEWCOV_OFF_OK;
+}
+
+// ---- filter covariances (eofx_lagcov.hpp, eofx_lowpass.hpp) ----------------------------------------------------------------
+// ny tile pairs of 64 columns x G splits of the row tiles (a function of the shape alone), and the weights as the kernels'
+// sliding windows read them: zero-padded by WIN - 1 on either side.
+struct FilterPlan {
+  int ny, G;
+  std::vector<double> w;
+};
+// w[0 .. ntau): wpad[15 + tau] = w[tau]
+inline FilterPlan lagcov_plan(int64_t n, int p, const double* w, int ntau) {
+  FilterPlan pl;
+  const int nb = (p + 63) / 64;
+  pl.ny = nb * ((nb + 3) / 4);
+  const int64_t ntiles = (n + LAGCOV_R - 1) / LAGCOV_R;
+  pl.G = (int)std::min<int64_t>(ntiles, std::max(1, LAGCOV_WGS / pl.ny));
+  pl.w.assign((size_t)ntau + 2 * LAGCOV_PADW, 0.0);
+  std::copy(w, w + ntau, pl.w.begin() + LAGCOV_PADW);
+  return pl;
+}
+// w[0 .. h]: the symmetric wsym[15 + h + k] = w[|k|], k = -h .. h
+inline FilterPlan lowpass_plan(int64_t n, int p, const double* w, int h) {
+  FilterPlan pl;
+  const int nb = (p + 63) / 64;
+  pl.ny = nb * (nb + 1) / 2;
+  const int64_t ntiles = (n + LOWPASS_R - 1) / LOWPASS_R;
+  const int64_t gmax = std::max<int64_t>(1, std::min<int64_t>(LOWPASS_WGS / pl.ny, LOWPASS_PART_MAX / ((int64_t)p * p)));
+  pl.G = (int)std::min<int64_t>(ntiles, gmax);
+  pl.w.assign((size_t)2 * h + 1 + 2 * LOWPASS_PADW, 0.0);
+  for (int k = -h; k <= h; ++k) pl.w[(size_t)(LOWPASS_PADW + h + k)] = w[(size_t)(k < 0 ? -k : k)];
+  return pl;
+}
+
+}  // namespace eofx

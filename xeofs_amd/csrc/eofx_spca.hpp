@@ -25,7 +25,6 @@ constexpr int SPCA_KMAX = 64;       // modes of the kernel route
 constexpr int SPCA_LMAX = 128;      // columns of V (k + oversample, or min(n, p) on the exact route)
 constexpr int SPCA_R = 32;          // rows of V and B staged per chunk in spca_update_kernel
 constexpr int SPCA_ACC = SPCA_LMAX * SPCA_KMAX / 256;   // entries of P' per thread
-constexpr int SPCA_GMAX = 2048;     // workgroups of the streaming passes (a function of the shape only)
 constexpr int SPCA_GRAM_E = 8;      // entries of X^T Y per thread of spca_gram_kernel
 
 // ctl[] of the loop state (device, int): finished flag, iterations completed

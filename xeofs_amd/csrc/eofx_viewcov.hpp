@@ -33,12 +33,8 @@ namespace eofx {
 
 constexpr int VIEWCOV_PMAX = 4096;       // columns of Z
 constexpr int VIEWCOV_MMAX = 64;         // views
-constexpr int VIEWCOV_T = 128;           // rows and columns of C per tile (64 per wave)
-constexpr int VIEWCOV_K = 16;            // samples per slab
 constexpr int VIEWCOV_LD = VIEWCOV_T + 16;             // row stride of a slab in doubles
 constexpr int VIEWCOV_E = VIEWCOV_K * VIEWCOV_T / 256; // elements of one slab per thread (8: one column, every other row)
-constexpr int VIEWCOV_WGS = 512;         // workgroups aimed at; also the bound of the partial blocks
-constexpr int VIEWCOV_SPLIT_SLABS = 16;  // a split takes at least this many slabs (256 samples)
 constexpr int64_t VIEWCOV_TT = (int64_t)VIEWCOV_T * VIEWCOV_T;
 
 // grid (ceil(p / 256), p), block 256: row blockIdx.y
