@@ -16,8 +16,9 @@ using namespace eofx;
 extern "C" {
 // ---- eofx_plans.hpp
 void pl_constants(int* out) {
-  const int c[] = {ATB_BM, ATB_KG, AXB_BM, AXB_KG, EOFX_LAG_GROUP_COLS, VIEWCOV_T, VIEWCOV_WGS, LAGCOV_PADW, LOWPASS_PADW, GW_T};
-  std::copy(c, c + 10, out);
+  const int c[] = {ATB_BM, ATB_KG, AXB_BM, AXB_KG, EOFX_LAG_GROUP_COLS, VIEWCOV_T, VIEWCOV_WGS, LAGCOV_PADW, LOWPASS_PADW, GW_T,
+                   KRYLOV_MAX_ORDER, C64_IT_MIN, C64_IT_CAP};
+  std::copy(c, c + 13, out);
 }
 int pl_atb_wide(int L) { return atb_wide(L) ? 1 : 0; }
 // widths of the tiles in launch order (96: the partial 128-column tile) -> their number
@@ -102,6 +103,19 @@ int pl_lowpass_plan(int64_t n, int p, const double* w, int h, double* wsym, int*
   nyG[0] = pl.ny;
   nyG[1] = pl.G;
   return (int)pl.w.size();
+}
+
+// out [19]: status, r, l, adaptive, n_iter, auto_count, h, LP, ko, Lo, transposed, small, small_pad, tall_pad, big, krylov, nbmax,
+// ldk, arena_bytes
+void pl_c64_plan(int64_t n, int64_t p, int64_t n_pad, int64_t p_pad, int64_t p_total, int masked, int64_t p_valid, int k, int n_oversamples,
+                 int n_iter, int krylov_allowed, int64_t* out) {
+  const C64Plan c = c64_plan(n, p, n_pad, p_pad, p_total, masked != 0, p_valid, k, n_oversamples, n_iter, krylov_allowed != 0);
+  const int64_t o[] = {c.status, c.r, c.l, c.adaptive, c.n_iter, c.auto_count, c.h, c.LP, c.ko, c.Lo, c.transposed, c.small, c.small_pad,
+                       c.tall_pad, c.big, c.krylov, c.nbmax, c.ldk, (int64_t)c.arena_bytes};
+  std::copy(o, o + 19, out);
+}
+int64_t pl_c64_mul_scratch_bytes(int64_t n, int64_t p, int64_t n_pad, int64_t p_pad, int L) {
+  return (int64_t)c64_mul_scratch_bytes(n, p, n_pad, p_pad, L);
 }
 
 // ---- eofx_sketch.hpp
@@ -191,7 +205,7 @@ double lcg() {      // uniform in [-1, 1)
 
 int main() {
   // plans
-  int widths[64], c[10];
+  int widths[64], c[13];
   pl_constants(c);
   for (int L = 32; L <= 544; L += 32) {
     expect(pl_tiles(L, 0, widths) > 0 && pl_tiles(L, 1, widths) > 0, "tiles cover the panel");
@@ -233,6 +247,27 @@ int main() {
     int nyG[2];
     expect(pl_lagcov_plan(700, 130, w.data(), 66, wp.data(), nyG) == 66 + 30, "lagcov_plan");
     expect(pl_lowpass_plan(700, 130, w.data(), 40, wp.data(), nyG) == 81 + 30, "lowpass_plan");
+  }
+  // the complex driver's plan, the hand cases of tests/test_plans_cpu.py: {n, p, p_total, masked, p_valid, k, n_oversamples, n_iter,
+  // krylov_allowed} -> {status, l, LP, n_iter, transposed, krylov, nbmax}
+  {
+    const int64_t cases[][16] = {
+        {300, 900, 0, 0, 0, 22, 10, -1, 1, /**/ C64_PLAN_OK, 32, 64, 7, 1, 1, 8},     {300, 900, 0, 0, 0, 23, 10, -1, 1, /**/ C64_PLAN_OK, 33, 128, 7, 1, 1, 8},
+        {300, 900, 0, 0, 0, 29, 10, -1, 1, /**/ C64_PLAN_OK, 39, 128, 7, 1, 1, 8},    {300, 900, 0, 0, 0, 30, 10, -1, 1, /**/ C64_PLAN_OK, 40, 128, 4, 1, 1, 5},
+        {300, 900, 0, 0, 0, 6, 10, 0, 1, /**/ C64_PLAN_OK, 16, 64, 0, 1, 0, 0},       {300, 900, 0, 0, 0, 6, 10, -2, 1, /**/ C64_PLAN_OK, 16, 64, 20, 1, 1, 21},
+        {300, 900, 0, 0, 0, 6, 10, -3, 1, /**/ C64_PLAN_N_ITER, 16, 0, 0, 0, 0, 0},   {300, 900, 0, 0, 0, 38, 10, 7, 1, /**/ C64_PLAN_OK, 48, 128, 7, 1, 1, 8},
+        {300, 900, 0, 0, 0, 39, 10, 7, 1, /**/ C64_PLAN_OK, 49, 128, 7, 1, 1, 7},     {300, 900, 0, 0, 0, 54, 10, 7, 1, /**/ C64_PLAN_OK, 64, 128, 7, 1, 1, 6},
+        {300, 900, 0, 0, 0, 55, 10, 7, 1, /**/ C64_PLAN_WIDTH, 65, 0, 0, 0, 0, 0},    {20, 900, 0, 0, 0, 21, 10, -1, 1, /**/ C64_PLAN_RANK, 0, 0, 0, 0, 0, 0},
+        {300, 900, 0, 1, 301, 6, 10, -1, 1, /**/ C64_PLAN_OK, 16, 64, 7, 1, 1, 8},    {300, 900, 0, 1, 300, 6, 10, -1, 1, /**/ C64_PLAN_MASKED, 16, 0, 0, 0, 0, 0},
+        {300, 100, 301, 0, 0, 6, 10, -1, 1, /**/ C64_PLAN_OK, 16, 64, 7, 1, 1, 8},    {300, 100, 300, 0, 0, 6, 10, -1, 1, /**/ C64_PLAN_SHARD_SIDE, 0, 0, 0, 0, 0, 0},
+        {900, 300, 0, 0, 0, 6, 10, -1, 1, /**/ C64_PLAN_OK, 16, 64, 7, 0, 1, 8},      {300, 900, 0, 0, 0, 6, 10, -1, 0, /**/ C64_PLAN_OK, 16, 64, 7, 1, 0, 0}};
+    for (auto& q : cases) {
+      int64_t o[19];
+      pl_c64_plan(q[0], q[1], round_up(q[0], ATB_BM), round_up(q[1], ATB_BM), q[2], (int)q[3], q[4], (int)q[5], (int)q[6], (int)q[7], (int)q[8], o);
+      expect(o[0] == q[9] && o[2] == q[10] && o[7] == q[11] && o[4] == q[12] && o[10] == q[13] && o[15] == q[14] && o[16] == q[15], "c64_plan hand case");
+      expect(o[0] != C64_PLAN_OK || (o[16] * o[2] <= KRYLOV_MAX_ORDER && o[17] == o[16] * o[7] && o[18] > 0), "c64_plan invariants");
+    }
+    expect(pl_c64_mul_scratch_bytes(300, 900, 512, 1024, 64) > (8 << 20), "c64_mul_scratch_bytes");
   }
   // the sketch generator at eight threads (twice: the second call reuses the pool and the buffers) and at one
   {

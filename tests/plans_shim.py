@@ -26,6 +26,7 @@ SIGNATURES = {
     "pl_colstats_scratch": (I64, [I64, I64]), "pl_summary_blocks": (I, [I64]),
     "pl_apply_plan": (None, [I64, I64, I64, I64, I, I, I, I, P]), "pl_viewcov_plan": (I, [I64, I, P, I, I, P, P, I, P]),
     "pl_lagcov_plan": (I, [I64, I, P, I, P, P]), "pl_lowpass_plan": (I, [I64, I, P, I, P, P]),
+    "pl_c64_plan": (None, [I64, I64, I64, I64, I64, I, I64, I, I, I, I, P]), "pl_c64_mul_scratch_bytes": (I64, [I64, I64, I64, I64, I]),
     "sk_gaussian_f32": (None, [U32, I64, I64, P]), "sk_candidates": (I64, [I64]),
     "hh_kappa": (D, [I64, I64]), "hh_fft": (None, [P, I64]), "hh_length": (I64, [I64, P]), "hh_position_frequency": (I64, [I, I64]),
     "hh_fused_table": (None, [I64, I64, I, P]), "hh_circular_kernel": (None, [I64, I64, I64, P]),
@@ -33,7 +34,8 @@ SIGNATURES = {
     "gwp_build": (P, [P, I64, I64, I64, I64, I, I, I, D]), "gwp_free": (None, [P]), "gwp_sizes": (None, [P, P]),
     "gwp_copy": (None, [P, P, P, P, P, P, P, P]),
 }
-CONSTANTS = ("ATB_BM", "ATB_KG", "AXB_BM", "AXB_KG", "LAG_GROUP_COLS", "VIEWCOV_T", "VIEWCOV_WGS", "LAGCOV_PADW", "LOWPASS_PADW", "GW_T")
+CONSTANTS = ("ATB_BM", "ATB_KG", "AXB_BM", "AXB_KG", "LAG_GROUP_COLS", "VIEWCOV_T", "VIEWCOV_WGS", "LAGCOV_PADW", "LOWPASS_PADW", "GW_T",
+             "KRYLOV_MAX_ORDER", "C64_IT_MIN", "C64_IT_CAP")
 
 
 @functools.lru_cache(maxsize=1)

@@ -488,12 +488,14 @@ def test_complex_rsvd_flat_bulk_vs_reference_solver_and_exact(ctx, n, p, k, monk
     assert e_old.max() > 10 * e7.max(), (e_old.max(), e7.max())
 
 
-@pytest.mark.parametrize("case", ["wide_sketch", "full_width", "rank_deficient", "n_iter_1", "n_iter_2", "converge", "feature_side"])
+@pytest.mark.parametrize("case", ["wide_sketch", "full_width", "rank_deficient", "n_iter_1", "n_iter_2", "converge", "feature_side",
+                                  "thick_restart"])
 def test_complex_rsvd_krylov_edge_cases(ctx, case):
     """The block Lanczos recurrence where it ends early or runs in another shape: a sketch wider than 32 complex columns
     (128-column real panels), a full-width sketch (identity start: the first product exhausts the space), an exactly
-    rank-deficient matrix (blocks die), one and two products, restarted cycles ("converge"), and the sketch on the feature
-    side (n > p) -- values against the exact SVD for every mode clear of the bulk."""
+    rank-deficient matrix (blocks die), one and two products, restarted cycles ("converge"), the sketch on the feature
+    side (n > p), and a sketch of 52 columns at seven products, whose eighth block would take the Rayleigh-Ritz problem past
+    order 384 (one thick restart) -- values against the exact SVD for every mode clear of the bulk."""
     from xeofs_amd import engine
 
     rng = np.random.default_rng(11)
@@ -510,6 +512,8 @@ def test_complex_rsvd_krylov_edge_cases(ctx, case):
         n_iter, noise = "converge", 0.3
     elif case == "feature_side":
         n, p = 900, 260
+    elif case == "thick_restart":
+        n, p, k, n_iter = 400, 600, 42, 7   # l = 52: 7 blocks fit below order 384, the sample side holds them (7 * 52 <= 400)
     r = 5 if case == "rank_deficient" else 9
     L = (rng.standard_normal((n, r)) + 1j * rng.standard_normal((n, r))) * (6.0 * 0.6 ** np.arange(r))
     Z = L @ (rng.standard_normal((r, p)) + 1j * rng.standard_normal((r, p))) / np.sqrt(p)

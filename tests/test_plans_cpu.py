@@ -290,3 +290,98 @@ def test_low_pass_weights(lib, h):
     k = lib.pl_lowpass_plan(700, 130, w.ctypes.data, h, out.ctypes.data, nyG.ctypes.data)
     assert c["LOWPASS_PADW"] == 15 and k == 2 * h + 31 and np.array_equal(out[:k], np.pad(np.concatenate([w[:0:-1], w]), 15))
     assert np.all(out[k:] == 7.0) and nyG.tolist() == [6, 11]       # 3 (3 + 1) / 2 tile pairs; min(11 row tiles, 512 // 6)
+
+
+# --------------------------------------------------------------------------- #
+# 3. the plan of the complex driver (c64_plan)                                  #
+# --------------------------------------------------------------------------- #
+C64_FIELDS = ("status", "r", "l", "adaptive", "n_iter", "auto_count", "h", "LP", "ko", "Lo", "transposed", "small", "small_pad", "tall_pad",
+              "big", "krylov", "nbmax", "ldk", "arena_bytes")
+C64_OK, C64_SHARD_SIDE, C64_RANK, C64_WIDTH, C64_MASKED, C64_N_ITER = range(6)      # the order the driver reports the checks in
+
+
+def c_c64(lib, n, p, k, n_oversamples=10, n_iter=-1, p_total=0, masked=False, p_valid=0, krylov_allowed=True):
+    out = np.zeros(len(C64_FIELDS), np.int64)
+    lib.pl_c64_plan(n, p, routes._up(n, 512), routes._up(p, 512), p_total, int(masked), p_valid, k, n_oversamples, n_iter,
+                    int(krylov_allowed), out.ctypes.data)
+    return dict(zip(C64_FIELDS, out.tolist()))
+
+
+def _has(plan, **want):
+    return {key: plan[key] for key in want} == want
+
+
+def test_c64_plan_hand_cases(lib):
+    """Values written out from the rules: r = min(n, features), l = min(k + oversamples, r), panels of 32 complex columns up to
+    l = 32 and of 64 above, output panels of round_up(k, 16), scikit-learn's count 7 below k = 0.1 r and 4 from there,
+    nb_fit = 384 // l blocks before a thick restart, nbmax = min(products + 1, nb_fit), block Krylov from one product and three
+    blocks on.  A 300 x 900 field pads to 512 x 1024."""
+    c = plans_shim.constants(lib)
+    assert (c["KRYLOV_MAX_ORDER"], c["C64_IT_MIN"], c["C64_IT_CAP"]) == (384, 2, 20)
+    # the panel width switches between l = 32 and l = 33 (k < 30: 7 products, 8 blocks of the 12 / 11 that fit)
+    assert _has(c_c64(lib, 300, 900, 22), status=C64_OK, r=300, l=32, h=32, LP=64, ko=32, Lo=64, auto_count=7, n_iter=7, adaptive=0,
+                transposed=1, small=300, small_pad=512, tall_pad=1024, big=1024, krylov=1, nbmax=8, ldk=512)
+    assert _has(c_c64(lib, 300, 900, 23), status=C64_OK, l=33, h=64, LP=128, ko=32, Lo=64, n_iter=7, krylov=1, nbmax=8, ldk=1024)
+    # scikit-learn's count on both sides of k < 0.1 r
+    assert _has(c_c64(lib, 300, 900, 29), auto_count=7, n_iter=7, l=39, nbmax=8)
+    assert _has(c_c64(lib, 300, 900, 30), auto_count=4, n_iter=4, l=40, nbmax=5, ldk=5 * 128)
+    assert _has(c_c64(lib, 300, 900, 30, n_iter=9), auto_count=4, n_iter=9, nbmax=9)           # 384 // 40 = 9 < 10
+    # the iteration codes
+    assert _has(c_c64(lib, 300, 900, 6, n_iter=0), status=C64_OK, n_iter=0, krylov=0, nbmax=0, ldk=0, l=16, ko=16, Lo=32)
+    assert _has(c_c64(lib, 300, 900, 6, n_iter=-2), status=C64_OK, adaptive=1, n_iter=20, auto_count=7, krylov=1, nbmax=21, ldk=21 * 64)
+    assert c_c64(lib, 300, 900, 6, n_iter=-3)["status"] == C64_N_ITER
+    # seven products: 8 blocks of 48 columns fit (no restart), of 49 columns only 7 (one restart)
+    assert _has(c_c64(lib, 300, 900, 38, n_iter=7), status=C64_OK, l=48, krylov=1, nbmax=8)
+    assert _has(c_c64(lib, 300, 900, 39, n_iter=7), status=C64_OK, l=49, krylov=1, nbmax=7)
+    # the widest sketch
+    assert _has(c_c64(lib, 300, 900, 54, n_iter=7), status=C64_OK, l=64, h=64, LP=128, ko=64, Lo=128, nbmax=6)
+    assert _has(c_c64(lib, 300, 900, 55, n_iter=7), status=C64_WIDTH, l=65)
+    assert _has(c_c64(lib, 300, 900, 60, n_oversamples=0), status=C64_OK, l=60)
+    # more modes than rank; the sketch is cut to the rank
+    assert _has(c_c64(lib, 20, 900, 21), status=C64_RANK, r=20)
+    assert _has(c_c64(lib, 20, 900, 20), status=C64_OK, r=20, l=20, auto_count=4)
+    # masked in place: the valid features count, and there must be more of them than samples
+    assert _has(c_c64(lib, 300, 900, 6, masked=True, p_valid=301), status=C64_OK, r=300, transposed=1)
+    assert c_c64(lib, 300, 900, 6, masked=True, p_valid=300)["status"] == C64_MASKED
+    assert _has(c_c64(lib, 300, 900, 6, masked=True, p_valid=5), status=C64_RANK, r=5)
+    # sharded: the features of all ranks count, the sketch sits on the sample side whatever the slice
+    assert _has(c_c64(lib, 300, 100, 6, p_total=301), status=C64_OK, r=300, transposed=1, small=300, small_pad=512, tall_pad=512, big=512)
+    assert c_c64(lib, 300, 100, 6, p_total=300)["status"] == C64_SHARD_SIDE
+    assert _has(c_c64(lib, 300, 100, 6), status=C64_OK, r=100, transposed=0, small=100, small_pad=512, tall_pad=512)
+    assert _has(c_c64(lib, 900, 300, 6), status=C64_OK, transposed=0, small=300, small_pad=512, tall_pad=1024, big=1024)
+    # the subspace iteration on request
+    assert _has(c_c64(lib, 300, 900, 6, krylov_allowed=False), status=C64_OK, n_iter=7, krylov=0, nbmax=0, ldk=0)
+
+
+def test_c64_plan_on_a_sweep(lib):
+    """Every accepted plan keeps the Rayleigh-Ritz problem within order 384, holds at least three blocks where the block Krylov
+    recurrence runs (all of them, two, when one product is asked for), has panels of 64 or 128 real columns, and reserves what the formula restated here gives; the scratch of one
+    pass of eofx_cmat_mul_f32 is its part of that formula."""
+    rng = np.random.default_rng(384)
+    up, scratch = routes._up, lib.pl_atb_scratch_bytes
+    accepted = 0
+    for _ in range(3000):
+        n, p = (int(x) for x in rng.integers(1, 6000, 2))
+        k, over, n_iter = int(rng.integers(1, 70)), int(rng.integers(0, 12)), int(rng.integers(-2, 22))
+        pl = c_c64(lib, n, p, k, over, n_iter, krylov_allowed=bool(rng.integers(0, 4)))
+        r = min(n, p)
+        want = C64_RANK if k > r else C64_WIDTH if min(k + over, r) > 64 else C64_OK
+        assert pl["status"] == want, (n, p, k, over, n_iter)
+        if want != C64_OK:
+            continue
+        accepted += 1
+        LP, Lo, nbmax, sp, tp, big = (pl[key] for key in ("LP", "Lo", "nbmax", "small_pad", "tall_pad", "big"))
+        assert LP in (64, 128) and LP == 2 * pl["h"] and pl["l"] <= pl["h"] and nbmax * pl["l"] <= 384 and pl["ldk"] == nbmax * LP
+        if pl["krylov"]:        # (a run of one product makes two blocks, Z_0 and Z_1, and is never short of room)
+            assert 384 // pl["l"] >= 3 and (nbmax >= 3 or nbmax == pl["n_iter"] + 1 == 2), (n, p, k, over, n_iter)
+        else:
+            assert nbmax == 0
+        n_pad, p_pad = up(n, 512), up(p, 512)
+        passes = 2 * scratch(p_pad, up(n, 32), LP) + 2 * scratch(n_pad, up(p, 32), LP)
+        need = (2 * sp + 2 * tp + 2 * big) * LP * 4 + (sp + tp) * Lo * 4 + passes
+        need += (4 * lib.pl_gram_parts(big, LP) + 8) * LP * LP * 8 + big * (Lo + LP) * 4 + (8 << 20)
+        if pl["krylov"]:
+            need += nbmax * (2 * sp + tp) * LP * 4 + sp * LP * 4 + (3 + nbmax) * nbmax * LP * LP * 8 + (48 << 20)
+        assert pl["arena_bytes"] == need, (n, p, k, over, n_iter)
+        assert lib.pl_c64_mul_scratch_bytes(n, p, n_pad, p_pad, LP) == 4 * big * LP * 4 + (8 << 20) + passes
+    assert accepted >= 1500

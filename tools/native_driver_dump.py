@@ -5,8 +5,10 @@ compare two builds of libeofx.so bit for bit where the host algebra between the 
 existing test instead (TOLERANCE), everything else must be equal between A1 and B).  The sibling of cross_surface_dump.py one level down: engine.rsvd tall / wide / with a sketch
 beyond 64 columns on either route of the Cholesky inverse / with more modes than rank / on a peaked spectrum over a tall panel
 above 16 MiB, engine.crosscov_rsvd with more modes than rank, engine.rsvd_c64 at the edge cases of
-tests/test_gpu_complex.py with and without the block-Krylov recurrence, engine.rsvd_hilbert_c64 under both rules, and the
-two host eigen-solvers."""
+tests/test_gpu_complex.py with and without the block-Krylov recurrence and on the branches those do not reach (`c64_branches`),
+engine.rsvd_hilbert_c64 under both rules, and the two host eigen-solvers.  With EOFX_C64_TRACE set, stderr holds the complex
+driver's trace, one `# key` line after the lines of each case: two builds that take the same branches print the same text
+once the milliseconds of the host-solve lines are removed."""
 import os
 import sys
 
@@ -54,6 +56,83 @@ def low_rank(rng, n, p, rank, decay, noise, cplx=False):
     return X
 
 
+def c64_branches(record):
+    """The branches of the complex driver that the edge cases of the test do not reach: a thick restart (l = 52: 7 blocks fit
+    below order 384; scikit-learn's count is 4 products at this k, so 7 products and "converge" are the cases that restart),
+    the lean layout, a masked in-place real part, no sign rule, outputs left on the device, the two sharded entries over a
+    one-rank RCCL communicator, and one pass of eofx_cmat_mul_f32 in both directions, lean and not."""
+    import torch
+
+    from xeofs_amd import engine
+
+    ctx = engine.default_context()
+
+    def waves(n, p, seed, noise=0.3):
+        rng = np.random.default_rng(seed)
+        tt, xx = np.arange(n)[:, None], np.linspace(0, 2 * np.pi, p)[None, :]
+        X = sum(a * np.cos(w * tt - m * xx + ph) for a, w, m, ph in ((3.0, 0.21, 2, 0.0), (1.7, 0.37, -3, 0.4), (0.9, 0.11, 1, 1.0)))
+        return (X + noise * rng.standard_normal((n, p)) + 3.0).astype(np.float32)
+
+    # (120 samples hold two blocks of 52 columns and a rest: that space is exhausted at the third product, before it is full;
+    # 400 samples hold the 7 blocks)
+    for n, n_iter, noise in ((120, "auto", 0.02), (120, "converge", 0.3), (400, 7, 0.02), (400, "converge", 0.3)):
+        Z = low_rank(np.random.default_rng(11), n, 600, 9, 0.6, noise, cplx=True).astype(np.complex64)
+        A = engine.from_dense(ctx, np.ascontiguousarray(Z.real))
+        B = engine.from_dense(ctx, np.ascontiguousarray(Z.imag))
+        record(f"rsvd_c64.thick_restart.n{n}.{n_iter}", engine.rsvd_c64(ctx, A, B, 42, random_state=2, n_iter=n_iter), iters=True)
+        A.free()
+        B.free()
+    # lean: Re raw in place, Im in the sample-contiguous layout only; then the same field with every layout written
+    X = waves(300, 1536, 7)
+    for lean in (True, False):
+        A, _ = engine.preprocess(ctx, X, in_place=lean)
+        B, _ = engine.hilbert(ctx, A, "exp", 0.2)
+        tag = "lean" if lean else "written"
+        record(f"rsvd_c64.{tag}", engine.rsvd_c64(ctx, A, B, 6, random_state=3), iters=True)
+        if not lean:
+            record("rsvd_c64.no_flip", engine.rsvd_c64(ctx, A, B, 6, random_state=3, flip=False))
+            record("rsvd_c64.device_out", [t if isinstance(t, np.ndarray) else t.cpu().numpy()
+                                           for t in engine.rsvd_c64(ctx, A, B, 6, random_state=3, device_out=True)])
+        gen = torch.Generator().manual_seed(5)
+        for conj_left in (True, False):
+            P = torch.randn((A.n_pad if conj_left else A.p_pad, 64), generator=gen).to(f"cuda:{ctx.device}")
+            for final in (False, True):
+                record(f"cmat_mul.{tag}.conj{int(conj_left)}.final{int(final)}",
+                       [engine.cmat_mul(ctx, A, B, P, conj_left, final=final).cpu().numpy()])
+        A.free()
+        B.free()
+    # masked in place: 30 % all-NaN grid points stay as zero columns of the real part
+    X = waves(300, 1600, 9)
+    X[:, np.random.default_rng(1600).choice(1600, size=480, replace=False)] = np.nan
+    A, _ = engine.preprocess(ctx, X, in_place=True, allow_masked=True)
+    assert A.masked
+    B, _ = engine.hilbert(ctx, A, "exp", 0.2)
+    record("rsvd_c64.masked", engine.rsvd_c64(ctx, A, B, 6, random_state=3), iters=True)
+    A.free()
+    B.free()
+    # the sharded entries, world size 1 (ncclAllReduce really runs)
+    n, p, k = 400, 2600, 6
+    X = waves(n, p, 4)
+    for route in ("operator", "two_part"):
+        A, _ = engine.preprocess(ctx, X, in_place=True, for_hilbert=(route == "operator"))
+        if route == "operator":
+            engine.hilbert_sumsq(ctx, A, "exp", 0.2)
+        else:
+            B, _ = engine.hilbert(ctx, A, "exp", 0.2)
+        engine.comm_init_rccl(ctx, engine.comm_unique_id(), 1, 0)
+        try:
+            if route == "operator":
+                got = engine.rsvd_hilbert_sharded_c64(ctx, A, k, p, "exp", 0.2, random_state=3)
+            else:
+                got = engine.rsvd_sharded_c64(ctx, A, B, k, p, random_state=3)
+        finally:
+            engine.comm_clear(ctx)
+        record(f"rsvd_sharded_c64.{route}", got, iters=True)
+        A.free()
+        if route != "operator":
+            B.free()
+
+
 def main(out_path):
     from xeofs_amd import _lib, engine
 
@@ -61,6 +140,8 @@ def main(out_path):
     out = {}
 
     def record(key, obj, iters=False):
+        if os.environ.get("EOFX_C64_TRACE"):        # closes the driver's trace lines of this case on stderr
+            print(f"# {key}", file=sys.stderr, flush=True)
         if isinstance(obj, dict):
             obj = [obj[name] for name in sorted(obj) if isinstance(obj[name], (np.ndarray, float, int, np.generic))]
         for i, o in enumerate(obj):
@@ -125,6 +206,7 @@ def main(out_path):
                    with_env("EOFX_C64_KRYLOV", krylov, lambda: engine.rsvd_c64(ctx, A, B, k, random_state=2, n_iter=n_iter)), iters=True)
         A.free()
         B.free()
+    c64_branches(record)
     # --- engine.rsvd_hilbert_c64
     X = low_rank(rng, 300, 900, 9, 0.6, 0.3)
     mat = engine.from_dense(ctx, (X - X.mean(axis=0)).astype(np.float32))

@@ -2847,6 +2847,16 @@ static int comm_vote(eofx_ctx* ctx, int local, int* global) {
   return EOFX_OK;
 }
 
+// The ranks agree before they go on.  This rank votes 2 when rc_local is an error, else local_state (0, or 1 for the caller's
+// second state); *verdict is the worst vote.  Verdict 2 ends the call on every rank: with this rank's own error where it has
+// one, else with "<what> failed on another rank".
+static int comm_agree(eofx_ctx* ctx, int rc_local, int local_state, const char* what, int* verdict) {
+  const std::string err_local = rc_local < 0 ? ctx->err : std::string();
+  CHK(comm_vote(ctx, rc_local < 0 ? 2 : local_state, verdict));
+  if (*verdict != 2) return EOFX_OK;
+  return rc_local < 0 ? (ctx->err = err_local, rc_local) : set_err(ctx, EOFX_ERR_HIP, "%s failed on another rank", what);
+}
+
 // sum of one integer per rank (float64 carries integers below 2^53 exactly); one all-reduce + a host read
 static int comm_sum_i64(eofx_ctx* ctx, int64_t local, int64_t* global) {
   *global = local;
@@ -2916,13 +2926,8 @@ extern "C" int eofx_ctx_comm_probe(eofx_ctx* ctx, int ncases, const int64_t* cou
     if (counts[i] <= 0 || dtypes[i] < 0 || dtypes[i] > 2) return set_err(ctx, EOFX_ERR_ARG, "bad argument");    // (the same on every rank)
     most = std::max<int64_t>(most, counts[i] * 8);
   }
-  {   // a rank-local failure before the first collective (growing the arena) becomes a vote: every rank leaves together
-    const int rc_local = arena_reserve(ctx, (size_t)most + 4096);
-    const std::string err_local = rc_local != EOFX_OK ? ctx->err : std::string();
-    int verdict = 0;
-    CHK(comm_vote(ctx, rc_local != EOFX_OK ? 2 : 0, &verdict));
-    if (verdict != 0) return rc_local != EOFX_OK ? (ctx->err = err_local, rc_local) : set_err(ctx, EOFX_ERR_HIP, "the communicator probe failed on another rank");
-  }
+  int verdict = 0;   // a rank-local failure before the first collective (growing the arena) becomes a vote: every rank leaves together
+  CHK(comm_agree(ctx, arena_reserve(ctx, (size_t)most + 4096), 0, "the communicator probe", &verdict));
   ArenaScope scope(ctx);
   ARENA(char, buf, (size_t)most);
   HIPCHK(hipMemsetAsync(buf, 0, (size_t)most, ctx->stream));
@@ -2989,18 +2994,14 @@ extern "C" int eofx_fit_sharded_f32(eofx_ctx* ctx, const float* X, int64_t n, in
     rc = eligible ? ff.prepare(ctx, st.dev, n, P, center, standardize, feat_weights, l) : EOFX_FIT_FALLBACK;
     if (!eligible) ctx->fit_info[2] = -1.0;
   }
-  const std::string err_local = rc < 0 ? ctx->err : std::string();
   int verdict = 0;
-  CHK(comm_vote(ctx, rc < 0 ? 2 : rc > 0 ? 1 : 0, &verdict));
-  if (verdict == 2) return rc < 0 ? (ctx->err = err_local, rc) : set_err(ctx, EOFX_ERR_HIP, "the sharded fit failed on another rank");
+  CHK(comm_agree(ctx, rc, rc > 0, "the sharded fit", &verdict));
   if (verdict == 1) return EOFX_FIT_FALLBACK;
   // the first product + the statistics of the slice; then the ranks agree on whether every slice passed
   FirstFwd first = [&](const float* Zs, float* Yt, int LL) -> int {
     const int r1 = ff.run(Zs, Yt, LL);
-    const std::string e1 = r1 < 0 ? ctx->err : std::string();
     int v = 0;
-    CHK(comm_vote(ctx, r1 < 0 ? 2 : r1 > 0 ? 1 : 0, &v));
-    if (v == 2) return r1 < 0 ? (ctx->err = e1, r1) : set_err(ctx, EOFX_ERR_HIP, "the sharded fit failed on another rank");
+    CHK(comm_agree(ctx, r1, r1 > 0, "the sharded fit", &v));
     if (v == 1) return EOFX_FIT_FALLBACK;
     // all-NaN grid points (a land / sea mask) stay as zero columns of every slice: the decomposition needs more valid features
     // over ALL slices than samples (the sketch sits on the sample side); one int32 sum, the same verdict on every rank
@@ -3510,12 +3511,8 @@ static int crosscov_impl(eofx_ctx* ctx, const eofx_mat* x, const eofx_mat* y, in
     // sized for either route up front (+ room for the null-mode repair of a sharded factor).
     const size_t Lo_ = (size_t)round_up(k, 32), pp_ = (size_t)std::max(x->p_pad, y->p_pad);
     need += pp_ * Lo_ * 4 + (size_t)(gram_parts((int64_t)pp_, (int)Lo_) + 4) * Lo_ * Lo_ * 8 + (64 << 10) + std::max(need_gram, need_plain);
-    const int rc_local = arena_reserve(ctx, need);
-    const std::string err_local = rc_local != EOFX_OK ? ctx->err : std::string();
     int worst = 0;
-    CHK(comm_vote(ctx, rc_local != EOFX_OK ? 2 : gram_route ? 0 : 1, &worst));
-    if (worst == 2)
-      return rc_local != EOFX_OK ? (ctx->err = err_local, rc_local) : set_err(ctx, EOFX_ERR_HIP, "the sharded cross-covariance fit failed on another rank");
+    CHK(comm_agree(ctx, arena_reserve(ctx, need), gram_route ? 0 : 1, "the sharded cross-covariance fit", &worst));
     gram_route = worst == 0;
   } else {
     need += gram_route ? need_gram : need_plain;
@@ -4243,10 +4240,7 @@ extern "C" int eofx_cmat_mul_f32(eofx_ctx* ctx, const eofx_mat* A, const eofx_ma
     CHK(ensure_X(ctx, B));
   }
   const int64_t big = std::max(A->n_pad, A->p_pad);
-  size_t need = (size_t)2 * big * L * 4 + (8 << 20);
-  need += (size_t)2 * big * L * 4;   // the two partial results of a two-matrix launch that needs no split
-  need += 2 * atb_scratch_bytes(A->p_pad, round_up(A->n, ATB_KG), L) + 2 * atb_scratch_bytes(A->n_pad, round_up(A->p, ATB_KG), L);
-  CHK(arena_reserve(ctx, need));
+  CHK(arena_reserve(ctx, c64_mul_scratch_bytes(A->n, A->p, A->n_pad, A->p_pad, L)));
   ArenaScope scope(ctx);
   ARENA(float, rot, (size_t)big * L);
   ARENA(float, tmp, (size_t)big * L);
@@ -4275,10 +4269,9 @@ extern "C" int eofx_cmat_mul_f32(eofx_ctx* ctx, const eofx_mat* A, const eofx_ma
 //   n_iter >= 0: that many products;  -1: scikit-learn's count (7 if k < 0.1 min(n, p) else 4);
 //   -2 ("converge"): restarted cycles of that count, each starting from the Ritz block of the previous one, until the leading k
 //        values move by <= 1e-6 (relative, squared values) or 20 products have been made (lobpcg's own limit under svds).
-// Sketches whose Krylov space would exceed order 384 (k + n_oversamples > 48 at q = 7) are THICK-RESTARTED (`compress`: the Ritz
-// block + the newest block) so that the host's Rayleigh-Ritz problem stays below that order; sketches so wide that fewer than 3
-// blocks fit (l > 128: not reachable, l <= 64) would keep the subspace iteration of rounds 1-4 (EOFX_C64_KRYLOV=0 forces it, for
-// comparisons).  The panel-level driver (xeofs_amd/complex_svd.py) solves its Rayleigh-Ritz problem with numpy and keeps up to
+// Sketches whose Krylov space would exceed order 384 (k + n_oversamples > 48 at q = 7) are THICK-RESTARTED (`compress`); sketches
+// so wide that fewer than 3 blocks fit (l > 128: not reachable, l <= 64) would keep the subspace iteration of rounds 1-4
+// (EOFX_C64_KRYLOV=0 forces it, for comparisons).  The panel-level driver (xeofs_amd/complex_svd.py) solves its Rayleigh-Ritz problem with numpy and keeps up to
 // order 512 WITHOUT a restart: for 48 < l <= 64 at q = 7 the two drivers run different (both convergent) recurrences -- by design.
 // B != nullptr: Z = A + i B (both resident).  B == nullptr: Z = (I + i Hc) A with the resident Hilbert operator Hop.
 // p_total > 0 (eofx_rsvd_sharded_c64 / eofx_rsvd_hilbert_sharded_c64): A (and B) are this rank's slice of the feature axis of a
@@ -4286,106 +4279,105 @@ extern "C" int eofx_cmat_mul_f32(eofx_ctx* ctx, const eofx_mat* A, const eofx_ma
 // sample side, which is replicated: the only collectives are one all-reduce(sum) of the n x LP sample-side panel per product
 // Z Y, one of the LP x LP float64 Gram matrix per feature-side panel that is factorised, and two small ones for the sign rule.
 // The Hilbert operator acts on the replicated sample-side panel, so the operator route shards without further exchange.
-static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, const eofx_mat* Hop, int k, int n_oversamples,
-                         int n_iter, const float* omega, int flip_signs, float* U, float* s, float* V, int64_t p_total = 0) {
-  if (!ctx || !A || (!B && !Hop) || !omega || !s || k <= 0 || n_oversamples < 0)
-    return set_err(ctx, EOFX_ERR_ARG, "bad argument");
-  if (B && (A->n != B->n || A->p != B->p)) return set_err(ctx, EOFX_ERR_SHAPE, "real and imaginary parts must have the same shape");
-  ENTER(ctx);
-  const bool shd = p_total > 0;
-  if (shd && !ctx->comm) return set_err(ctx, EOFX_ERR_ARG, "no communicator attached (eofx_ctx_comm_init_rccl / eofx_ctx_comm_set_callback)");
-  if (shd && !(A->n < p_total)) return set_err(ctx, EOFX_ERR_ARG, "the sharded complex decomposition needs the sketch on the sample side (n < p_total)");
-  const int64_t n = A->n, p = A->p, r = std::min(n, shd ? p_total : (A->masked ? A->p_valid : p));
-  if (k > r) return set_err(ctx, EOFX_ERR_RANK, "n_modes must be less than or equal to the rank of the dataset (rank = %lld).", (long long)r);
-  const int l = (int)std::min<int64_t>(k + n_oversamples, r);
-  if (l > 64) return set_err(ctx, EOFX_ERR_ARG, "complex sketch width %d > 64 is not supported (n_modes + n_oversamples <= 64)", l);
-  if (!shd && A->masked && !(n < A->p_valid)) return set_err(ctx, EOFX_ERR_ARG, "masked in-place matrix with fewer valid features than samples");
-  const bool adaptive = n_iter == -2;
-  const int auto_count = k < 0.1 * (double)r ? 7 : 4;
-  if (n_iter == -1) n_iter = auto_count;
-  const int it_min = 2, it_cap = 20;
-  if (adaptive) n_iter = it_cap;
-  if (n_iter < 0) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
-  const int h = l <= 32 ? 32 : 64, LP = 2 * h;
-  const int ko = (int)round_up(k, 16), Lo = 2 * ko;       // output panels [Re(ko) | Im(ko)]
-  const bool lean = B && cplx_lean(A, B, LP, ctx->prec_power, ctx->prec_final);
-  // (sharded: a rank-local failure of the steps before the first collective -- building a layout, growing the arena -- must not
-  // leave the other ranks in an all-reduce: it becomes this rank's vote below and every rank returns together)
-  int rc_local = EOFX_OK;
-  if (B && !lean) {
-    rc_local = ensure_X(ctx, A);   // (ensure_X builds the sample-contiguous layout first where that is missing too)
-    if (rc_local == EOFX_OK) rc_local = ensure_X(ctx, B);
-    if (!shd) CHK(rc_local);
-  }
-  const bool transposed = shd || n < p;     // A_op = Z^H: tall side = features
-  const int64_t small = transposed ? n : p;
-  const int64_t small_pad = transposed ? A->n_pad : A->p_pad, tall_pad = transposed ? A->p_pad : A->n_pad;
-  const int64_t big = std::max(A->n_pad, A->p_pad);
-  // block Krylov: products per cycle, blocks, order of the Rayleigh-Ritz problem
-  // blocks kept before a thick restart: the Rayleigh-Ritz problem stays below order 384 (the host solves it: ~10 ms at 240)
-  constexpr int KRYLOV_MAX_ORDER = 384;
-  const char* kenv = std::getenv("EOFX_C64_KRYLOV");
-  const int nb_fit = KRYLOV_MAX_ORDER / l;
-  const bool krylov = n_iter >= 1 && nb_fit >= 3 && !(kenv && atoi(kenv) == 0);
-  const int nbmax = krylov ? std::min(n_iter + 1, nb_fit) : 0;
-  const int64_t ldk = (int64_t)nbmax * LP;
-  size_t need = (size_t)(2 * small_pad + 2 * tall_pad + 2 * big) * LP * 4 + (size_t)(small_pad + tall_pad) * Lo * 4;
-  need += 2 * atb_scratch_bytes(A->p_pad, round_up(n, ATB_KG), LP) + 2 * atb_scratch_bytes(A->n_pad, round_up(p, ATB_KG), LP);
-  need += (size_t)(4 * gram_parts(big, LP) + 8) * LP * LP * 8 + (size_t)big * (Lo + LP) * 4 + (8 << 20);
-  if (krylov)
-    need += (size_t)nbmax * (2 * small_pad + tall_pad) * LP * 4 + (size_t)small_pad * LP * 4 + (size_t)(3 + nbmax) * nbmax * LP * LP * 8 +
-            ((size_t)48 << 20);
-  if (rc_local == EOFX_OK) rc_local = arena_reserve(ctx, need);
-  if (shd) {
-    const std::string err_local = rc_local != EOFX_OK ? ctx->err : std::string();
-    int verdict = 0;
-    CHK(comm_vote(ctx, rc_local != EOFX_OK ? 2 : 0, &verdict));
-    if (verdict != 0)
-      return rc_local != EOFX_OK ? (ctx->err = err_local, rc_local) : set_err(ctx, EOFX_ERR_HIP, "the sharded complex decomposition failed on another rank");
-  } else {
-    CHK(rc_local);
-  }
-  ArenaScope scope(ctx);
-  ARENA(float, Zs, (size_t)small_pad * LP);
-  ARENA(float, Ws, (size_t)small_pad * LP);
-  ARENA(float, Yt, (size_t)tall_pad * LP);
-  ARENA(float, Qt, (size_t)tall_pad * LP);
-  ARENA(float, rot, (size_t)big * LP);
-  ARENA(float, tmp, (size_t)big * LP);
-  ARENA(float, Tv, (size_t)tall_pad * Lo);
-  ARENA(float, Sv, (size_t)small_pad * Lo);
-  ARENA(double, G, (size_t)LP * LP);
-  ARENA(double, Ed, (size_t)LP * LP);
+//
+// The sizes and routes are C64Plan (eofx_plans.hpp); C64Driver holds the panels and the state of the recurrence, its methods are
+// the steps and the stages, and rsvd_c64_impl below runs the stages in order.
+struct C64Driver {
+  eofx_ctx* const ctx;
+  const eofx_mat* const A;
+  const C64Plan pl;
+  const int64_t p_total;      // > 0: sharded (shd)
+  const bool shd;
+  const int l, LP;            // pl.l, pl.LP
+  const int k, pp, pf;        // modes; precision of the power passes and of the projection pass
+  const bool trace;           // EOFX_C64_TRACE
+  CplxOps ops{};
+  // arena: small-side panels Zs (the current block), Ws, Vs; tall-side panels Yt, Qt; output panels Tv (tall), Sv (small)
+  float *Zs = nullptr, *Ws = nullptr, *Yt = nullptr, *Qt = nullptr, *Tv = nullptr, *Sv = nullptr;
+  double *G = nullptr, *Ed = nullptr;
+  // arena, block Krylov only: the blocks Z_0 .. Z_q side by side, their products W_i = A_op^H (A_op Z_i), the tall panels
+  // P_i = A_op Z_i (or their Q factors), and the float64 matrices of the small-side products
   float *Kw = nullptr, *Ww = nullptr, *Pt = nullptr, *Vs = nullptr;
   double *Cd = nullptr, *Ecd = nullptr, *Eall = nullptr, *Cf = nullptr;
-  if (krylov) {
-    Kw = arena_alloc<float>(ctx, (size_t)small_pad * ldk);               // the Krylov blocks Z_0 .. Z_q side by side
-    Ww = arena_alloc<float>(ctx, (size_t)small_pad * ldk);               // their products W_i = A_op^H (A_op Z_i)
-    Pt = arena_alloc<float>(ctx, (size_t)nbmax * tall_pad * LP);         // the tall panels P_i = A_op Z_i (or their Q factors)
-    Vs = arena_alloc<float>(ctx, (size_t)small_pad * LP);
-    Cd = arena_alloc<double>(ctx, (size_t)nbmax * LP * LP);
-    Ecd = arena_alloc<double>(ctx, (size_t)nbmax * LP * LP);
-    Eall = arena_alloc<double>(ctx, (size_t)nbmax * LP * LP);
-    Cf = arena_alloc<double>(ctx, (size_t)nbmax * nbmax * LP * LP);
-    if (!Kw || !Ww || !Pt || !Vs || !Cd || !Ecd || !Eall || !Cf) return set_err(ctx, EOFX_ERR_NOMEM, "arena exhausted (block Krylov panels)");
+  // host scratch: H is the Hermitian Gram matrix of the last gram_h, T the factor of the last chol_rinv
+  std::vector<double> hG, hE, hC, hCf, Hr, Hi, hEall, dref, ones;
+  std::vector<zdouble> H, T, blk;
+  std::vector<std::vector<zdouble>> ritz_raw;      // (an output of hostla::ritz_assemble that only ritz_residual reads)
+  // block Lanczos state: blocks Z_0 .. Z_{nb-1} side by side in Kw (orthonormal, dead columns zero); block b < nW has been
+  // multiplied: slot b of Pt holds A_op Z_b (or its Q factor, then Rf[b] is the triangular factor) and block b of Ww holds
+  // W_b with M Z_b = W_b Rf[b]
+  int nb = 0, nW = 0;
+  bool exhausted = false, orth_always = false, orth_rest = false;     // (orth_*: the tall panel is orthonormalised in every product / in the remaining ones)
+  std::vector<std::vector<zdouble>> Rf;            // (empty = identity: the tall panel was not orthonormalised)
+  std::vector<zdouble> Hqq;                        // P^H P of the newest block's tall panel
+  std::vector<double> Xr, Xi, wv;                  // the last Rayleigh-Ritz solve: eigenvectors (order nbr l) and values
+  std::vector<float> hs;                           // results: the values, the signs of the modes
+  std::vector<double> sign;
+
+  C64Driver(eofx_ctx* c, const eofx_mat* a, const C64Plan& plan, int64_t ptot, int k_)
+      : ctx(c), A(a), pl(plan), p_total(ptot), shd(ptot > 0), l(plan.l), LP(plan.LP), k(k_), pp(c->prec_power), pf(c->prec_final),
+        trace(std::getenv("EOFX_C64_TRACE") != nullptr), hG((size_t)LP * LP), dref(l), ones(l, 1.0), Rf(plan.nbmax), sign(k_, 1.0) {}
+
+  template <typename T_>
+  int take(T_*& ptr, size_t count, const char* name) {
+    ptr = arena_alloc<T_>(ctx, count);
+    return ptr ? EOFX_OK : set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (%s)", name);
   }
-  CplxOps ops{ctx, A, B, LP, rot, tmp, B ? std::max(A->absmax, B->absmax) : A->absmax};
-  ops.Hop = B ? nullptr : Hop;
-  if (lean) CHK(cplx_lean_setup(ctx, ops));
-  const int pp = ctx->prec_power, pf = ctx->prec_final;
-  auto fwd = [&](const float* in, float* out, int prec) { return transposed ? ops.zh_mul(in, out, prec) : ops.z_mul(in, out, prec); };
-  auto bwd = [&](const float* in, float* out, int prec) -> int {
-    if (!transposed) return ops.zh_mul(in, out, prec);
+  int allocate(const eofx_mat* B, const eofx_mat* Hop, bool lean) {
+    float *rot = nullptr, *tmp = nullptr;
+    CHK(take(Zs, (size_t)pl.small_pad * LP, "Zs"));
+    CHK(take(Ws, (size_t)pl.small_pad * LP, "Ws"));
+    CHK(take(Yt, (size_t)pl.tall_pad * LP, "Yt"));
+    CHK(take(Qt, (size_t)pl.tall_pad * LP, "Qt"));
+    CHK(take(rot, (size_t)pl.big * LP, "rot"));
+    CHK(take(tmp, (size_t)pl.big * LP, "tmp"));
+    CHK(take(Tv, (size_t)pl.tall_pad * pl.Lo, "Tv"));
+    CHK(take(Sv, (size_t)pl.small_pad * pl.Lo, "Sv"));
+    CHK(take(G, (size_t)LP * LP, "G"));
+    CHK(take(Ed, (size_t)LP * LP, "Ed"));
+    if (pl.krylov) {
+      Kw = arena_alloc<float>(ctx, (size_t)pl.small_pad * pl.ldk);
+      Ww = arena_alloc<float>(ctx, (size_t)pl.small_pad * pl.ldk);
+      Pt = arena_alloc<float>(ctx, (size_t)pl.nbmax * pl.tall_pad * LP);
+      Vs = arena_alloc<float>(ctx, (size_t)pl.small_pad * LP);
+      Cd = arena_alloc<double>(ctx, (size_t)pl.nbmax * LP * LP);
+      Ecd = arena_alloc<double>(ctx, (size_t)pl.nbmax * LP * LP);
+      Eall = arena_alloc<double>(ctx, (size_t)pl.nbmax * LP * LP);
+      Cf = arena_alloc<double>(ctx, (size_t)pl.nbmax * pl.nbmax * LP * LP);
+      if (!Kw || !Ww || !Pt || !Vs || !Cd || !Ecd || !Eall || !Cf) return set_err(ctx, EOFX_ERR_NOMEM, "arena exhausted (block Krylov panels)");
+    }
+    ops = CplxOps{ctx, A, B, LP, rot, tmp, B ? std::max(A->absmax, B->absmax) : A->absmax};
+    ops.Hop = B ? nullptr : Hop;
+    if (lean) CHK(cplx_lean_setup(ctx, ops));
+    return EOFX_OK;
+  }
+  // start panel [Omega | 0]: a real Gaussian (or the identity for a full-width sketch, which the caller passes as omega)
+  int start(const float* omega, int omega_cols) {
+    std::vector<float> host((size_t)pl.small * LP, 0.f);
+    for (int64_t i = 0; i < pl.small; ++i)
+      for (int j = 0; j < l; ++j) host[(size_t)i * LP + j] = omega[(size_t)i * omega_cols + j];
+    CHK(import_panel(ctx, host.data(), pl.small, LP, Zs, pl.small_pad, LP));
+    // (adaptive subspace iteration: the tall panel is orthonormalised in every iteration -- only then is W^H W the Rayleigh
+    // quotient whose eigenvalues are compared)
+    orth_always = (pl.adaptive && !pl.krylov) || orth_tall_rule(shd ? round_up(p_total, ATB_BM) : pl.tall_pad, LP, pp);
+    orth_rest = orth_always;
+    ctx->last_iters = 0;
+    return EOFX_OK;
+  }
+
+  // ---- the steps ------------------------------------------------------------------------------------------------------------
+  int fwd(const float* in, float* out, int prec) { return pl.transposed ? ops.zh_mul(in, out, prec) : ops.z_mul(in, out, prec); }
+  int bwd(const float* in, float* out, int prec) {
+    if (!pl.transposed) return ops.zh_mul(in, out, prec);
     CHK(ops.z_mul(in, out, prec));
     if (shd) {                       // the partial sum over this rank's features -> the sum over all of them
       amax_forget(ctx, out);
-      CHK(comm_allreduce(ctx, out, small_pad * LP, 0, 0));
+      CHK(comm_allreduce(ctx, out, pl.small_pad * LP, 0, 0));
     }
     return EOFX_OK;
-  };
-  std::vector<double> hG((size_t)LP * LP), hE;
-  std::vector<zdouble> H, T;
-  auto gram_h = [&](const float* P, int64_t rows_pad, bool tall_side = false) -> int {
+  }
+  // H <- P^H P (Hermitian l x l, on the host; synchronises)
+  int gram_h(const float* P, int64_t rows_pad, bool tall_side = false) {
     CHK(launch_gram(ctx, P, rows_pad, LP, G));
     if (shd && tall_side) CHK(comm_allreduce(ctx, G, (int64_t)LP * LP, 1, 0));     // rows sharded over the ranks
     HIPCHK(hipMemcpyAsync(hG.data(), G, sizeof(double) * LP * LP, hipMemcpyDeviceToHost, ctx->stream));
@@ -4393,94 +4385,74 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
     if (!hostla::hermitian_from_real(hG.data(), LP, l, H))
       return set_err(ctx, EOFX_ERR_LINALG, "SVD failed. This may be due to isolated NaN values in the data.");
     return EOFX_OK;
-  };
-  auto right_mul = [&](const float* P, int64_t rows_pad, const std::vector<zdouble>& M, int mcols, int Lout, float* out, const double* colscale = nullptr) -> int {
+  }
+  // out [rows_pad x Lout] <- P M for a complex l x mcols matrix M on the host (columns scaled by colscale)
+  int right_mul(const float* P, int64_t rows_pad, const std::vector<zdouble>& M, int mcols, int Lout, float* out, const double* colscale = nullptr) {
     hostla::embed_right(M.data(), l, l, mcols, LP, Lout, hE, colscale);
     HIPCHK(hipMemcpyAsync(Ed, hE.data(), sizeof(double) * LP * Lout, hipMemcpyHostToDevice, ctx->stream));
     CHK(launch_matmul(ctx, P, rows_pad, LP, Ed, Lout, out));
     HIPCHK(hipStreamSynchronize(ctx->stream));    // hE / Ed are reused
     return EOFX_OK;
-  };
-  auto orth = [&](const float* P, int64_t rows_pad, float* out, bool tall_side = false) -> int {
+  }
+  // out <- the Q factor of P (Cholesky-QR)
+  int orth(const float* P, int64_t rows_pad, float* out, bool tall_side = false) {
     CHK(gram_h(P, rows_pad, tall_side));
     hostla::chol_rinv(H.data(), l, l, T, 1e-13);
     return right_mul(P, rows_pad, T, l, LP, out);
-  };
-  // start panel [Omega | 0]: a real Gaussian (or the identity for a full-width sketch, which the caller passes as omega)
-  {
-    std::vector<float> host((size_t)small * LP, 0.f);
-    for (int64_t i = 0; i < small; ++i)
-      for (int j = 0; j < l; ++j) host[(size_t)i * LP + j] = omega[(size_t)i * (k + n_oversamples) + j];
-    CHK(import_panel(ctx, host.data(), small, LP, Zs, small_pad, LP));
   }
-  // (adaptive subspace iteration: the tall panel is orthonormalised in every iteration -- only then is W^H W the Rayleigh
-  // quotient whose eigenvalues are compared)
-  const bool orth_always = (adaptive && !krylov) || orth_tall_rule(shd ? round_up(p_total, ATB_BM) : tall_pad, LP, pp);
-  const bool trace = std::getenv("EOFX_C64_TRACE") != nullptr;
-  ctx->last_iters = 0;
-
-  // ---- block Lanczos state: blocks Z_0 .. Z_{nb-1} side by side in Kw (orthonormal, dead columns zero); block b < nW has
-  //      been multiplied: slot b of Pt holds A_op Z_b (or its Q factor, then Rf[b] is the triangular factor) and block b of Ww
-  //      holds W_b with M Z_b = W_b Rf[b]
-  auto copy_block = [&](float* wide, const float* src, int blk) -> int {
-    HIPCHK(hipMemcpy2DAsync(wide + (size_t)blk * LP, sizeof(float) * ldk, src, sizeof(float) * LP, sizeof(float) * LP, (size_t)small_pad,
+  int copy_block(float* wide, const float* src, int blk_) {
+    HIPCHK(hipMemcpy2DAsync(wide + (size_t)blk_ * LP, sizeof(float) * pl.ldk, src, sizeof(float) * LP, sizeof(float) * LP, (size_t)pl.small_pad,
                             hipMemcpyDeviceToDevice, ctx->stream));
     return EOFX_OK;
-  };
-  std::vector<double> hC;
+  }
   // out = Win - K (K^H Win) over the first nbk blocks; the real cross-Gram K^T Win stays in Cd (and in hC when asked for)
-  auto project = [&](const float* Win, int nbk, float* out, bool to_host) -> int {
-    CHK(launch_xgram(ctx, Kw, ldk, nbk * LP, Win, LP, LP, small_pad, Cd));
+  int project(const float* Win, int nbk, float* out, bool to_host) {
+    CHK(launch_xgram(ctx, Kw, pl.ldk, nbk * LP, Win, LP, LP, pl.small_pad, Cd));
     if (to_host) {
       hC.resize((size_t)nbk * LP * LP);
       HIPCHK(hipMemcpyAsync(hC.data(), Cd, sizeof(double) * hC.size(), hipMemcpyDeviceToHost, ctx->stream));
     }
-    hipLaunchKernelGGL(cproj_embed_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)nbk * h * h + 255) / 256, 1024)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(cproj_embed_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)nbk * pl.h * pl.h + 255) / 256, 1024)), dim3(256), 0, ctx->stream,
                        (const double*)Cd, nbk, LP, Ecd);
     KCHK();
-    return launch_matmul_gen(ctx, Kw, ldk, 64, 1 << 20, small_pad, nbk * LP, Ecd, LP, Win, out);
-  };
-  int nb = 0, nW = 0;
-  bool exhausted = false, orth_rest = orth_always;
-  std::vector<std::vector<zdouble>> Rf(nbmax), raw; // (Rf: empty = identity: the tall panel was not orthonormalised)
-  std::vector<zdouble> Hqq, blk;
-  std::vector<double> dref(l), ones(l, 1.0);
+    return launch_matmul_gen(ctx, Kw, pl.ldk, 64, 1 << 20, pl.small_pad, nbk * LP, Ecd, LP, Win, out);
+  }
   // multiply the newest block (b = nb - 1 = nW): slot b of Pt <- A_op Z_b, or its Q factor and Rf[b]; hqq (optional): P^H P of the product
-  auto multiply_newest = [&](std::vector<zdouble>* hqq) -> int {
-    float* slot = Pt + (size_t)nW * tall_pad * LP;
+  int multiply_newest(std::vector<zdouble>* hqq) {
+    float* slot = Pt + (size_t)nW * pl.tall_pad * LP;
     Rf[nW].clear();
     if (ctx->last_iters == 0 || orth_rest) {
       CHK(fwd(Zs, Yt, pp));
-      CHK(gram_h(Yt, tall_pad, true));
+      CHK(gram_h(Yt, pl.tall_pad, true));
       if (hqq) *hqq = H;
       hostla::chol_rinv(H.data(), l, l, T, 1e-13, &Rf[nW]);
-      return right_mul(Yt, tall_pad, T, l, LP, slot);
+      return right_mul(Yt, pl.tall_pad, T, l, LP, slot);
     }
     CHK(fwd(Zs, slot, pp));
     if (hqq) {
-      CHK(gram_h(slot, tall_pad, true));
+      CHK(gram_h(slot, pl.tall_pad, true));
       *hqq = H;
     }
     return EOFX_OK;
-  };
+  }
   // one step: multiply the newest block, W_b; then the next block = what is left of W_b after two rounds of
   // (project on all blocks, Cholesky-QR).  A column of the new block dies when what is left of it after the columns before it
   // falls below 1e-13 of its own squared norm (as everywhere), or -- first round -- below 1e-10 of its squared norm BEFORE the
   // projection (a residual below 1e-5 of the product is the rounding noise of a converged direction), or -- second round --
   // when the re-projected unit column kept less than half its length (it lay inside the blocks already there).
-  auto lanczos_step = [&]() -> int {
+  int lanczos_step() {
     const int b = nW;
     CHK(multiply_newest(nullptr));
-    CHK(bwd(Pt + (size_t)b * tall_pad * LP, Ws, pp));
+    CHK(bwd(Pt + (size_t)b * pl.tall_pad * LP, Ws, pp));
     const bool first = ctx->last_iters == 0;
     ++ctx->last_iters;
     CHK(copy_block(Ww, Ws, b));
     nW = b + 1;
     CHK(project(Ws, nb, Vs, true));
-    CHK(gram_h(Vs, small_pad));                      // (synchronises: hC is on the host)
+    CHK(gram_h(Vs, pl.small_pad));                   // (synchronises: hC is on the host)
     hostla::product_norms(H, hC.data(), nb, LP, l, dref);
-    if (first && !orth_always && n_iter > 1) {       // peaked spectrum?  H_00 = Z_0^H M Z_0 is on the host
-      hostla::cplx_block(hC.data(), LP, h, l, blk);
+    if (first && !orth_always && pl.n_iter > 1) {    // peaked spectrum?  H_00 = Z_0^H M Z_0 is on the host
+      hostla::cplx_block(hC.data(), LP, pl.h, l, blk);
       std::vector<zdouble> H00 = Rf[0].empty() ? blk : hostla::zmatmul(blk, Rf[0], l), V0;
       hostla::hermitise(H00, l);
       std::vector<double> w0;
@@ -4488,12 +4460,12 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
     }
     int live = 0;
     hostla::chol_rinv(H.data(), l, l, T, 1e-13, (std::vector<zdouble>*)nullptr, &live, dref.data(), 1e-10);
-    CHK(right_mul(Vs, small_pad, T, l, LP, Zs));
+    CHK(right_mul(Vs, pl.small_pad, T, l, LP, Zs));
     if (live > 0) {
       CHK(project(Zs, nb, Vs, false));
-      CHK(gram_h(Vs, small_pad));
+      CHK(gram_h(Vs, pl.small_pad));
       hostla::chol_rinv(H.data(), l, l, T, 1e-13, (std::vector<zdouble>*)nullptr, &live, ones.data(), 0.25);
-      CHK(right_mul(Vs, small_pad, T, l, LP, Zs));
+      CHK(right_mul(Vs, pl.small_pad, T, l, LP, Zs));
     }
     if (trace) fprintf(stderr, "[eofx_rsvd_c64] product %d: %d live columns in the next block (%d blocks)\n", ctx->last_iters, live, nb + (live > 0));
     if (live == 0) {
@@ -4503,20 +4475,17 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
     CHK(copy_block(Kw, Zs, nb));
     ++nb;
     return EOFX_OK;
-  };
+  }
   // Rayleigh-Ritz over the first nbr blocks: H = K^H M K from the columns K^H W_i Rf[i] (i < nW) and, when the newest block has no
-  // product yet, P^H P of its tall panel (Hqq).  -> leading l eigenvectors X (order nbr l), values wv; res[j] (with_res): the
-  // norm of the part of M K y_j outside the first nbr blocks, read off the coupling to block nbr.
-  std::vector<double> Xr, Xi, wv, hCf, Hr, Hi;
-  auto rayleigh_ritz = [&](int nbr, bool with_last, std::vector<double>* res) -> int {
+  // product yet, P^H P of its tall panel (Hqq).  -> leading l eigenvectors (Xr, Xi; order nbr l), values wv
+  int rayleigh_ritz(int nbr, bool with_last) {
     const int nWr = std::min(nW, nbr);
-    const int nrow = res ? std::min(nb, nbr + 1) : nbr;         // one more block row: the coupling
-    CHK(launch_xgram(ctx, Kw, ldk, nrow * LP, Ww, ldk, nWr * LP, small_pad, Cf));
-    hCf.resize((size_t)nrow * LP * nWr * LP);
+    CHK(launch_xgram(ctx, Kw, pl.ldk, nbr * LP, Ww, pl.ldk, nWr * LP, pl.small_pad, Cf));
+    hCf.resize((size_t)nbr * LP * nWr * LP);
     HIPCHK(hipMemcpyAsync(hCf.data(), Cf, sizeof(double) * hCf.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     const int m = nbr * l;
-    hostla::ritz_assemble(hCf.data(), nrow, nWr, nbr, LP, l, Rf, with_last ? &Hqq : nullptr, raw, Hr, Hi);
+    hostla::ritz_assemble(hCf.data(), nbr, nWr, nbr, LP, l, Rf, with_last ? &Hqq : nullptr, ritz_raw, Hr, Hi);
     if (!hostla::all_finite(Hr.data(), Hr.size())) return set_err(ctx, EOFX_ERR_LINALG, "SVD failed. This may be due to isolated NaN values in the data.");
     wv.assign(l, 0.0);
     Xr.assign((size_t)m * l, 0.0);
@@ -4527,15 +4496,10 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
                        1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_rr0).count());
     if (rc_rr != 0 && hosteig::zheigh_top_embedded(Hr.data(), Hi.data(), m, l, wv.data(), Xr.data(), Xi.data()) != 0)
       return set_err(ctx, EOFX_ERR_LINALG, "complex SVD: Rayleigh-Ritz eigen-solver failed");
-    if (res) {
-      res->assign(l, 0.0);
-      if (nrow > nbr) hostla::ritz_residual(raw, nbr, nWr, l, Xr.data(), Xi.data(), *res);
-    }
     return EOFX_OK;
-  };
-  // coefficient stack for a linear combination of per-block panels: block b gets Rf[b] y_b (with_rf) or y_b
-  std::vector<double> hEall;
-  auto coeff_stack = [&](int nbr, bool with_rf) -> int {
+  }
+  // Eall <- the coefficient stack for a linear combination of per-block panels: block b gets Rf[b] y_b (with_rf) or y_b
+  int coeff_stack(int nbr, bool with_rf) {
     hEall.assign((size_t)nbr * LP * LP, 0.0);
     std::vector<double> eb;
     for (int b = 0; b < nbr; ++b) {
@@ -4546,21 +4510,21 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
     }
     HIPCHK(hipMemcpyAsync(Eall, hEall.data(), sizeof(double) * hEall.size(), hipMemcpyHostToDevice, ctx->stream));
     return EOFX_OK;
-  };
+  }
   // thick restart when the space is full: blocks 0 .. nb-2 (all multiplied) collapse to their leading Ritz block X = K y, with
   // A_op X and M X as the same combination of the kept panels; the newest block (not yet multiplied) follows it
-  auto compress = [&]() -> int {
+  int compress() {
     const int nbr = nb - 1;
-    CHK(rayleigh_ritz(nbr, false, nullptr));
+    CHK(rayleigh_ritz(nbr, false));
     if (trace) fprintf(stderr, "[eofx_rsvd_c64] thick restart after %d products: %d blocks -> Ritz block + newest block\n", ctx->last_iters, nb);
     CHK(coeff_stack(nbr, false));
-    CHK(launch_matmul_gen(ctx, Kw, ldk, 64, 1 << 20, small_pad, nbr * LP, Eall, LP, nullptr, Vs));        // X
+    CHK(launch_matmul_gen(ctx, Kw, pl.ldk, 64, 1 << 20, pl.small_pad, nbr * LP, Eall, LP, nullptr, Vs));        // X
     HIPCHK(hipStreamSynchronize(ctx->stream));
     CHK(coeff_stack(nbr, true));
-    CHK(launch_matmul_gen(ctx, Ww, ldk, 64, 1 << 20, small_pad, nbr * LP, Eall, LP, nullptr, Ws));        // M X
-    CHK(launch_matmul_gen(ctx, Pt, LP, tall_pad * LP, LP / 64, tall_pad, nbr * LP, Eall, LP, nullptr, Yt)); // A_op X
+    CHK(launch_matmul_gen(ctx, Ww, pl.ldk, 64, 1 << 20, pl.small_pad, nbr * LP, Eall, LP, nullptr, Ws));        // M X
+    CHK(launch_matmul_gen(ctx, Pt, LP, pl.tall_pad * LP, LP / 64, pl.tall_pad, nbr * LP, Eall, LP, nullptr, Yt)); // A_op X
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipMemcpyAsync(Pt, Yt, sizeof(float) * (size_t)tall_pad * LP, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(Pt, Yt, sizeof(float) * (size_t)pl.tall_pad * LP, hipMemcpyDeviceToDevice, ctx->stream));
     CHK(copy_block(Kw, Vs, 0));
     CHK(copy_block(Ww, Ws, 0));
     CHK(copy_block(Kw, Zs, 1));
@@ -4568,22 +4532,22 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
     nb = 2;
     nW = 1;
     return EOFX_OK;
-  };
+  }
 
-  std::vector<double> w;
-  std::vector<zdouble> Uh;
-  if (krylov) {
-    CHK(orth(Zs, small_pad, Vs));                    // Z_0: the orthonormalised start panel
+  // ---- the stages: either range finder leaves the tall panel of the chosen subspace in Yt --------------------------------------
+  int range_krylov() {
+    const int n_iter = pl.n_iter;
+    CHK(orth(Zs, pl.small_pad, Vs));                 // Z_0: the orthonormalised start panel
     std::swap(Zs, Vs);
     CHK(copy_block(Kw, Zs, 0));
     nb = 1;
     // "converge" (round 6): the Ritz values' own history (hostla::RitzHistory) decides when to stop, or 20 products (lobpcg's limit under svds)
-    hostla::RitzHistory history(auto_count, it_min);
+    hostla::RitzHistory history(pl.auto_count, C64_IT_MIN);
     while (ctx->last_iters < n_iter && !exhausted) {
-      if (nb == nbmax) CHK(compress());
+      if (nb == pl.nbmax) CHK(compress());
       CHK(lanczos_step());
-      if (adaptive && !exhausted && ctx->last_iters >= history.next_check && ctx->last_iters < n_iter) {
-        CHK(rayleigh_ritz(nb - 1, false, nullptr));
+      if (pl.adaptive && !exhausted && ctx->last_iters >= history.next_check && ctx->last_iters < n_iter) {
+        CHK(rayleigh_ritz(nb - 1, false));
         const bool stop = history.feed(wv.data(), k, l, ctx->last_iters, n_iter);
         if (trace) fprintf(stderr, "[eofx_rsvd_c64] after %d products: worst (error estimate / tolerance) over the leading %d Ritz values %.3e\n", ctx->last_iters, k, history.worst);
         if (stop) break;
@@ -4596,28 +4560,31 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
       CHK(multiply_newest(&Hqq));
       with_last = true;
     }
-    CHK(rayleigh_ritz(nb, with_last, nullptr));
+    CHK(rayleigh_ritz(nb, with_last));
     if (trace) fprintf(stderr, "[eofx_rsvd_c64] Rayleigh-Ritz over %d blocks (order %d) after %d products: leading Ritz values %.6e %.6e ... %.6e\n", nb, nb * l, ctx->last_iters, wv[0], l > 1 ? wv[1] : 0.0, wv[l - 1]);
     CHK(coeff_stack(nb, true));
-    CHK(launch_matmul_gen(ctx, Pt, LP, tall_pad * LP, LP / 64, tall_pad, nb * LP, Eall, LP, nullptr, Yt));   // A_op K y
-  } else {
+    return launch_matmul_gen(ctx, Pt, LP, pl.tall_pad * LP, LP / 64, pl.tall_pad, nb * LP, Eall, LP, nullptr, Yt);   // A_op K y
+  }
+  // the subspace iteration of rounds 1-4
+  int range_subspace() {
+    const int n_iter = pl.n_iter;
     std::vector<double> ritz_prev, w0;
     std::vector<zdouble> V0;
     int calm = 0;
     for (int it = 0; it < n_iter; ++it) {
       CHK(fwd(Zs, Yt, pp));
       if (it == 0 || orth_rest) {
-        CHK(orth(Yt, tall_pad, Qt, true));
+        CHK(orth(Yt, pl.tall_pad, Qt, true));
         CHK(bwd(Qt, Ws, pp));
       } else {
         CHK(bwd(Yt, Ws, pp));
       }
-      CHK(gram_h(Ws, small_pad));
+      CHK(gram_h(Ws, pl.small_pad));
       ctx->last_iters = it + 1;
       if (it == 0 && !orth_always && n_iter > 1)     // peaked spectrum?  the Hermitian Gram matrix is on the host already
         orth_rest = hosteig::heigh(H, l, w0, V0) != 0 || hostla::peaked_spectrum(w0.data(), l);      // (a failed solve keeps the step)
       bool done = false;
-      if (adaptive && hosteig::heigh(H, l, w0, V0) == 0) {
+      if (pl.adaptive && hosteig::heigh(H, l, w0, V0) == 0) {
         double worst = 0.0;
         if (ritz_prev.size() == (size_t)k)
           for (int j = 0; j < k; ++j) worst = std::max(worst, std::fabs(w0[j] - ritz_prev[j]) / std::max(w0[j], 1e-300));
@@ -4626,55 +4593,61 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
         ritz_prev.assign(w0.begin(), w0.begin() + k);
         calm = worst <= 1e-6 ? calm + 1 : 0;
         if (trace) fprintf(stderr, "[eofx_rsvd_c64] iteration %d: max relative change of the leading %d Ritz values %.3e\n", it + 1, k, worst);
-        done = calm >= 2 && it + 1 >= it_min;
+        done = calm >= 2 && it + 1 >= C64_IT_MIN;
       }
       hostla::chol_rinv(H.data(), l, l, T, 1e-13);
-      CHK(right_mul(Ws, small_pad, T, l, LP, Zs));
+      CHK(right_mul(Ws, pl.small_pad, T, l, LP, Zs));
       if (done) break;
     }
-    CHK(fwd(Zs, Yt, pp));
+    return fwd(Zs, Yt, pp);
   }
-  CHK(orth(Yt, tall_pad, Qt, true));
-  CHK(orth(Qt, tall_pad, Yt, true));                     // Q in Yt (CholeskyQR2: the final stage starts from the tall panel in Yt)
-  CHK(bwd(Yt, Ws, pf));                            // B^H, B = Q^H A_op
-  CHK(gram_h(Ws, small_pad));                      // B B^H
-  if (hosteig::heigh(H, l, w, Uh) != 0) return set_err(ctx, EOFX_ERR_LINALG, "complex SVD: Hermitian eigen-solver failed");
-  std::vector<float> hs(k);
-  std::vector<double> inv(k);
-  for (int j = 0; j < k; ++j) {
-    const double sv = std::sqrt(std::max(w[j], 0.0));
-    hs[j] = (float)sv;
-    inv[j] = sv > 0.0 ? 1.0 / sv : 0.0;
+  // CholeskyQR2 of the tall panel, one projection pass, the l x l Hermitian problem: values in hs, factors in Tv (tall) and Sv (small)
+  int final_stage() {
+    std::vector<double> w;
+    std::vector<zdouble> Uh;
+    CHK(orth(Yt, pl.tall_pad, Qt, true));
+    CHK(orth(Qt, pl.tall_pad, Yt, true));            // Q in Yt
+    CHK(bwd(Yt, Ws, pf));                            // B^H, B = Q^H A_op
+    CHK(gram_h(Ws, pl.small_pad));                   // B B^H
+    if (hosteig::heigh(H, l, w, Uh) != 0) return set_err(ctx, EOFX_ERR_LINALG, "complex SVD: Hermitian eigen-solver failed");
+    hs.resize(k);
+    std::vector<double> inv(k);
+    for (int j = 0; j < k; ++j) {
+      const double sv = std::sqrt(std::max(w[j], 0.0));
+      hs[j] = (float)sv;
+      inv[j] = sv > 0.0 ? 1.0 / sv : 0.0;
+    }
+    CHK(right_mul(Yt, pl.tall_pad, Uh, k, pl.Lo, Tv));     // A_op = Tall diag(s) Small^H: Tall = Q Uh[:, :k], Small = B^H Uh[:, :k] / s
+    return right_mul(Ws, pl.small_pad, Uh, k, pl.Lo, Sv, inv.data());
   }
-  CHK(right_mul(Yt, tall_pad, Uh, k, Lo, Tv));     // A_op = Tall diag(s) Small^H: Tall = Q Uh[:, :k], Small = B^H Uh[:, :k] / s
-  CHK(right_mul(Ws, small_pad, Uh, k, Lo, Sv, inv.data()));
   // Numerically null modes (more modes asked for than the matrix has rank: the analytic signal of a short series has about
   // n / 2 + 1 independent rows): B^H u / s is rounding noise there.  The reference's solver ends with a dense SVD of A V
   // (scipy svds, _svds.py), whose left vectors are orthonormal whatever the values; here such columns of the small-side factor
   // are re-orthonormalised on the host against all the columns before them (two rounds of Gram-Schmidt in float64; a column
   // that lay inside their span is replaced by the first unit vector that does not).  Values and the tall side are untouched.
-  {
+  int repair_null_modes() {
+    const int Lo = pl.Lo;
     int first_null = k;
     for (int j = k - 1; j >= 0 && (double)hs[j] <= 3e-6 * (double)hs[0]; --j) first_null = j;
-    if (first_null < k && hs[0] > 0.f) {
-      std::vector<float> hp((size_t)small * Lo);
-      HIPCHK(hipMemcpy2DAsync(hp.data(), sizeof(float) * Lo, Sv, sizeof(float) * Lo, sizeof(float) * Lo, (size_t)small, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      hostla::null_repair_c(hp.data(), small, Lo, ko, first_null, k);
-      HIPCHK(hipMemcpy2DAsync(Sv, sizeof(float) * Lo, hp.data(), sizeof(float) * Lo, sizeof(float) * Lo, (size_t)small, hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
+    if (!(first_null < k && hs[0] > 0.f)) return EOFX_OK;
+    std::vector<float> hp((size_t)pl.small * Lo);
+    HIPCHK(hipMemcpy2DAsync(hp.data(), sizeof(float) * Lo, Sv, sizeof(float) * Lo, sizeof(float) * Lo, (size_t)pl.small, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    hostla::null_repair_c(hp.data(), pl.small, Lo, pl.ko, first_null, k);
+    HIPCHK(hipMemcpy2DAsync(Sv, sizeof(float) * Lo, hp.data(), sizeof(float) * Lo, sizeof(float) * Lo, (size_t)pl.small, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return EOFX_OK;
   }
-  const float* Vp = transposed ? Tv : Sv;
-  const float* Up = transposed ? Sv : Tv;
-  std::vector<double> sign(k, 1.0);
-  if (flip_signs) {
-    // VT = conj(V)^T; numpy's max / min of complex numbers are lexicographic (real part, then imaginary part)
+  const float* Vp() const { return pl.transposed ? Tv : Sv; }
+  const float* Up() const { return pl.transposed ? Sv : Tv; }
+  // the reference's sign rule on VT = conj(V)^T; numpy's max / min of complex numbers are lexicographic (real part, then imaginary part)
+  int signs() {
+    const int Lo = pl.Lo;
     ARENA(int64_t, amax, Lo);
     ARENA(int64_t, amin, Lo);
-    CHK(panel_colargminmax(ctx, Vp, p, Lo, amax, amin, A->masked ? A->aff + 2 * A->p_pad : nullptr));   // (scale plane: 0 at masked features)
+    CHK(panel_colargminmax(ctx, Vp(), A->p, Lo, amax, amin, A->masked ? A->aff + 2 * A->p_pad : nullptr));   // (scale plane: 0 at masked features)
     ARENA(float, picks, 4 * (size_t)k);
-    hipLaunchKernelGGL(cpanel_pick_kernel, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, Vp, Lo, k, amax, amin, picks);
+    hipLaunchKernelGGL(cpanel_pick_kernel, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, Vp(), Lo, k, amax, amin, picks);
     KCHK();
     std::vector<float> c(4 * (size_t)k);
     HIPCHK(hipMemcpyAsync(c.data(), picks, sizeof(float) * 4 * k, hipMemcpyDeviceToHost, ctx->stream));
@@ -4684,34 +4657,40 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
       mag[j] = std::hypot((double)c[4 * j], (double)c[4 * j + 1]);
       mag[k + j] = std::hypot((double)c[4 * j + 2], (double)c[4 * j + 3]);
     }
-    if (shd) {
-      // global lexicographic extrema over the slices: the largest / smallest real part wins (all-reduce(max) of [re_max | -re_min]),
-      // the rank that holds it contributes the magnitude of its entry (all-reduce(max) of float64, -1 from the others)
-      ARENA(float, dre, 2 * (size_t)k);
-      ARENA(double, dmag, 2 * (size_t)k);
-      std::vector<float> re(2 * (size_t)k), gre(2 * (size_t)k);
-      for (int j = 0; j < k; ++j) {
-        re[j] = p > 0 ? c[4 * j] : -INFINITY;
-        re[k + j] = p > 0 ? -c[4 * j + 2] : -INFINITY;
-      }
-      HIPCHK(hipMemcpyAsync(dre, re.data(), sizeof(float) * 2 * k, hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      CHK(comm_allreduce(ctx, dre, 2 * (int64_t)k, 0, 1));
-      HIPCHK(hipMemcpyAsync(gre.data(), dre, sizeof(float) * 2 * k, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      for (int j = 0; j < 2 * k; ++j)
-        if (!(p > 0 && re[j] == gre[j])) mag[j] = -1.0;
-      HIPCHK(hipMemcpyAsync(dmag, mag.data(), sizeof(double) * 2 * k, hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      CHK(comm_allreduce(ctx, dmag, 2 * (int64_t)k, 1, 1));
-      HIPCHK(hipMemcpyAsync(mag.data(), dmag, sizeof(double) * 2 * k, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
+    if (shd) CHK(signs_exchange(c, mag));
     for (int j = 0; j < k; ++j)   // |max| >= |min| in numpy's lexicographic complex order (real part decides)
       sign[j] = mag[j] >= mag[k + j] ? 1.0 : -1.0;
+    return EOFX_OK;
   }
-  // interleaved complex64 exports
-  auto export_c = [&](const float* P, int64_t rows, float* dst) -> int {
+  // dst <- all-reduce(max) of src (host vectors of `count` entries) through the device buffer dev
+  template <typename T_>
+  int allreduce_max_host(T_* dev, const T_* src, T_* dst, int count, int dtype) {
+    HIPCHK(hipMemcpyAsync(dev, src, sizeof(T_) * count, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    CHK(comm_allreduce(ctx, dev, (int64_t)count, dtype, 1));
+    HIPCHK(hipMemcpyAsync(dst, dev, sizeof(T_) * count, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return EOFX_OK;
+  }
+  // global lexicographic extrema over the slices: the largest / smallest real part wins (all-reduce(max) of [re_max | -re_min]),
+  // the rank that holds it contributes the magnitude of its entry (all-reduce(max) of float64, -1 from the others)
+  int signs_exchange(const std::vector<float>& c, std::vector<double>& mag) {
+    const int64_t p = A->p;
+    ARENA(float, dre, 2 * (size_t)k);
+    ARENA(double, dmag, 2 * (size_t)k);
+    std::vector<float> re(2 * (size_t)k), gre(2 * (size_t)k);
+    for (int j = 0; j < k; ++j) {
+      re[j] = p > 0 ? c[4 * j] : -INFINITY;
+      re[k + j] = p > 0 ? -c[4 * j + 2] : -INFINITY;
+    }
+    CHK(allreduce_max_host(dre, re.data(), gre.data(), 2 * k, 0));
+    for (int j = 0; j < 2 * k; ++j)
+      if (!(p > 0 && re[j] == gre[j])) mag[j] = -1.0;
+    CHK(allreduce_max_host(dmag, mag.data(), mag.data(), 2 * k, 1));
+    return EOFX_OK;
+  }
+  // interleaved complex64 export of the leading k columns of a panel, signs applied
+  int export_c(const float* P, int64_t rows, float* dst) {
     if (!dst) return EOFX_OK;
     ArenaScope sc(ctx);
     double* dsign = arena_alloc<double>(ctx, k);
@@ -4725,17 +4704,66 @@ static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, co
     }
     const int64_t total = rows * k;
     hipLaunchKernelGGL(cpanel_export_kernel, dim3((int)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, ctx->stream, P,
-                       rows, Lo, k, dsign, t);
+                       rows, pl.Lo, k, dsign, t);
     KCHK();
     if (!dev) CHK(copy_out(ctx, dst, t, sizeof(float) * total * 2));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return EOFX_OK;
-  };
-  CHK(export_c(Up, n, U));
-  CHK(export_c(Vp, p, V));
-  if (is_device_ptr(s)) HIPCHK(hipMemcpy(s, hs.data(), sizeof(float) * k, hipMemcpyHostToDevice));
-  else std::memcpy(s, hs.data(), sizeof(float) * k);
-  return EOFX_OK;
+  }
+  int export_all(float* U, float* s, float* V) {
+    CHK(export_c(Up(), A->n, U));
+    CHK(export_c(Vp(), A->p, V));
+    if (is_device_ptr(s)) HIPCHK(hipMemcpy(s, hs.data(), sizeof(float) * k, hipMemcpyHostToDevice));
+    else std::memcpy(s, hs.data(), sizeof(float) * k);
+    return EOFX_OK;
+  }
+};
+
+// today's message for the check of the plan that failed
+static int c64_plan_error(eofx_ctx* ctx, const C64Plan& pl) {
+  switch (pl.status) {
+    case C64_PLAN_OK: return EOFX_OK;
+    case C64_PLAN_SHARD_SIDE: return set_err(ctx, EOFX_ERR_ARG, "the sharded complex decomposition needs the sketch on the sample side (n < p_total)");
+    case C64_PLAN_RANK: return set_err(ctx, EOFX_ERR_RANK, "n_modes must be less than or equal to the rank of the dataset (rank = %lld).", (long long)pl.r);
+    case C64_PLAN_WIDTH: return set_err(ctx, EOFX_ERR_ARG, "complex sketch width %d > 64 is not supported (n_modes + n_oversamples <= 64)", pl.l);
+    case C64_PLAN_MASKED: return set_err(ctx, EOFX_ERR_ARG, "masked in-place matrix with fewer valid features than samples");
+    default: return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  }
+}
+
+static int rsvd_c64_impl(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, const eofx_mat* Hop, int k, int n_oversamples,
+                         int n_iter, const float* omega, int flip_signs, float* U, float* s, float* V, int64_t p_total = 0) {
+  if (!ctx || !A || (!B && !Hop) || !omega || !s || k <= 0 || n_oversamples < 0)
+    return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (B && (A->n != B->n || A->p != B->p)) return set_err(ctx, EOFX_ERR_SHAPE, "real and imaginary parts must have the same shape");
+  ENTER(ctx);
+  const bool shd = p_total > 0;
+  if (shd && !ctx->comm) return set_err(ctx, EOFX_ERR_ARG, "no communicator attached (eofx_ctx_comm_init_rccl / eofx_ctx_comm_set_callback)");
+  const char* kenv = std::getenv("EOFX_C64_KRYLOV");
+  const C64Plan pl = c64_plan(A->n, A->p, A->n_pad, A->p_pad, p_total, A->masked, A->p_valid, k, n_oversamples, n_iter,
+                              !(kenv && atoi(kenv) == 0));
+  CHK(c64_plan_error(ctx, pl));
+  const bool lean = B && cplx_lean(A, B, pl.LP, ctx->prec_power, ctx->prec_final);
+  // (sharded: a rank-local failure of the steps before the first collective -- building a layout, growing the arena -- must not
+  // leave the other ranks in an all-reduce: it becomes this rank's vote and every rank returns together)
+  int rc_local = EOFX_OK;
+  if (B && !lean) {
+    rc_local = ensure_X(ctx, A);   // (ensure_X builds the sample-contiguous layout first where that is missing too)
+    if (rc_local == EOFX_OK) rc_local = ensure_X(ctx, B);
+  }
+  if (rc_local == EOFX_OK) rc_local = arena_reserve(ctx, pl.arena_bytes);
+  int verdict = 0;
+  if (shd) CHK(comm_agree(ctx, rc_local, 0, "the sharded complex decomposition", &verdict));
+  else CHK(rc_local);
+  ArenaScope scope(ctx);
+  C64Driver d(ctx, A, pl, p_total, k);
+  CHK(d.allocate(B, Hop, lean));
+  CHK(d.start(omega, k + n_oversamples));
+  CHK(pl.krylov ? d.range_krylov() : d.range_subspace());
+  CHK(d.final_stage());
+  CHK(d.repair_null_modes());
+  if (flip_signs) CHK(d.signs());
+  return d.export_all(U, s, V);
 }
 
 extern "C" int eofx_rsvd_c64(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, int k, int n_oversamples, int n_iter,
@@ -4748,19 +4776,29 @@ extern "C" int eofx_rsvd_c64(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B
 // Z = A + i H(A) = (I + i Hc) A with Hc the n x n operator of the Hilbert stage along the samples (padding, decay as in
 // eofx_hilbert_f32; get_hilbert_operator).  Same arguments, rules and outputs as eofx_rsvd_c64 on (A, eofx_hilbert_f32(A));
 // every product streams the real field once and applies Hc on the sample side (CplxOps operator mode), so a pass moves
-// half the bytes of the two-part form and the field needs no second resident copy.
-extern "C" int eofx_rsvd_hilbert_c64(eofx_ctx* ctx, const eofx_mat* A, int padding, double decay_factor, int k,
-                                     int n_oversamples, int n_iter, const float* omega, int flip_signs, float* U, float* s,
-                                     float* V) {
+// half the bytes of the two-part form and the field needs no second resident copy.  p_total > 0: the sharded entry.
+static int rsvd_hilbert_impl(eofx_ctx* ctx, const eofx_mat* A, int64_t p_total, int padding, double decay_factor, int k, int n_oversamples,
+                             int n_iter, const float* omega, int flip_signs, float* U, float* s, float* V) {
+  const bool shd = p_total > 0;
   if (!ctx || !A) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
   if (padding && !(decay_factor > 0.0)) return set_err(ctx, EOFX_ERR_ARG, "decay_factor must be positive");
   if (A->n > EOFX_HILBERT_OP_MAX_N)
-    return set_err(ctx, EOFX_ERR_ARG, "the resident Hilbert operator is limited to %d samples (got %lld): use eofx_hilbert_f32 + eofx_rsvd_c64",
-                   EOFX_HILBERT_OP_MAX_N, (long long)A->n);
+    return set_err(ctx, EOFX_ERR_ARG, "the resident Hilbert operator is limited to %d samples (got %lld): use eofx_hilbert_f32 + %s",
+                   EOFX_HILBERT_OP_MAX_N, (long long)A->n, shd ? "eofx_rsvd_sharded_c64" : "eofx_rsvd_c64");
+  if (shd && !ctx->comm) return set_err(ctx, EOFX_ERR_ARG, "no communicator attached (eofx_ctx_comm_init_rccl / eofx_ctx_comm_set_callback)");
   ENTER(ctx);
   const eofx_mat* Hop = nullptr;
-  CHK(get_hilbert_operator(ctx, A->n, padding ? 1 : 0, decay_factor, &Hop));
-  return rsvd_c64_impl(ctx, A, nullptr, Hop, k, n_oversamples, n_iter, omega, flip_signs, U, s, V);
+  // (sharded: building the operator -- host memory, an upload -- can fail on one rank alone: the ranks agree before the first collective)
+  const int rc_local = get_hilbert_operator(ctx, A->n, padding ? 1 : 0, decay_factor, &Hop);
+  int verdict = 0;
+  if (shd) CHK(comm_agree(ctx, rc_local, 0, "the sharded Hilbert decomposition", &verdict));
+  else CHK(rc_local);
+  return rsvd_c64_impl(ctx, A, nullptr, Hop, k, n_oversamples, n_iter, omega, flip_signs, U, s, V, p_total);
+}
+extern "C" int eofx_rsvd_hilbert_c64(eofx_ctx* ctx, const eofx_mat* A, int padding, double decay_factor, int k,
+                                     int n_oversamples, int n_iter, const float* omega, int flip_signs, float* U, float* s,
+                                     float* V) {
+  return rsvd_hilbert_impl(ctx, A, 0, padding, decay_factor, k, n_oversamples, n_iter, omega, flip_signs, U, s, V);
 }
 
 extern "C" int eofx_rsvd_sharded_c64(eofx_ctx* ctx, const eofx_mat* A, const eofx_mat* B, int64_t p_total, int k, int n_oversamples,
@@ -4772,23 +4810,8 @@ extern "C" int eofx_rsvd_sharded_c64(eofx_ctx* ctx, const eofx_mat* A, const eof
 extern "C" int eofx_rsvd_hilbert_sharded_c64(eofx_ctx* ctx, const eofx_mat* A, int64_t p_total, int padding, double decay_factor,
                                              int k, int n_oversamples, int n_iter, const float* omega, int flip_signs, float* U,
                                              float* s, float* V) {
-  if (!ctx || !A || p_total <= 0) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
-  if (padding && !(decay_factor > 0.0)) return set_err(ctx, EOFX_ERR_ARG, "decay_factor must be positive");
-  if (A->n > EOFX_HILBERT_OP_MAX_N)
-    return set_err(ctx, EOFX_ERR_ARG, "the resident Hilbert operator is limited to %d samples (got %lld): use eofx_hilbert_f32 + eofx_rsvd_sharded_c64",
-                   EOFX_HILBERT_OP_MAX_N, (long long)A->n);
-  if (!ctx->comm) return set_err(ctx, EOFX_ERR_ARG, "no communicator attached (eofx_ctx_comm_init_rccl / eofx_ctx_comm_set_callback)");
-  ENTER(ctx);
-  const eofx_mat* Hop = nullptr;
-  {   // building the operator (host memory, an upload) can fail on one rank alone: the ranks agree before the first collective
-    const int rc_local = get_hilbert_operator(ctx, A->n, padding ? 1 : 0, decay_factor, &Hop);
-    const std::string err_local = rc_local != EOFX_OK ? ctx->err : std::string();
-    int verdict = 0;
-    CHK(comm_vote(ctx, rc_local != EOFX_OK ? 2 : 0, &verdict));
-    if (verdict != 0)
-      return rc_local != EOFX_OK ? (ctx->err = err_local, rc_local) : set_err(ctx, EOFX_ERR_HIP, "the sharded Hilbert decomposition failed on another rank");
-  }
-  return rsvd_c64_impl(ctx, A, nullptr, Hop, k, n_oversamples, n_iter, omega, flip_signs, U, s, V, p_total);
+  if (p_total <= 0) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  return rsvd_hilbert_impl(ctx, A, p_total, padding, decay_factor, k, n_oversamples, n_iter, omega, flip_signs, U, s, V);
 }
 
 // sum of squares of the resident matrix in float64 (fixed tree); for zero-mean columns

@@ -187,6 +187,84 @@ inline bool orth_tall_rule(int64_t tall_pad, int L, int prec_power) {
   return prec_power == EOFX_PREC_F64 || (size_t)tall_pad * L * sizeof(float) <= EOFX_ORTH_TALL_BYTES;
 }
 
+// ---- the complex decomposition (eofx_rsvd_c64 and its Hilbert / sharded forms) ----------------------------------------------
+// Scratch of one pass of the complex operator on a panel of L real columns, either direction: the split-K partials of the two
+// streaming products, twice each (the two parts of a two-launch pass).
+inline size_t c64_pass_scratch_bytes(int64_t n, int64_t p, int64_t n_pad, int64_t p_pad, int L) {
+  return 2 * atb_scratch_bytes(p_pad, round_up(n, ATB_KG), L) + 2 * atb_scratch_bytes(n_pad, round_up(p, ATB_KG), L);
+}
+// eofx_cmat_mul_f32: the companion panel and the second product [big x L], the two partial results of a two-matrix launch that
+// needs no split, and the pass itself
+inline size_t c64_mul_scratch_bytes(int64_t n, int64_t p, int64_t n_pad, int64_t p_pad, int L) {
+  const int64_t big = std::max(n_pad, p_pad);
+  return (size_t)2 * big * L * 4 + (8 << 20) + (size_t)2 * big * L * 4 + c64_pass_scratch_bytes(n, p, n_pad, p_pad, L);
+}
+
+constexpr int KRYLOV_MAX_ORDER = 384;   // the host solves the Rayleigh-Ritz problem (~10 ms at order 240): blocks beyond are thick-restarted
+constexpr int C64_IT_MIN = 2;           // "converge": products before the first stop
+constexpr int C64_IT_CAP = 20;          // "converge": products at most (lobpcg's own limit under svds)
+enum { C64_PLAN_OK = 0, C64_PLAN_SHARD_SIDE, C64_PLAN_RANK, C64_PLAN_WIDTH, C64_PLAN_MASKED, C64_PLAN_N_ITER };
+// Sizes and routes of the complex driver for an n x p field (this rank's slice of p_total features when p_total > 0; masked:
+// p_valid of the p columns hold data).  n_iter: a count, -1 scikit-learn's (auto_count), -2 "converge".  status: the first check
+// that failed, in the order the driver reports them; nothing else is set then (but r, for the message of C64_PLAN_RANK, and l).
+struct C64Plan {
+  int status;
+  int64_t r;                  // rank bound min(n, valid features over all ranks)
+  int l;                      // sketch width (complex columns)
+  bool adaptive;              // "converge"
+  int n_iter, auto_count;     // products (resolved), scikit-learn's count
+  int h, LP;                  // complex columns of a panel (32 | 64), real columns [Re(h) | Im(h)]
+  int ko, Lo;                 // the same for the output panels [Re(ko) | Im(ko)]
+  bool transposed;            // A_op = Z^H: the tall side is the features
+  int64_t small, small_pad, tall_pad, big;
+  bool krylov;                // block Krylov (else subspace iteration)
+  int nbmax;                  // blocks kept before a thick restart
+  int64_t ldk;                // row stride of the side-by-side blocks
+  size_t arena_bytes;
+};
+inline C64Plan c64_plan(int64_t n, int64_t p, int64_t n_pad, int64_t p_pad, int64_t p_total, bool masked, int64_t p_valid, int k,
+                        int n_oversamples, int n_iter, bool krylov_allowed) {
+  C64Plan pl{};
+  auto fail = [&](int status) { return pl.status = status, pl; };
+  const bool shd = p_total > 0;
+  if (shd && !(n < p_total)) return fail(C64_PLAN_SHARD_SIDE);
+  pl.r = std::min(n, shd ? p_total : (masked ? p_valid : p));
+  if (k > pl.r) return fail(C64_PLAN_RANK);
+  pl.l = (int)std::min<int64_t>(k + n_oversamples, pl.r);
+  if (pl.l > 64) return fail(C64_PLAN_WIDTH);
+  if (!shd && masked && !(n < p_valid)) return fail(C64_PLAN_MASKED);
+  pl.adaptive = n_iter == -2;
+  pl.auto_count = k < 0.1 * (double)pl.r ? 7 : 4;
+  if (n_iter == -1) n_iter = pl.auto_count;
+  if (pl.adaptive) n_iter = C64_IT_CAP;
+  if (n_iter < 0) return fail(C64_PLAN_N_ITER);
+  pl.n_iter = n_iter;
+  const int l = pl.l;
+  pl.h = l <= 32 ? 32 : 64;
+  pl.LP = 2 * pl.h;
+  pl.ko = (int)round_up(k, 16);
+  pl.Lo = 2 * pl.ko;
+  pl.transposed = shd || n < p;
+  pl.small = pl.transposed ? n : p;
+  pl.small_pad = pl.transposed ? n_pad : p_pad;
+  pl.tall_pad = pl.transposed ? p_pad : n_pad;
+  pl.big = std::max(n_pad, p_pad);
+  const int nb_fit = KRYLOV_MAX_ORDER / l;
+  pl.krylov = n_iter >= 1 && nb_fit >= 3 && krylov_allowed;
+  pl.nbmax = pl.krylov ? std::min(n_iter + 1, nb_fit) : 0;
+  pl.ldk = (int64_t)pl.nbmax * pl.LP;
+  const int LP = pl.LP, Lo = pl.Lo, nbmax = pl.nbmax;
+  const int64_t small_pad = pl.small_pad, tall_pad = pl.tall_pad, big = pl.big;
+  size_t need = (size_t)(2 * small_pad + 2 * tall_pad + 2 * big) * LP * 4 + (size_t)(small_pad + tall_pad) * Lo * 4;
+  need += c64_pass_scratch_bytes(n, p, n_pad, p_pad, LP);
+  need += (size_t)(4 * gram_parts(big, LP) + 8) * LP * LP * 8 + (size_t)big * (Lo + LP) * 4 + (8 << 20);
+  if (pl.krylov)
+    need += (size_t)nbmax * (2 * small_pad + tall_pad) * LP * 4 + (size_t)small_pad * LP * 4 + (size_t)(3 + nbmax) * nbmax * LP * LP * 8 +
+            ((size_t)48 << 20);
+  pl.arena_bytes = need;
+  return pl;
+}
+
 // the lag operator: lags per group (see EOFX_LAG_GROUP_COLS), the lags of the last group, workgroups of its streaming kernels
 inline int lag_groupsize(int E, int L) { return std::max(1, std::min(E, EOFX_LAG_GROUP_COLS / std::max(L, 1))); }
 inline int lag_last_group(int E, int G) { return E - (E - 1) / G * G; }
