@@ -118,6 +118,32 @@ int64_t pl_c64_mul_scratch_bytes(int64_t n, int64_t p, int64_t n_pad, int64_t p_
   return (int64_t)c64_mul_scratch_bytes(n, p, n_pad, p_pad, L);
 }
 
+int64_t pl_null_repair_bytes(int64_t rows_pad, int Lo) { return (int64_t)null_repair_bytes(rows_pad, Lo); }
+int64_t pl_rinv_blocked_bytes(int l) { return (int64_t)rinv_blocked_bytes(l); }
+int64_t pl_rsvd_scratch_bytes(int64_t tall_pad, int64_t small_pad, int l, int k) { return (int64_t)rsvd_scratch_bytes(tall_pad, small_pad, l, k); }
+// out [9]: status, r, l_req, l, L, Lo, n_iter, transposed, full_width
+static void rsvd_plan_out(const RsvdPlan& q, int64_t* out) {
+  const int64_t o[] = {q.status, q.r, q.l_req, q.l, q.L, q.Lo, q.n_iter, q.transposed, q.full_width};
+  std::copy(o, o + 9, out);
+}
+void pl_rsvd_plan(int64_t rows, int64_t cols, int k, int n_oversamples, int n_iter, int64_t* out) {
+  rsvd_plan_out(rsvd_plan(rows, cols, k, n_oversamples, n_iter), out);
+}
+// out [15]: the nine of pl_rsvd_plan, then tall, small, tall_pad, small_pad, gram_route, arena_bytes
+void pl_cross_plan(int64_t n, int64_t n_pad, int64_t p1, int64_t p1_pad, int64_t p2, int64_t p2_pad, int64_t P1, int64_t P2, int sharded,
+                   int want_tsc, int fast1, int fast2, int64_t fast_scratch1, int64_t fast_scratch2, int k, int n_oversamples, int n_iter,
+                   int no_gram, int64_t* out) {
+  const CrossPlan c = cross_plan(n, n_pad, p1, p1_pad, p2, p2_pad, P1, P2, sharded != 0, want_tsc != 0, fast1 != 0, fast2 != 0,
+                                 (size_t)fast_scratch1, (size_t)fast_scratch2, k, n_oversamples, n_iter, no_gram != 0);
+  rsvd_plan_out(c, out);
+  const int64_t o[] = {c.tall, c.small, c.tall_pad, c.small_pad, c.gram_route, (int64_t)c.arena_bytes};
+  std::copy(o, o + 6, out + 9);
+}
+int pl_fused_fit_eligible(int keep_raw, int prec, int aligned16, int64_t n, int64_t P, int k, int n_oversamples, int64_t omega_rows,
+                          int omega_on_device) {
+  return fused_fit_eligible(keep_raw, prec, aligned16 != 0, n, P, k, rsvd_plan(n, P, k, n_oversamples, -1), omega_rows, omega_on_device != 0) ? 1 : 0;
+}
+
 // ---- eofx_sketch.hpp
 void sk_gaussian_f32(uint32_t seed, int64_t rows, int64_t cols, float* out) { eofx_sketch::gaussian_f32(seed, rows, cols, out); }
 int64_t sk_candidates(int64_t need) { return eofx_sketch::candidates(need); }
@@ -268,6 +294,28 @@ int main() {
       expect(o[0] != C64_PLAN_OK || (o[16] * o[2] <= KRYLOV_MAX_ORDER && o[17] == o[16] * o[7] && o[18] > 0), "c64_plan invariants");
     }
     expect(pl_c64_mul_scratch_bytes(300, 900, 512, 1024, 64) > (8 << 20), "c64_mul_scratch_bytes");
+  }
+  // the real drivers' plans, the hand cases of tests/test_plans_cpu.py: {rows, cols, k, n_oversamples, n_iter} -> {status, r, l, L,
+  // n_iter, transposed, full_width}; then the cross plan in both forms and the fused-fit predicate
+  {
+    const int64_t cases[][12] = {{700, 60, 5, 10, -1, /**/ RSVD_PLAN_OK, 60, 15, 32, 7, 0, 0},   {60, 700, 5, 10, -1, /**/ RSVD_PLAN_OK, 60, 15, 32, 7, 1, 0},
+                                 {60, 12, 4, 10, -1, /**/ RSVD_PLAN_OK, 12, 12, 32, 4, 0, 1},    {60, 12, 13, 0, -1, /**/ RSVD_PLAN_RANK, 12, 12, 32, 4, 0, 1},
+                                 {900, 400, 250, 10, 3, /**/ RSVD_PLAN_WIDTH, 400, 260, 288, 3, 0, 0}};
+    for (auto& q : cases) {
+      int64_t o[9];
+      pl_rsvd_plan(q[0], q[1], (int)q[2], (int)q[3], (int)q[4], o);
+      expect(o[0] == q[5] && o[1] == q[6] && o[3] == q[7] && o[4] == q[8] && o[6] == q[9] && o[7] == q[10] && o[8] == q[11], "rsvd_plan hand case");
+    }
+    int64_t loc[15], shd[15];
+    for (int route = 0; route < 2; ++route) {
+      pl_cross_plan(300, 512, 1300, 1536, 900, 1024, 1300, 900, 0, 1, route, route, 5 << 20, 3 << 20, 6, 10, -1, 0, loc);
+      pl_cross_plan(300, 512, 1300, 1536, 900, 1024, 1300, 900, 1, 1, route, route, 5 << 20, 3 << 20, 6, 10, -1, 0, shd);
+      expect(loc[0] == RSVD_PLAN_OK && loc[13] == route && loc[9] == 1300 && loc[12] == 1024 && shd[14] >= loc[14] && loc[14] > 0, "cross_plan");
+    }
+    expect(pl_null_repair_bytes(1536, 32) > 1536 * 32 * 4 && pl_rinv_blocked_bytes(100) > 0 && pl_rsvd_scratch_bytes(1536, 512, 16, 6) > (4 << 20),
+           "real drivers' sizes");
+    expect(pl_fused_fit_eligible(2, EOFX_PREC_F16X3, 1, 120, 132, 6, 10, 120, 0) == 1 && pl_fused_fit_eligible(2, EOFX_PREC_F16X3, 1, 120, 132, 6, 10, 119, 0) == 0,
+           "fused_fit_eligible");
   }
   // the sketch generator at eight threads (twice: the second call reuses the pool and the buffers) and at one
   {

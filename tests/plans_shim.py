@@ -27,6 +27,10 @@ SIGNATURES = {
     "pl_apply_plan": (None, [I64, I64, I64, I64, I, I, I, I, P]), "pl_viewcov_plan": (I, [I64, I, P, I, I, P, P, I, P]),
     "pl_lagcov_plan": (I, [I64, I, P, I, P, P]), "pl_lowpass_plan": (I, [I64, I, P, I, P, P]),
     "pl_c64_plan": (None, [I64, I64, I64, I64, I64, I, I64, I, I, I, I, P]), "pl_c64_mul_scratch_bytes": (I64, [I64, I64, I64, I64, I]),
+    "pl_null_repair_bytes": (I64, [I64, I]), "pl_rinv_blocked_bytes": (I64, [I]), "pl_rsvd_scratch_bytes": (I64, [I64, I64, I, I]),
+    "pl_rsvd_plan": (None, [I64, I64, I, I, I, P]),
+    "pl_cross_plan": (None, [I64, I64, I64, I64, I64, I64, I64, I64, I, I, I, I, I64, I64, I, I, I, I, P]),
+    "pl_fused_fit_eligible": (I, [I, I, I, I64, I64, I, I, I64, I]),
     "sk_gaussian_f32": (None, [U32, I64, I64, P]), "sk_candidates": (I64, [I64]),
     "hh_kappa": (D, [I64, I64]), "hh_fft": (None, [P, I64]), "hh_length": (I64, [I64, P]), "hh_position_frequency": (I64, [I, I64]),
     "hh_fused_table": (None, [I64, I64, I, P]), "hh_circular_kernel": (None, [I64, I64, I64, P]),

@@ -385,3 +385,204 @@ def test_c64_plan_on_a_sweep(lib):
         assert pl["arena_bytes"] == need, (n, p, k, over, n_iter)
         assert lib.pl_c64_mul_scratch_bytes(n, p, n_pad, p_pad, LP) == 4 * big * LP * 4 + (8 << 20) + passes
     assert accepted >= 1500
+
+
+# --------------------------------------------------------------------------- #
+# 4. the plans of the real drivers (rsvd_plan, cross_plan)                      #
+# --------------------------------------------------------------------------- #
+RSVD_FIELDS = ("status", "r", "l_req", "l", "L", "Lo", "n_iter", "transposed", "full_width")
+CROSS_FIELDS = RSVD_FIELDS + ("tall", "small", "tall_pad", "small_pad", "gram_route", "arena_bytes")
+RSVD_OK, RSVD_RANK, RSVD_WIDTH = range(3)       # the order the entries report the checks in
+MAX_SKETCH = 256                                # EOFX_MAX_SKETCH (include/eofx.h)
+
+
+def c_rsvd(lib, rows, cols, k, n_oversamples=10, n_iter=-1):
+    out = np.zeros(len(RSVD_FIELDS), np.int64)
+    lib.pl_rsvd_plan(rows, cols, k, n_oversamples, n_iter, out.ctypes.data)
+    return dict(zip(RSVD_FIELDS, out.tolist()))
+
+
+def c_cross(lib, n, p1, p2, k, n_oversamples=10, n_iter=-1, P1=None, P2=None, sharded=False, want_tsc=True, fast=(True, True),
+            fast_scratch=(0, 0), no_gram=False):
+    out = np.zeros(len(CROSS_FIELDS), np.int64)
+    lib.pl_cross_plan(n, routes._up(n, 512), p1, routes._up(p1, 512), p2, routes._up(p2, 512), p1 if P1 is None else P1,
+                      p2 if P2 is None else P2, int(sharded), int(want_tsc), int(fast[0]), int(fast[1]), fast_scratch[0], fast_scratch[1], k,
+                      n_oversamples, n_iter, int(no_gram), out.ctypes.data)
+    return dict(zip(CROSS_FIELDS, out.tolist()))
+
+
+def null_repair(lib, rows_pad, Lo):
+    """fix_null_columns' reservation as the drivers spelled it before null_repair_bytes"""
+    return rows_pad * Lo * 4 + (lib.pl_gram_parts(rows_pad, Lo) + 4) * Lo * Lo * 8 + (64 << 10)
+
+
+def rsvd_scratch(lib, tall_pad, small_pad, l, k):
+    """rsvd_scratch_bytes as eofx_abi.hip spelled it before it moved into the header"""
+    up, atb = routes._up, lib.pl_atb_scratch_bytes
+    L, Lo, big = up(l, 32), up(k, 32), max(tall_pad, small_pad)
+    b = 2 * small_pad * L * 4 + 2 * tall_pad * L * 4 + tall_pad * Lo * 4 + small_pad * Lo * 4
+    b += atb(small_pad, tall_pad, L) + atb(tall_pad, small_pad, L) + atb(small_pad, tall_pad, Lo)
+    b += (4 * lib.pl_gram_parts(big, L) + 8) * L * L * 8 + 2 * L * Lo * 8 + 4096 + big * (Lo + L) * 4
+    if l > 64:
+        Lb = up(l, 64)
+        b += (2 * Lb * Lb + Lb * Lb // 2 + 64 * 64 + Lb) * 8 + 8192
+    return b + (4 << 20)
+
+
+def cross_arena(lib, n_pad, p1_pad, p2_pad, l, k, sharded, want_tsc, fast, fast_scratch, gram_route):
+    """The arena of crosscov_impl as the driver sized it inline before cross_plan."""
+    atb = lib.pl_atb_scratch_bytes
+    L, pp = routes._up(l, 32), max(p1_pad, p2_pad)
+    need = rsvd_scratch(lib, pp, pp, l, k) + n_pad * L * 4 * 2 + atb(n_pad, pp, L)
+    if want_tsc:
+        need += n_pad * n_pad * 4 * 2 + (1 << 20)
+    need_gram = max(fast_scratch) + n_pad * L * 4 * 2 + atb(n_pad, n_pad, L) if all(fast) else 0
+    need_plain = atb(n_pad, pp, n_pad) if want_tsc else 0
+    if sharded:
+        return need + null_repair(lib, pp, routes._up(k, 32)) + max(need_gram, need_plain)
+    return need + (need_gram if gram_route else need_plain)
+
+
+def test_rsvd_plan_hand_cases(lib):
+    """r = min(rows, cols), l = min(k + oversamples, r), panels of round_up(l, 32) and round_up(k, 32) columns, scikit-learn's
+    count 7 below k = 0.1 r and 4 from there, the transpose when there are fewer rows than columns."""
+    assert c_rsvd(lib, 700, 60, 5) == dict(status=RSVD_OK, r=60, l_req=15, l=15, L=32, Lo=32, n_iter=7, transposed=0, full_width=0)
+    assert c_rsvd(lib, 60, 700, 5) == dict(status=RSVD_OK, r=60, l_req=15, l=15, L=32, Lo=32, n_iter=7, transposed=1, full_width=0)
+    # the sketch is cut to the rank and is then full width: l = r = 12
+    assert c_rsvd(lib, 60, 12, 4) == dict(status=RSVD_OK, r=12, l_req=14, l=12, L=32, Lo=32, n_iter=4, transposed=0, full_width=1)
+    assert _has(c_rsvd(lib, 60, 12, 2, n_oversamples=10), status=RSVD_OK, l_req=12, l=12, full_width=1)       # exactly the rank, unclamped
+    assert _has(c_rsvd(lib, 60, 12, 1, n_oversamples=10), status=RSVD_OK, l=11, full_width=0)
+    # more modes than rank; the rank is reported first
+    assert _has(c_rsvd(lib, 60, 12, 13), status=RSVD_RANK, r=12)
+    assert _has(c_rsvd(lib, 60, 12, 12), status=RSVD_OK, r=12, l=12)
+    assert _has(c_rsvd(lib, 200, 300, 400, n_oversamples=0), status=RSVD_RANK, r=200)
+    # the widest sketch
+    assert _has(c_rsvd(lib, 900, 400, 246), status=RSVD_OK, l=256, L=256, Lo=256)
+    assert _has(c_rsvd(lib, 900, 400, 247), status=RSVD_WIDTH, l=257)
+    assert _has(c_rsvd(lib, 900, 256, 250), status=RSVD_OK, l=256, full_width=1)
+    # an explicit count, zero included
+    assert c_rsvd(lib, 700, 60, 5, n_iter=3)["n_iter"] == 3 and c_rsvd(lib, 700, 60, 5, n_iter=0)["n_iter"] == 0
+    # the automatic count on both sides of k = 0.1 r (r = 60: k = 5 < 6 <= k = 6; r = 55: k = 5 < 5.5 < k = 6)
+    assert [c_rsvd(lib, 700, 60, k)["n_iter"] for k in (5, 6, 7)] == [7, 4, 4]
+    assert [c_rsvd(lib, 55, 700, k)["n_iter"] for k in (5, 6)] == [7, 4]
+    # the sharded fit: (n, features over all ranks), so the sample count bounds the sketch
+    assert _has(c_rsvd(lib, 120, 100000, 115), status=RSVD_OK, r=120, l_req=125, l=120, transposed=1, full_width=1, n_iter=4)
+
+
+def test_rsvd_plan_on_a_sweep(lib):
+    """l <= r; a clamped sketch is a full-width one (so eofx_rsvd_f32 needs no copy of the leading columns of omega: the identity
+    replaces it); whole panels of 32 columns; and the two Python restatements of the rules (sharded.rsvd_auto_iters, the width
+    sharded._resolve_sketch takes) agree with the header."""
+    from xeofs_amd import sharded
+
+    rng = np.random.default_rng(2275)
+    seen = dict(clamped=0, full=0, rank=0, width=0)
+    for _ in range(2500):
+        rows, cols = (int(x) for x in rng.integers(1, 3000, 2))
+        if rng.integers(0, 3) == 0:                 # small matrices: clamped sketches are common there
+            rows, cols = (int(x) for x in rng.integers(1, 80, 2))
+        k, over, n_iter = int(rng.integers(1, 300)), int(rng.integers(0, 12)), int(rng.integers(-1, 9))
+        if rng.integers(0, 2):
+            k = int(rng.integers(1, 40))
+        pl = c_rsvd(lib, rows, cols, k, over, n_iter)
+        r = min(rows, cols)
+        want = RSVD_RANK if k > r else RSVD_WIDTH if min(k + over, r) > MAX_SKETCH else RSVD_OK
+        assert pl["status"] == want and pl["r"] == r and pl["l_req"] == k + over, (rows, cols, k, over, n_iter)
+        seen["rank"] += want == RSVD_RANK
+        seen["width"] += want == RSVD_WIDTH
+        assert pl["l"] <= r
+        assert pl["l"] == pl["l_req"] or pl["full_width"], (rows, cols, k, over)
+        assert pl["full_width"] == (pl["l"] == r) and pl["transposed"] == (rows < cols)
+        assert pl["L"] % 32 == 0 and pl["L"] >= pl["l"] and pl["L"] - pl["l"] < 32 and pl["Lo"] == routes._up(k, 32)
+        assert pl["n_iter"] == (sharded.rsvd_auto_iters(k, rows, cols) if n_iter < 0 else n_iter)
+        seen["clamped"] += pl["l"] != pl["l_req"]
+        seen["full"] += pl["full_width"]
+        if want != RSVD_RANK:
+            omega, l = sharded._resolve_sketch(k, r, over, np.zeros((r, k + over), np.float32), None)
+            assert l == pl["l"] and omega.shape == (r, l)
+    assert min(seen.values()) >= 50, seen
+
+
+def test_null_repair_and_scratch_bytes(lib):
+    rng = np.random.default_rng(2192)
+    for _ in range(2000):
+        rows_pad, Lo = 512 * int(rng.integers(1, 600)), 32 * int(rng.integers(1, 9))
+        assert lib.pl_null_repair_bytes(rows_pad, Lo) == null_repair(lib, rows_pad, Lo)
+    for _ in range(500):
+        tp, sp = (512 * int(x) for x in rng.integers(1, 300, 2))
+        l, k = int(rng.integers(1, 257)), int(rng.integers(1, 200))
+        assert lib.pl_rsvd_scratch_bytes(tp, sp, l, k) == rsvd_scratch(lib, tp, sp, l, k), (tp, sp, l, k)
+
+
+def test_cross_plan_hand_cases(lib):
+    """300 samples pad to 512; 1300 and 900 features to 1536 and 1024.  The operator is C = X^T Y (p1 x p2), transposed when
+    p1 < p2; the Gram route is this rank's wish when the total squared covariance is asked for, both fields are wider than long,
+    both pass gram_fast_ok and the switch is off."""
+    fs = (5 << 20, 3 << 20)
+    pl = c_cross(lib, 300, 1300, 900, 6, fast_scratch=fs)
+    assert _has(pl, status=RSVD_OK, r=900, l=16, L=32, Lo=32, n_iter=7, transposed=0, tall=1300, small=900, tall_pad=1536, small_pad=1024,
+                gram_route=1)
+    assert pl["arena_bytes"] == cross_arena(lib, 512, 1536, 1024, 16, 6, False, True, (True, True), fs, True)
+    pl = c_cross(lib, 300, 900, 1300, 6, fast_scratch=fs)
+    assert _has(pl, transposed=1, tall=1300, small=900, tall_pad=1536, small_pad=1024, gram_route=1)
+    # every reason against the route
+    assert c_cross(lib, 300, 1300, 900, 6, fast_scratch=fs, want_tsc=False)["gram_route"] == 0
+    assert c_cross(lib, 300, 1300, 900, 6, fast_scratch=fs, no_gram=True)["gram_route"] == 0
+    assert c_cross(lib, 300, 1300, 900, 6, fast=(True, False))["gram_route"] == 0
+    assert c_cross(lib, 300, 1300, 900, 6, fast=(False, True))["gram_route"] == 0
+    assert c_cross(lib, 300, 1300, 300, 6, fast_scratch=fs)["gram_route"] == 0 and c_cross(lib, 300, 1300, 301, 6, fast_scratch=fs)["gram_route"] == 1
+    assert c_cross(lib, 300, 300, 1300, 6, fast_scratch=fs)["gram_route"] == 0
+    assert c_cross(lib, 700, 50, 40, 6, fast_scratch=fs)["gram_route"] == 0
+    # the valid (or global) counts rule: a masked first field with fewer valid features than the second turns the operator round
+    assert _has(c_cross(lib, 300, 1300, 900, 6, P1=800), r=800, transposed=1, tall=900, small=1300, tall_pad=1024, small_pad=1536)
+    assert _has(c_cross(lib, 300, 1300, 900, 6, P1=250), r=250, gram_route=0)
+    # the checks, and the full-width sketch the driver answers with the identity
+    assert _has(c_cross(lib, 80, 50, 40, 41), status=RSVD_RANK, r=40, arena_bytes=0)
+    assert _has(c_cross(lib, 700, 400, 300, 250), status=RSVD_WIDTH, l=260, arena_bytes=0)
+    assert _has(c_cross(lib, 80, 50, 40, 30), status=RSVD_OK, l=40, l_req=40, full_width=1)
+    assert _has(c_cross(lib, 80, 50, 40, 31), status=RSVD_OK, l=40, l_req=41)       # the driver refuses a clamped sketch itself
+
+
+def test_cross_plan_on_a_sweep(lib):
+    """The reservation equals the formula the driver carried inline, the sharded one holds either route, and the Gram route is never
+    wished for without the total squared covariance or with a field that is not wider than long."""
+    rng = np.random.default_rng(3501)
+    accepted = 0
+    for _ in range(1500):
+        n, p1, p2 = int(rng.integers(2, 3000)), int(rng.integers(1, 6000)), int(rng.integers(1, 6000))
+        P1, P2 = (p if rng.integers(0, 3) else int(rng.integers(1, p + 1)) for p in (p1, p2))
+        k, over, n_iter = int(rng.integers(1, 70)), int(rng.integers(0, 12)), int(rng.integers(-1, 9))
+        fast = (bool(rng.integers(0, 4)), bool(rng.integers(0, 4)))
+        fs = tuple(int(rng.integers(1, 1 << 28)) if all(fast) else 0 for _ in range(2))
+        want_tsc, no_gram = bool(rng.integers(0, 3)), not rng.integers(0, 5)
+        kw = dict(n_oversamples=over, n_iter=n_iter, P1=P1, P2=P2, want_tsc=want_tsc, fast=fast, fast_scratch=fs, no_gram=no_gram)
+        loc, shd = c_cross(lib, n, p1, p2, k, sharded=False, **kw), c_cross(lib, n, p1, p2, k, sharded=True, **kw)
+        assert {key: loc[key] for key in RSVD_FIELDS} == c_rsvd(lib, P1, P2, k, over, n_iter)
+        assert loc["gram_route"] == shd["gram_route"] == int(want_tsc and n < P1 and n < P2 and all(fast) and not no_gram)
+        if not want_tsc or n >= P1 or n >= P2:
+            assert loc["gram_route"] == 0
+        if loc["status"] != RSVD_OK:
+            assert loc["arena_bytes"] == shd["arena_bytes"] == 0
+            continue
+        accepted += 1
+        n_pad, pads = routes._up(n, 512), (routes._up(p1, 512), routes._up(p2, 512))
+        assert (loc["tall_pad"], loc["small_pad"]) == (pads[::-1] if loc["transposed"] else pads)
+        for pl, sharded in ((loc, False), (shd, True)):
+            assert pl["arena_bytes"] == cross_arena(lib, n_pad, *pads, pl["l"], k, sharded, want_tsc, fast, fs, bool(pl["gram_route"]))
+        # whichever route the vote of a sharded fit ends on, its arena holds what a local fit on that route reserves
+        for route in (False, True):
+            if route and not all(fast):
+                continue
+            assert shd["arena_bytes"] >= cross_arena(lib, n_pad, *pads, loc["l"], k, False, want_tsc, fast, fs, route)
+    assert accepted >= 700
+
+
+def test_fused_fit_eligible(lib):
+    """fit_first_eligible plus: no more modes than samples, an unclamped sketch, a row of omega per sample, omega on the host."""
+    ok = lambda **kw: lib.pl_fused_fit_eligible(*[{**dict(keep_raw=2, prec=PREC_F16X3, aligned=1, n=120, P=132, k=6, over=10, rows=120, dev=0),
+                                                   **kw}[key] for key in ("keep_raw", "prec", "aligned", "n", "P", "k", "over", "rows", "dev")])
+    assert ok() == 1 and ok(rows=500) == 1
+    assert ok(rows=119) == 0 and ok(dev=1) == 0 and ok(keep_raw=1) == 0 and ok(aligned=0) == 0
+    assert ok(over=26) == 0                 # l = 32: no spare column for the ones (fit_first_eligible)
+    assert ok(k=115, over=10) == 0          # clamped to the 120 samples
+    assert lib.pl_fit_first_eligible(2, PREC_F16X3, 1, 120, 132, 16) == 1

@@ -4,7 +4,8 @@ compare two builds of libeofx.so bit for bit where the host algebra between the 
 `--compare3 A1.npz A2.npz B.npz`: what differs between two runs of the SAME build is listed and held to the tolerance of its
 existing test instead (TOLERANCE), everything else must be equal between A1 and B).  The sibling of cross_surface_dump.py one level down: engine.rsvd tall / wide / with a sketch
 beyond 64 columns on either route of the Cholesky inverse / with more modes than rank / on a peaked spectrum over a tall panel
-above 16 MiB, engine.crosscov_rsvd with more modes than rank, engine.rsvd_c64 at the edge cases of
+above 16 MiB, engine.crosscov_rsvd with more modes than rank, the branches of the real drivers those cases do not reach (`real_branches`),
+engine.rsvd_c64 at the edge cases of
 tests/test_gpu_complex.py with and without the block-Krylov recurrence and on the branches those do not reach (`c64_branches`),
 engine.rsvd_hilbert_c64 under both rules, and the two host eigen-solvers.  With EOFX_C64_TRACE set, stderr holds the complex
 driver's trace, one `# key` line after the lines of each case: two builds that take the same branches print the same text
@@ -54,6 +55,136 @@ def low_rank(rng, n, p, rank, decay, noise, cplx=False):
     if noise:
         X = X + noise * g(n, p) / np.sqrt(p)
     return X
+
+
+def with_env(name, value, fn):
+    old = os.environ.pop(name, None)
+    if value is not None:
+        os.environ[name] = value
+    try:
+        return fn()
+    finally:
+        os.environ.pop(name, None)
+        if old is not None:
+            os.environ[name] = old
+
+
+def real_branches(record):
+    """The branches of the real drivers: engine.fit fused / falling back before and after the first pass / ineligible / masked in
+    place / with more modes than the field has rank / refused by the two-step path (the message is recorded), engine.fit_first
+    fused and falling back, engine.rsvd with a full-width sketch, engine.crosscov_rsvd on the Gram route in both orientations,
+    with the route switched off, without the total squared covariance, with n above both widths, with the identity sketch, a
+    SketchFuture and no sign rule, and engine.fit_sharded / engine.crosscov_rsvd_sharded over a one-rank RCCL communicator."""
+    from xeofs_amd import engine
+
+    ctx = engine.default_context()
+
+    def field(n, p, seed, rank=9, noise=0.3):
+        return (low_rank(np.random.default_rng(seed), n, p, rank, 0.7, noise) + 2.0).astype(np.float32)
+
+    def fitted(key, res, fused=None):
+        mat, st, U, s, V = res
+        assert fused is None or bool(st["fused"]) == fused, (key, engine.fit_info(ctx))
+        record(key, [U, s, V])
+        record(key + ".stats", st)
+        out[key] = engine.fit_info(ctx)["reason"]
+        mat.free()
+
+    def refused(key, fn):
+        try:
+            fn()
+        except Exception as e:
+            record(key, [np.frombuffer(f"{type(e).__name__}: {e}".encode(), np.uint8)])
+        else:
+            raise AssertionError(f"{key}: no error")
+
+    def rccl1(fn):
+        engine.comm_init_rccl(ctx, engine.comm_unique_id(), 1, 0)
+        try:
+            return fn()
+        finally:
+            engine.comm_clear(ctx)
+
+    out = {}
+    n, P, k = 300, 2048, 6
+    X = field(n, P, 1)
+    nan_feature, outlier, masked, rank4 = X.copy(), X.copy(), X.copy(), field(n, P, 2, rank=4, noise=0.0)
+    nan_feature[:, 900] = np.nan                    # seen by the probe of the sampled rows: back to the two-step path before the pass
+    outlier[200, 77] = 3.0e7                        # not in a sampled row: the provisional fp16 range overflows during the pass
+    masked[:, np.random.default_rng(5).random(P) < 0.25] = np.nan
+    # --- engine.fit
+    fitted("fit.fused", engine.fit(ctx, X, k, random_state=4), fused=True)
+    fitted("fit.fallback_nan_feature", engine.fit(ctx, nan_feature, k, random_state=4), fused=False)
+    fitted("fit.fallback_outlier", engine.fit(ctx, outlier, k, random_state=4), fused=False)
+    fitted("fit.ineligible_l32", engine.fit(ctx, X, 22, random_state=4), fused=False)
+    fitted("fit.masked", engine.fit(ctx, masked, k, random_state=4, allow_masked=True), fused=True)
+    fitted("fit.null_modes", engine.fit(ctx, rank4, 9, random_state=4))
+    fitted("fit.no_flip", engine.fit(ctx, X, k, random_state=4, flip=False), fused=True)
+    # (more modes than a 40 x 2048 field has rank: the two-step path's decomposition refuses, the matrix goes, the message stays)
+    refused("fit.more_modes_than_rank", lambda: engine.fit(ctx, X[:40], 50, random_state=4))
+    # --- engine.fit_first
+    for tag, F, fused in (("fused", X, True), ("fallback", nan_feature, False)):
+        Z = engine.panel_import(ctx, engine.sketch_matrix(n, k + 10, 4), (n + 511) // 512 * 512, 32)
+        mat, st, Yp = engine.fit_first(ctx, F, Z, k + 10)
+        assert bool(st["fused"]) == fused, (tag, engine.fit_info(ctx))
+        record(f"fit_first.{tag}", [Yp.cpu().numpy()])
+        record(f"fit_first.{tag}.stats", st)
+        mat.free()
+    # --- engine.rsvd, a sketch cut to the rank: 60 x 12, k = 4, l = r = 12 (the identity)
+    mat = engine.from_dense(ctx, field(60, 12, 3, rank=12))
+    record("rsvd.full_width", engine.rsvd(ctx, mat, 4, random_state=5))
+    mat.free()
+    # --- engine.crosscov_rsvd
+    def pair(n, p1, p2, seed, in_place=True, nan1=None):
+        rng = np.random.default_rng(seed)
+        t = rng.standard_normal((n, 8)) * (5.0 * 0.8 ** np.arange(8))
+        A = (t @ rng.standard_normal((8, p1)) + rng.standard_normal((n, p1))).astype(np.float32)
+        B = (t @ rng.standard_normal((8, p2)) + rng.standard_normal((n, p2))).astype(np.float32)
+        if nan1 is not None:
+            A[:, rng.random(p1) < nan1] = np.nan
+        return (engine.preprocess(ctx, A, in_place=in_place, allow_masked=nan1 is not None)[0], engine.preprocess(ctx, B, in_place=in_place)[0])
+
+    for p1, p2 in ((1300, 900), (900, 1300)):
+        mx, my = pair(300, p1, p2, 6)
+        tag = f"crosscov_rsvd.wide_{p1}_{p2}"
+        gram = engine.crosscov_rsvd(ctx, mx, my, k, random_state=7)
+        record(tag + ".gram", gram)
+        plain = with_env("EOFX_CROSS_NO_GRAM", "1", lambda: engine.crosscov_rsvd(ctx, mx, my, k, random_state=7))
+        record(tag + ".no_gram", plain)
+        out[tag + ".routes_differ"] = int(not np.array_equal(gram["Q1"], plain["Q1"]))
+        record(tag + ".no_tsc", engine.crosscov_rsvd(ctx, mx, my, k, random_state=7, want_tsc=False))
+        if p1 > p2:
+            small = min(mx.p, my.p)
+            record(tag + ".future", engine.crosscov_rsvd(ctx, mx, my, k, omega=engine.SketchFuture(small, k + 10, 7)))
+            record(tag + ".no_flip", engine.crosscov_rsvd(ctx, mx, my, k, random_state=7, flip=False))
+        mx.free()
+        my.free()
+    mx, my = pair(700, 50, 40, 8, in_place=False)
+    record("crosscov_rsvd.tall", engine.crosscov_rsvd(ctx, mx, my, k, random_state=7))
+    record("crosscov_rsvd.identity", engine.crosscov_rsvd(ctx, mx, my, 30, random_state=7))       # k + 10 = min(p1, p2)
+    mx.free()
+    my.free()
+    # --- one rank over RCCL
+    fitted("fit_sharded.plain", rccl1(lambda: engine.fit_sharded(ctx, X, k, P, random_state=4)))
+    fitted("fit_sharded.masked", rccl1(lambda: engine.fit_sharded(ctx, masked, k, P, random_state=4, allow_masked=True)))
+    fitted("fit_sharded.null_modes", rccl1(lambda: engine.fit_sharded(ctx, rank4, 9, P, random_state=4)))
+    fitted("fit_sharded.no_flip", rccl1(lambda: engine.fit_sharded(ctx, X, k, P, random_state=4, flip=False)))
+    mx, my = pair(300, 1300, 900, 6, nan1=0.25)
+    assert mx.masked and not my.masked
+    for flip in (True, False):
+        record(f"crosscov_rsvd_sharded.masked.flip{int(flip)}",
+               rccl1(lambda: engine.crosscov_rsvd_sharded(ctx, mx, my, k, mx.p, 0, my.p, 0, random_state=7, flip=flip)))
+    record("crosscov_rsvd_sharded.no_tsc", rccl1(lambda: engine.crosscov_rsvd_sharded(ctx, mx, my, k, mx.p, 0, my.p, 0, random_state=7, want_tsc=False)))
+    mx.free()
+    my.free()
+    T = np.random.default_rng(9).standard_normal((80, 3))       # more modes than rank: both sharded factors are repaired
+    mx = engine.from_dense(ctx, (T @ np.random.default_rng(10).standard_normal((3, 50))).astype(np.float32))
+    my = engine.from_dense(ctx, (T @ np.random.default_rng(11).standard_normal((3, 40))).astype(np.float32))
+    record("crosscov_rsvd_sharded.null_modes", rccl1(lambda: engine.crosscov_rsvd_sharded(ctx, mx, my, 6, 50, 0, 40, 0, random_state=5)))
+    mx.free()
+    my.free()
+    record("real_branches.reasons", [np.asarray([out[key] for key in sorted(out)])])
+    print("native_driver_dump: real_branches: " + ", ".join(f"{key} = {out[key]}" for key in sorted(out)))
 
 
 def c64_branches(record):
@@ -149,17 +280,6 @@ def main(out_path):
         if iters:
             out[f"{key}.iterations"] = np.asarray(engine.last_iterations(ctx))
 
-    def with_env(name, value, fn):
-        old = os.environ.pop(name, None)
-        if value is not None:
-            os.environ[name] = value
-        try:
-            return fn()
-        finally:
-            os.environ.pop(name, None)
-            if old is not None:
-                os.environ[name] = old
-
     rng = np.random.default_rng(2024)
     # --- engine.rsvd
     for tag, n, p, k, kw, field in (
@@ -181,6 +301,7 @@ def main(out_path):
     record("crosscov_rsvd.null_modes", engine.crosscov_rsvd(ctx, xm, ym, 6, random_state=5))
     xm.free()
     ym.free()
+    real_branches(record)
     # --- engine.rsvd_c64: the cases of tests/test_gpu_complex.py::test_complex_rsvd_krylov_edge_cases
     for case in ("wide_sketch", "full_width", "rank_deficient", "n_iter_1", "n_iter_2", "converge", "feature_side"):
         crng = np.random.default_rng(11)

@@ -889,7 +889,6 @@ static int launch_xgram(eofx_ctx* ctx, const float* Pa, int64_t lda, int La, con
 
 // out = P R^-1 with G = R^T R (leading l x l block)
 static int launch_rinv(eofx_ctx* ctx, const double* G, int L, int l, double* Rinv);
-static size_t rinv_blocked_bytes(int l);
 static size_t matmul_nt_scratch(eofx_ctx* ctx, int64_t rows, int L, int Lo);
 static int launch_matmul_nt(eofx_ctx* ctx, const float* P, int64_t rows, int L, const double* Mx, int Lo, float* out);
 static int launch_cholqr(eofx_ctx* ctx, const float* P, int64_t rows, int L, int l, const double* G,
@@ -1880,11 +1879,7 @@ extern "C" int eofx_peaked_spectrum(const double* G, int ld, int l) {
 // (the PCA pre-reduction's int(0.3 rank) + 10 columns: l = 1510): 64-column blocks, the diagonal blocks through
 // chol_rinv_kernel (same pivots, same dependency rule against the ORIGINAL diagonal), row panels / trailing updates /
 // the inverse's block columns through dgemm64_kernel.  ~5 launches per block, everything in float64, fixed order.
-// Arena: 2 Lb^2 + Lb 64 + Lb doubles.
-static size_t rinv_blocked_bytes(int l) {
-  const size_t Lb = (size_t)round_up(l, 64);
-  return (2 * Lb * Lb + Lb * Lb / 2 + 64 * 64 + Lb) * sizeof(double) + 8192;
-}
+// Arena: rinv_blocked_bytes (eofx_plans.hpp).
 static int launch_rinv_blocked(eofx_ctx* ctx, const double* G, int L, int l, double* Rinv) {
   const int Lb = (int)round_up(l, 64), nb = Lb / 64;
   ArenaScope scope(ctx);
@@ -2132,24 +2127,10 @@ static int rsvd_core(eofx_ctx* ctx, const LinOp& op, int k, int l, int n_iter, c
   return EOFX_OK;
 }
 
-static size_t rsvd_scratch_bytes(int64_t tall_pad, int64_t small_pad, int l, int k) {
-  const size_t L = (size_t)round_up(l, 32), Lo = (size_t)round_up(k, 32);
-  size_t b = 0;
-  b += 2 * small_pad * L * 4 + 2 * tall_pad * L * 4 + tall_pad * Lo * 4 + small_pad * Lo * 4;
-  b += atb_scratch_bytes(small_pad, tall_pad, (int)L);        // split-K partials (small side)
-  b += atb_scratch_bytes(tall_pad, small_pad, (int)L);        // split-K partials (tall side)
-  b += atb_scratch_bytes(small_pad, tall_pad, (int)Lo);
-  b += (size_t)(4 * gram_parts(std::max(tall_pad, small_pad), (int)L) + 8) * L * L * 8 + 2 * L * Lo * 8 + 4096;  // gram partials, Rinv, G0, R2, M1, M2
-  b += (size_t)std::max(tall_pad, small_pad) * (Lo + L) * 4;  // export / import staging
-  if (l > 64) b += rinv_blocked_bytes(l);                     // blocked device Cholesky of a wide sketch
-  b += 4 << 20;
-  return b;
-}
-
 // xeofs sign rule (xarray_utils.py:273-301) from the per-mode max/min of VT
 static int comm_allreduce(eofx_ctx* ctx, void* buf, int64_t count, int dtype, int op);
 // over_ranks: the rows of Vpanel are this rank's slice of the feature axis -- one all-reduce(max) of [max | -min] over the
-// communicator of the context makes the extrema (and so the signs) global
+// communicator of the context makes the extrema (and so the signs) global; the host compares magnitudes, so -min stays negated
 static int sign_rule(eofx_ctx* ctx, const float* Vpanel, int64_t rows, int Lo, int k,
                      std::vector<double>& sign, bool over_ranks = false) {
   ArenaScope scope(ctx);
@@ -2160,8 +2141,6 @@ static int sign_rule(eofx_ctx* ctx, const float* Vpanel, int64_t rows, int Lo, i
     hipLaunchKernelGGL(negate_kernel, dim3(1), dim3(256), 0, ctx->stream, mn, Lo);
     KCHK();
     CHK(comm_allreduce(ctx, mx, 2 * (int64_t)Lo, 0, 1));
-    hipLaunchKernelGGL(negate_kernel, dim3(1), dim3(256), 0, ctx->stream, mn, Lo);
-    KCHK();
   }
   std::vector<float> hmx(Lo), hmn(Lo);
   HIPCHK(hipMemcpyAsync(hmx.data(), mx, sizeof(float) * Lo, hipMemcpyDeviceToHost, ctx->stream));
@@ -2189,8 +2168,7 @@ static int fix_null_columns(eofx_ctx* ctx, float* P, int64_t rows, int64_t rows_
   if (rows_total < 0) rows_total = rows;
   if (first >= k || rows_total <= first) return EOFX_OK;
   if (!reduce) {   // (the repair never turns a working call into an out-of-memory error: without room in the arena the columns stay)
-    const size_t need = (size_t)rows_pad * Lo * 4 + (size_t)(gram_parts(rows_pad, Lo) + 4) * Lo * Lo * 8 + (64 << 10);
-    if (ctx->arena_size - ctx->arena_off < need) return EOFX_OK;
+    if (ctx->arena_size - ctx->arena_off < null_repair_bytes(rows_pad, Lo)) return EOFX_OK;
   }
   ArenaScope scope(ctx);
   ARENA(double, G, (size_t)Lo * Lo);
@@ -2250,40 +2228,58 @@ static int fix_null_modes(eofx_ctx* ctx, const RsvdOut& ro, int64_t tall, int64_
   return EOFX_OK;
 }
 
-static int rsvd_finish(eofx_ctx* ctx, const RsvdOut& ro, bool transposed, int64_t n, int64_t p, int k, int flip,
-                       float* U, float* s, float* V) {
-  CHK(fix_null_modes(ctx, ro, transposed ? p : n, transposed ? n : p, k));
-  const float* Vp = transposed ? ro.Tvec : ro.Svec;
-  const float* Up = transposed ? ro.Svec : ro.Tvec;
+// The end of every real decomposition: null modes, the sign rule, both factors and s / s_divisor to the caller.  The right factor
+// (V: the one the sign rule reads) is the tall panel when right_is_tall.  `shards`: factors whose rows are split over the ranks --
+// the hooks and global row counts of fix_null_modes, and a sign rule over all ranks.  *sign_out: the signs applied (flip only).
+struct FactorShards {
+  const GramReduce* reduce_tall = nullptr;
+  int64_t tall_total = -1;
+  const GramReduce* reduce_small = nullptr;
+  int64_t small_total = -1;
+};
+static int rsvd_finish(eofx_ctx* ctx, const RsvdOut& ro, bool right_is_tall, int64_t left_rows, int64_t right_rows, int k, int flip,
+                       float* left, float* s, float* right, double s_divisor = 1.0, const FactorShards* shards = nullptr,
+                       std::vector<double>* sign_out = nullptr) {
+  const int64_t tall = right_is_tall ? right_rows : left_rows, small = right_is_tall ? left_rows : right_rows;
+  const FactorShards local, &sh = shards ? *shards : local;
+  CHK(fix_null_modes(ctx, ro, tall, small, k, sh.reduce_tall, sh.tall_total, sh.reduce_small, sh.small_total));
+  const float* Rp = right_is_tall ? ro.Tvec : ro.Svec;
+  const float* Lp = right_is_tall ? ro.Svec : ro.Tvec;
   std::vector<double> sign;
-  if (flip) CHK(sign_rule(ctx, Vp, p, ro.Lo, k, sign));
-  CHK(export_panel(ctx, Up, n, ro.Lo, k, flip ? sign.data() : nullptr, U));
-  CHK(export_panel(ctx, Vp, p, ro.Lo, k, flip ? sign.data() : nullptr, V));
+  if (flip) CHK(sign_rule(ctx, Rp, right_rows, ro.Lo, k, sign, shards != nullptr));
+  CHK(export_panel(ctx, Lp, left_rows, ro.Lo, k, flip ? sign.data() : nullptr, left));
+  CHK(export_panel(ctx, Rp, right_rows, ro.Lo, k, flip ? sign.data() : nullptr, right));
   if (s) {
     std::vector<float> hs(k);
-    for (int j = 0; j < k; ++j) hs[j] = (float)ro.s[j];
+    for (int j = 0; j < k; ++j) hs[j] = (float)(ro.s[j] / s_divisor);      // (a division: the reciprocal rounds differently)
     HIPCHK(hipMemcpy(s, hs.data(), sizeof(float) * k, hipMemcpyDefault));
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (sign_out) sign_out->swap(sign);
   return EOFX_OK;
+}
+
+// A sketch as wide as the rank spans everything, so the identity is used instead of the Gaussian draw: a square Gaussian
+// matrix is occasionally ill conditioned (cond ~ 1e3..1e4) and a single pass would amplify its rounding error by that factor.
+static const float* identity_sketch(int64_t small, int l, std::vector<float>& eye) {
+  eye.assign((size_t)small * l, 0.f);
+  for (int64_t i = 0; i < l; ++i) eye[(size_t)i * l + i] = 1.f;
+  return eye.data();
 }
 
 extern "C" int eofx_rsvd_f32(eofx_ctx* ctx, const eofx_mat* m, int k, int n_oversamples, int n_iter,
                              const float* omega, int flip, float* U, float* s, float* V) {
   if (!ctx || !m || !omega || k <= 0 || n_oversamples < 0) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
   ENTER(ctx);
-  const int64_t n = m->n, p = m->p, r = std::min(n, p);
-  if (k > r)
+  const int64_t n = m->n, p = m->p;
+  const RsvdPlan pl = rsvd_plan(n, p, k, n_oversamples, n_iter);
+  if (pl.status == RSVD_PLAN_RANK)
     return set_err(ctx, EOFX_ERR_RANK,
-                   "n_modes must be less than or equal to the rank of the dataset (rank = %lld).", (long long)r);
-  const int l_req = k + n_oversamples;
-  const int l = (int)std::min<int64_t>(l_req, r);
-  if (l > EOFX_MAX_SKETCH)
-    return set_err(ctx, EOFX_ERR_ARG, "sketch width k+n_oversamples = %d > %d is not supported", l, EOFX_MAX_SKETCH);
-  if (n_iter < 0) n_iter = rsvd_auto_iters(k, n, p);
-  const bool transposed = n < p;  // sklearn: transpose = n_samples < n_features
+                   "n_modes must be less than or equal to the rank of the dataset (rank = %lld).", (long long)pl.r);
+  if (pl.status == RSVD_PLAN_WIDTH)
+    return set_err(ctx, EOFX_ERR_ARG, "sketch width k+n_oversamples = %d > %d is not supported", pl.l, EOFX_MAX_SKETCH);
   LinOp op;
-  if (transposed) {
+  if (pl.transposed) {
     op = {p, n, m->p_pad, m->n_pad,
           [&](const float* z, float* y, int L, int pr) { return panel_tmul(ctx, m, z, y, L, pr); },
           [&](const float* y, float* w, int L, int pr) { return panel_mul(ctx, m, y, w, L, pr); }};
@@ -2292,27 +2288,14 @@ extern "C" int eofx_rsvd_f32(eofx_ctx* ctx, const eofx_mat* m, int k, int n_over
           [&](const float* z, float* y, int L, int pr) { return panel_mul(ctx, m, z, y, L, pr); },
           [&](const float* y, float* w, int L, int pr) { return panel_tmul(ctx, m, y, w, L, pr); }};
   }
-  CHK(arena_reserve(ctx, rsvd_scratch_bytes(op.tall_pad, op.small_pad, l, k)));
+  CHK(arena_reserve(ctx, rsvd_scratch_bytes(op.tall_pad, op.small_pad, pl.l, k)));
   ArenaScope scope(ctx);
-  // omega arrives as (small x l_req).  A sketch as wide as the rank spans everything, so the identity
-  // is used instead of the Gaussian draw: a square Gaussian matrix is occasionally ill conditioned
-  // (cond ~ 1e3..1e4) and a single pass would amplify its rounding error by that factor.
-  std::vector<float> om_clamped;
-  const float* om = omega;
-  if (l == r) {
-    om_clamped.assign((size_t)op.small * l, 0.f);
-    for (int64_t i = 0; i < l; ++i) om_clamped[(size_t)i * l + i] = 1.f;
-    om = om_clamped.data();
-  } else if (l != l_req) {
-    if (is_device_ptr(omega)) return set_err(ctx, EOFX_ERR_ARG, "omega must be a host pointer");
-    om_clamped.resize((size_t)op.small * l);
-    for (int64_t i = 0; i < op.small; ++i)
-      for (int j = 0; j < l; ++j) om_clamped[(size_t)i * l + j] = omega[(size_t)i * l_req + j];
-    om = om_clamped.data();
-  }
+  // omega arrives as (small x l_req); a sketch clamped to the rank is full width, so its columns are never read
+  std::vector<float> eye;
+  const float* om = pl.full_width ? identity_sketch(op.small, pl.l, eye) : omega;
   RsvdOut ro;
-  CHK(rsvd_core(ctx, op, k, l, n_iter, om, ro));
-  return rsvd_finish(ctx, ro, transposed, n, p, k, flip, U, s, V);
+  CHK(rsvd_core(ctx, op, k, pl.l, pl.n_iter, om, ro));
+  return rsvd_finish(ctx, ro, pl.transposed, n, p, k, flip, U, s, V);
 }
 
 // ------------------------------------------------------------------------------------
@@ -2548,6 +2531,10 @@ struct FitFirst {
 static bool fit_first_eligible(const eofx_ctx* ctx, const float* Xdev, int64_t n, int64_t P, int l) {
   return fit_first_eligible(ctx->keep_raw, ctx->prec_power, ((uintptr_t)Xdev % 16) == 0, n, P, l);
 }
+static bool fused_fit_eligible(const eofx_ctx* ctx, const float* Xdev, int64_t n, int64_t P, int k, const RsvdPlan& sk, int64_t omega_rows,
+                               const float* omega) {
+  return fused_fit_eligible(ctx->keep_raw, ctx->prec_power, ((uintptr_t)Xdev % 16) == 0, n, P, k, sk, omega_rows, is_device_ptr(omega));
+}
 
 // ------------------------------------------------------------------------------------
 // The fused fit: Scaler.fit + Sanitizer + Decomposer.fit with the column statistics taken during the FIRST pass of
@@ -2577,6 +2564,53 @@ static int fit_fused(eofx_ctx* ctx, const float* Xd, int64_t n, int64_t P, int c
   return ff.finish(mean, std_, total_variance, out);
 }
 
+// What eofx_fit_first_f32 and eofx_fit_f32 share: the field and what eofx_preprocess_f32 returns for it.
+struct FitIO {
+  Staged& st;
+  int64_t n, P;
+  int center, standardize;
+  const double* feat_weights;
+  int check_nans;
+  eofx_mat** out;
+  double *mean, *std_;
+  uint8_t *valid_feature, *valid_sample;
+  int64_t *n_out, *p_out;
+  double* total_variance;
+  int* fused;
+};
+// the fused pass succeeded (*io.out is set): nothing was dropped, pv of the P features hold data
+static int fit_fused_done(eofx_ctx* ctx, const FitIO& io, int64_t pv) {
+  adopt_staged(io.out, io.st, (size_t)io.n * io.P * sizeof(float));
+  if (io.valid_sample) std::memset(io.valid_sample, 1, (size_t)io.n);
+  if (io.n_out) *io.n_out = io.n;
+  if (io.p_out) *io.p_out = pv;
+  if (io.fused) *io.fused = 1;
+  ctx->fit_info[0] = 1.0;
+  return EOFX_OK;
+}
+// a matrix whose follow-up failed goes; the message of the failure stays
+static int destroy_keep_err(eofx_ctx* ctx, eofx_mat* m, int rc) {
+  const std::string keep = ctx->err;
+  eofx_mat_destroy(ctx, m);
+  ctx->err = keep;
+  return rc;
+}
+// the two-step path: statistics pass, NaN policies of the Sanitizer, then follow_up(matrix, samples kept)
+template <class FollowUp>
+static int fit_two_step(eofx_ctx* ctx, const FitIO& io, FollowUp&& follow_up) {
+  eofx_mat* m = nullptr;
+  int64_t ns = 0, pv = 0;
+  CHK(eofx_preprocess_f32(ctx, io.st.dev, io.n, io.P, io.center, io.standardize, io.feat_weights, io.check_nans, &m, io.mean, io.std_,
+                          io.valid_feature, io.valid_sample, &ns, &pv, io.total_variance));
+  adopt_staged(&m, io.st, (size_t)io.n * io.P * sizeof(float));
+  if (io.n_out) *io.n_out = ns;
+  if (io.p_out) *io.p_out = pv;
+  const int rc = follow_up(m, ns);
+  if (rc != EOFX_OK) return destroy_keep_err(ctx, m, rc);
+  *io.out = m;
+  return EOFX_OK;
+}
+
 // The first pass on its own, for drivers that put collectives between the passes (the feature-sharded fit: the product
 // X_g^T Z of a rank's shard needs no communication, so every rank takes its statistics while it computes it):
 // Yp [p_pad x L] = X'^T Zn for the device panel Zn [n_pad x L] whose first l columns are in use (l < L: the spare column
@@ -2594,6 +2628,8 @@ extern "C" int eofx_fit_first_f32(eofx_ctx* ctx, const float* X, int64_t n, int6
   ctx->fit_info[0] = ctx->fit_info[1] = ctx->fit_info[2] = 0.0;
   Staged st;
   CHK(stage_input(ctx, X, (size_t)n * P, st));
+  const FitIO io{st, n, P, center, standardize, feat_weights, check_nans, out, mean, std_, valid_feature, valid_sample, n_out, p_out,
+                 total_variance, fused};
   if (fit_first_eligible(ctx, st.dev, n, P, l) && round_up(l, 32) == L) {
     CHK(arena_reserve(ctx, FitFirst::bytes(n, P, l) + atb_scratch_bytes(round_up(P, ATB_BM), round_up(n, ATB_KG), L)));
     ArenaScope scope(ctx);
@@ -2605,33 +2641,14 @@ extern "C" int eofx_fit_first_f32(eofx_ctx* ctx, const float* X, int64_t n, int6
       CHK(ff.valid_features(valid_feature));
       const int64_t pv_fused = ff.m->masked ? ff.m->p_valid : P;
       CHK(ff.finish(mean, std_, total_variance, out));
-      adopt_staged(out, st, (size_t)n * P * sizeof(float));
-      if (valid_sample) std::memset(valid_sample, 1, (size_t)n);
-      if (n_out) *n_out = n;
-      if (p_out) *p_out = pv_fused;
-      if (fused) *fused = 1;
-      ctx->fit_info[0] = 1.0;
-      return EOFX_OK;
+      return fit_fused_done(ctx, io, pv_fused);
     }
   } else {
     ctx->fit_info[2] = -1.0;
   }
-  eofx_mat* m = nullptr;
-  int64_t ns = 0, pv = 0;
-  CHK(eofx_preprocess_f32(ctx, st.dev, n, P, center, standardize, feat_weights, check_nans, &m, mean, std_, valid_feature,
-                          valid_sample, &ns, &pv, total_variance));
-  adopt_staged(&m, st, (size_t)n * P * sizeof(float));
-  if (n_out) *n_out = ns;
-  if (p_out) *p_out = pv;
-  int rc = ns == n ? eofx_panel_tmul_f32(ctx, m, Zn, Yp, L, ctx->prec_power) : EOFX_OK;   // dropped samples: the caller re-imports Z
-  if (rc != EOFX_OK) {
-    const std::string keep = ctx->err;
-    eofx_mat_destroy(ctx, m);
-    ctx->err = keep;
-    return rc;
-  }
-  *out = m;
-  return EOFX_OK;
+  return fit_two_step(ctx, io, [&](eofx_mat* m, int64_t ns) {      // dropped samples: the caller re-imports Z
+    return ns == n ? eofx_panel_tmul_f32(ctx, m, Zn, Yp, L, ctx->prec_power) : EOFX_OK;
+  });
 }
 
 extern "C" int eofx_fit_f32(eofx_ctx* ctx, const float* X, int64_t n, int64_t P, int center, int standardize,
@@ -2646,49 +2663,25 @@ extern "C" int eofx_fit_f32(eofx_ctx* ctx, const float* X, int64_t n, int64_t P,
   ctx->fit_info[0] = ctx->fit_info[1] = ctx->fit_info[2] = 0.0;
   Staged st;
   CHK(stage_input(ctx, X, (size_t)n * P, st));
-  const int l_req = k + n_oversamples;
-  const int l = (int)std::min<int64_t>(l_req, std::min(n, P));
-  const int iters = n_iter < 0 ? rsvd_auto_iters(k, n, P) : n_iter;
-  const bool eligible = fit_first_eligible(ctx, st.dev, n, P, l) && k <= n && l == l_req && omega_rows >= n && !is_device_ptr(omega);
-  if (eligible) {
+  const FitIO io{st, n, P, center, standardize, feat_weights, check_nans, out, mean, std_, valid_feature, valid_sample, n_out, p_out,
+                 total_variance, fused};
+  const RsvdPlan pl = rsvd_plan(n, P, k, n_oversamples, n_iter);
+  if (fused_fit_eligible(ctx, st.dev, n, P, k, pl, omega_rows, omega)) {
     int64_t pv_fused = P;
-    const int rc = fit_fused(ctx, st.dev, n, P, center, standardize, feat_weights, k, l, iters, omega, flip, out, mean, std_,
+    const int rc = fit_fused(ctx, st.dev, n, P, center, standardize, feat_weights, k, pl.l, pl.n_iter, omega, flip, out, mean, std_,
                              total_variance, U, s, V, valid_feature, &pv_fused);
     if (rc < 0) return rc;
-    if (rc == EOFX_OK) {
-      adopt_staged(out, st, (size_t)n * P * sizeof(float));
-      if (valid_sample) std::memset(valid_sample, 1, (size_t)n);
-      if (n_out) *n_out = n;
-      if (p_out) *p_out = pv_fused;
-      if (fused) *fused = 1;
-      ctx->fit_info[0] = 1.0;
-      return EOFX_OK;
-    }
+    if (rc == EOFX_OK) return fit_fused_done(ctx, io, pv_fused);
   } else {
     ctx->fit_info[2] = -1.0;   // shape / precision / layout outside the fused path
   }
-  // the two-step path: statistics pass, NaN policies of the Sanitizer, then the decomposition
-  eofx_mat* m = nullptr;
-  int64_t ns = 0, pv = 0;
-  CHK(eofx_preprocess_f32(ctx, st.dev, n, P, center, standardize, feat_weights, check_nans, &m, mean, std_, valid_feature,
-                          valid_sample, &ns, &pv, total_variance));
-  adopt_staged(&m, st, (size_t)n * P * sizeof(float));
-  if (n_out) *n_out = ns;
-  if (p_out) *p_out = pv;
-  const int64_t small = std::min(m->n, m->p);
-  int rc = EOFX_OK;
-  if (omega_rows < small)
-    rc = set_err(ctx, EOFX_ERR_ARG, "omega has %lld rows, the compacted matrix needs %lld", (long long)omega_rows, (long long)small);
-  // numpy fills the sketch row by row, so the (small x l) draw of the reference is the leading part of a taller one
-  if (rc == EOFX_OK) rc = eofx_rsvd_f32(ctx, m, k, n_oversamples, n_iter, omega, flip, U, s, V);
-  if (rc != EOFX_OK) {
-    const std::string keep = ctx->err;
-    eofx_mat_destroy(ctx, m);
-    ctx->err = keep;
-    return rc;
-  }
-  *out = m;
-  return EOFX_OK;
+  return fit_two_step(ctx, io, [&](eofx_mat* m, int64_t) {
+    const int64_t small = std::min(m->n, m->p);
+    if (omega_rows < small)
+      return set_err(ctx, EOFX_ERR_ARG, "omega has %lld rows, the compacted matrix needs %lld", (long long)omega_rows, (long long)small);
+    // numpy fills the sketch row by row, so the (small x l) draw of the reference is the leading part of a taller one
+    return eofx_rsvd_f32(ctx, m, k, n_oversamples, n_iter, omega, flip, U, s, V);
+  });
 }
 
 // ------------------------------------------------------------------------------------
@@ -2977,20 +2970,16 @@ extern "C" int eofx_fit_sharded_f32(eofx_ctx* ctx, const float* X, int64_t n, in
   // would wait in the vote's all-reduce for ever.  It becomes this rank's verdict (2) and every rank leaves together.
   Staged st;
   int rc = stage_input(ctx, X, (size_t)n * P, st);
-  const int l_req = k + n_oversamples;
-  const int l = (int)std::min<int64_t>(l_req, n);
-  const int iters = n_iter < 0 ? rsvd_auto_iters(k, n, P_total) : n_iter;
+  const RsvdPlan pl = rsvd_plan(n, P_total, k, n_oversamples, n_iter);      // (n < P_total: the sketch is bounded by n)
+  const int l = pl.l;
   const int64_t p_pad = round_up(P, ATB_BM), n_pad = round_up(n, ATB_BM);
-  if (rc == EOFX_OK) {
-    const size_t Lo_ = (size_t)round_up(k, 32);
-    rc = arena_reserve(ctx, rsvd_scratch_bytes(p_pad, n_pad, l, k) + FitFirst::bytes(n, P, l) + (1 << 16) +
-                                (size_t)p_pad * Lo_ * 4 + (size_t)(gram_parts(p_pad, (int)Lo_) + 4) * Lo_ * Lo_ * 8 + (64 << 10));
-  }
+  if (rc == EOFX_OK)
+    rc = arena_reserve(ctx, rsvd_scratch_bytes(p_pad, n_pad, l, k) + FitFirst::bytes(n, P, l) + (1 << 16) + null_repair_bytes(p_pad, pl.Lo));
   ArenaScope scope(ctx);
   FitFirst ff;
   ff.sharded = true;
   if (rc == EOFX_OK) {
-    const bool eligible = fit_first_eligible(ctx, st.dev, n, P, l) && k <= n && l == l_req && omega_rows >= n && !is_device_ptr(omega);
+    const bool eligible = fused_fit_eligible(ctx, st.dev, n, P, k, pl, omega_rows, omega);
     rc = eligible ? ff.prepare(ctx, st.dev, n, P, center, standardize, feat_weights, l) : EOFX_FIT_FALLBACK;
     if (!eligible) ctx->fit_info[2] = -1.0;
   }
@@ -3026,31 +3015,13 @@ extern "C" int eofx_fit_sharded_f32(eofx_ctx* ctx, const float* X, int64_t n, in
   op.reduce_tall_gram = [&](double* G, int64_t count) { return comm_allreduce(ctx, G, count, 1, 0); };
   op.rule_tall_pad = round_up(P_total, ATB_BM);
   RsvdOut ro;
-  rc = rsvd_core(ctx, op, k, l, iters, omega, ro, &first);
+  rc = rsvd_core(ctx, op, k, l, pl.n_iter, omega, ro, &first);
   if (rc != EOFX_OK) return rc;       // (EOFX_FIT_FALLBACK: every rank leaves here together)
   // numerically null modes (more modes than the field has rank): both factors stay orthonormal, as in eofx_fit_f32 -- the
   // feature-side factor through its all-reduced Gram matrix, the replicated sample-side one locally (same bits on every rank)
-  CHK(fix_null_modes(ctx, ro, P, n, k, &op.reduce_tall_gram, P_total));
-  // sign rule over all slices: one all-reduce(max) of [max | -min]
-  std::vector<double> sign(k, 1.0);
-  if (flip) {
-    ARENA(float, ext, 2 * (size_t)ro.Lo);
-    CHK(launch_colminmax(ctx, ro.Tvec, P, ro.Lo, ext, ext + ro.Lo));
-    hipLaunchKernelGGL(negate_kernel, dim3(1), dim3(256), 0, ctx->stream, ext + ro.Lo, ro.Lo);
-    KCHK();
-    CHK(comm_allreduce(ctx, ext, 2 * (int64_t)ro.Lo, 0, 1));
-    std::vector<float> h(2 * (size_t)ro.Lo);
-    HIPCHK(hipMemcpyAsync(h.data(), ext, sizeof(float) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int j = 0; j < k; ++j) sign[j] = (std::fabs(h[j]) >= std::fabs(-h[ro.Lo + j])) ? 1.0 : -1.0;
-  }
-  CHK(export_panel(ctx, ro.Svec, n, ro.Lo, k, flip ? sign.data() : nullptr, U));
-  CHK(export_panel(ctx, ro.Tvec, P, ro.Lo, k, flip ? sign.data() : nullptr, V));
-  if (s) {
-    std::vector<float> hs(k);
-    for (int j = 0; j < k; ++j) hs[j] = (float)ro.s[j];
-    HIPCHK(hipMemcpy(s, hs.data(), sizeof(float) * k, hipMemcpyDefault));
-  }
+  // the sign rule reads the extrema over all slices
+  const FactorShards shards{&op.reduce_tall_gram, P_total};
+  CHK(rsvd_finish(ctx, ro, true, n, P, k, flip, U, s, V, 1.0, &shards));
   CHK(ff.valid_features(valid_feature));
   double tv_local = 0.0;
   CHK(ff.finish(mean, std_, &tv_local, out));
@@ -3457,6 +3428,72 @@ extern "C" int eofx_vec_dot_f64(eofx_ctx* ctx, const float* a, const float* b, i
 struct CrossShard {
   int64_t p1_total, p1_offset, p2_total, p2_offset;
 };
+// a sample-side panel of a sharded fit: the sum of the ranks' partial sums
+static int cross_reduce_panel(eofx_ctx* ctx, bool shd, float* Pn, int64_t count) {
+  if (!shd) return EOFX_OK;
+  amax_forget(ctx, Pn);
+  return comm_allreduce(ctx, Pn, count, 0, 0);
+}
+// Gx = X X^T, Gy = Y Y^T [n_pad x n_pad] through the NT kernel (fast) or the streaming product; sharded: summed over the slices
+static int cross_sample_grams(eofx_ctx* ctx, const eofx_mat* x, const eofx_mat* y, bool fast, bool shd, float* Gx, float* Gy) {
+  for (int which = 0; which < 2; ++which) {
+    const eofx_mat* m = which ? y : x;
+    float* G = which ? Gy : Gx;
+    CHK(fast ? mat_gram_fast(ctx, m, G) : sample_gram(ctx, m, G));
+    if (shd) CHK(comm_allreduce(ctx, G, m->n_pad * m->n_pad, 0, 0));
+  }
+  return EOFX_OK;
+}
+// The range finder in sample space.  With the two sample-space Gram matrices resident the power iterations need not touch the
+// fields at all: A = Ft^T Fs (Ft the field on the tall side), A Z = Ft^T (Fs Z) and (A^T A) Z = Fs^T Gt (Fs Z), so in terms of
+// T = Fs Z (n x l) one iteration is T <- Gs (Gt T) -- two n x n x l products (tens of microseconds) instead of four passes over
+// the fields.  Same subspace in exact arithmetic as scikit-learn's iteration on C (range of (C C^T)^q C Omega); the range basis
+// and the projection that decides the singular values are still computed from the fields themselves.
+// Tn: the caller's [n_pad x LL] panel; Zs -> Yt as a RangeFinder.
+static int cross_gram_range(eofx_ctx* ctx, const eofx_mat* ft, const eofx_mat* fs, const float* Gt, const float* Gs, bool shd, float* Tn,
+                            int l, int n_iter, const float* Zs, float* Yt, int LL) {
+  const int64_t npad = ft->n_pad;
+  ArenaScope inner(ctx);
+  ARENA(float, T2, (size_t)npad * LL);
+  ARENA(double, Gd, (size_t)LL * LL);
+  auto orth = [&](const float* in, float* outp) -> int {     // Cholesky-QR of an n x l panel (float64 Gram matrix)
+    CHK(launch_gram(ctx, in, npad, LL, Gd));
+    return launch_cholqr(ctx, in, npad, LL, l, Gd, outp);
+  };
+  // exact-f32 MFMA products with the symmetric Gram matrices (G^T T = G T): 100 MB each, tens of microseconds
+  auto gmul = [&](const float* Gm, const float* in, float* outp) -> int {
+    return launch_atb(ctx, Gm, npad, npad, npad, in, LL, LL, outp, EOFX_PREC_F32);
+  };
+  CHK(panel_mul(ctx, fs, Zs, Tn, LL, ctx->prec_power));      // T = Fs Z
+  CHK(cross_reduce_panel(ctx, shd, Tn, npad * LL));
+  for (int it = 0; it < n_iter; ++it) {
+    CHK(orth(Tn, T2));
+    CHK(gmul(Gt, T2, Tn));
+    CHK(orth(Tn, T2));
+    CHK(gmul(Gs, T2, Tn));
+  }
+  CHK(orth(Tn, T2));
+  return panel_tmul(ctx, ft, T2, Yt, LL, ctx->prec_power);   // Yt = Ft^T T
+}
+// scores = field x vectors and their norms (cpcca.py:204-208) of one side; Sn [n_pad x Lo], Gn [Lo x Lo]: the caller's
+static int cross_scores(eofx_ctx* ctx, const eofx_mat* m, bool shd, const float* Qp, int Lo, int k, const double* sign, float* Sn, double* Gn,
+                        float* scores, float* norm) {
+  if (!scores && !norm) return EOFX_OK;
+  CHK(panel_mul(ctx, m, Qp, Sn, Lo, ctx->prec_final));
+  CHK(cross_reduce_panel(ctx, shd, Sn, m->n_pad * Lo));
+  CHK(export_panel(ctx, Sn, m->n, Lo, k, sign, scores));
+  if (norm) {
+    CHK(launch_gram(ctx, Sn, m->n_pad, Lo, Gn));
+    std::vector<double> hg((size_t)Lo * Lo);
+    HIPCHK(hipMemcpyAsync(hg.data(), Gn, sizeof(double) * hg.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    std::vector<float> hn(k);
+    for (int j = 0; j < k; ++j) hn[j] = (float)std::sqrt(hg[(size_t)j * Lo + j]);
+    HIPCHK(hipMemcpy(norm, hn.data(), sizeof(float) * k, hipMemcpyDefault));
+  }
+  return EOFX_OK;
+}
+
 static int crosscov_impl(eofx_ctx* ctx, const eofx_mat* x, const eofx_mat* y, int k,
                          int n_oversamples, int n_iter, const float* omega, eofx_sketch_fn omega_fn, void* omega_user, int flip,
                          float* Q1, float* s, float* Q2, float* scores1, float* scores2,
@@ -3467,189 +3504,99 @@ static int crosscov_impl(eofx_ctx* ctx, const eofx_mat* x, const eofx_mat* y, in
     return set_err(ctx, EOFX_ERR_SHAPE,
                    "Both data matrices must have the same number of samples but found %lld in the first and %lld in the second.",
                    (long long)x->n, (long long)y->n);
+  // ---- 1. plan and vote.  The VALID feature counts decide the orientation, the rank and the iteration count, as in the reference
+  // (a masked in-place matrix carries its all-NaN grid points as zero columns: p1 / p2 are the physical widths of the panels).
+  // The Gram route (cross_gram_range) is taken when the TSC is asked for -- it needs the two Gram matrices anyway -- and both
+  // fields are wider than long.
   const bool shd = sh != nullptr;
-  const int64_t n = x->n, p1 = x->p, p2 = y->p;
-  // the VALID feature counts decide the orientation, the rank and the iteration count, as in the reference (a masked in-place
-  // matrix carries its all-NaN grid points as zero columns: p1 / p2 below are the physical widths of the panels)
-  const int64_t P1 = shd ? sh->p1_total : (x->masked ? x->p_valid : p1), P2 = shd ? sh->p2_total : (y->masked ? y->p_valid : p2),
-                r = std::min(P1, P2);
-  auto reduce_panel = [&](float* Pn, int64_t count) -> int {      // a sample-side panel: sum of the ranks' partial sums
-    if (!shd) return EOFX_OK;
-    amax_forget(ctx, Pn);
-    return comm_allreduce(ctx, Pn, count, 0, 0);
-  };
-  GramReduce reduce_gram;
-  if (shd) reduce_gram = [&](double* Gm, int64_t count) { return comm_allreduce(ctx, Gm, count, 1, 0); };
-  if (k > r)
+  const int64_t n = x->n, p1 = x->p, p2 = y->p, npad = x->n_pad;
+  const int64_t P1 = shd ? sh->p1_total : (x->masked ? x->p_valid : p1), P2 = shd ? sh->p2_total : (y->masked ? y->p_valid : p2);
+  const bool fast = gram_fast_ok(x) && gram_fast_ok(y);
+  const CrossPlan pl = cross_plan(n, npad, p1, x->p_pad, p2, y->p_pad, P1, P2, shd, tsc != nullptr, fast, fast, fast ? gram_fast_scratch(ctx, x) : 0,
+                                  fast ? gram_fast_scratch(ctx, y) : 0, k, n_oversamples, n_iter, std::getenv("EOFX_CROSS_NO_GRAM") != nullptr);
+  if (pl.status == RSVD_PLAN_RANK)
     return set_err(ctx, EOFX_ERR_RANK,
-                   "n_modes must be less than or equal to the rank of the dataset (rank = %lld).", (long long)r);
-  const int l_req = k + n_oversamples;
-  const int l = (int)std::min<int64_t>(l_req, r);
-  if (l > EOFX_MAX_SKETCH) return set_err(ctx, EOFX_ERR_ARG, "sketch width %d > %d is not supported", l, EOFX_MAX_SKETCH);
-  if (l != l_req) return set_err(ctx, EOFX_ERR_ARG, "sketch wider than rank not supported on the cross path");
-  if (n_iter < 0) n_iter = rsvd_auto_iters(k, P1, P2);
-  const int L = (int)round_up(l, 32);
-  const bool transposed = P1 < P2;  // C is (p1 x p2): sklearn transposes when rows < cols
-  const int64_t npad = x->n_pad;
-  // The total squared covariance needs the two sample-space Gram matrices (below).  With them resident the power
-  // iterations need not touch the fields at all: A = Ft^T Fs (Ft the field on the tall side), A Z = Ft^T (Fs Z) and
-  // (A^T A) Z = Fs^T Gt (Fs Z), so in terms of T = Fs Z (n x l) one iteration is T <- Gs (Gt T) -- two n x n x l products
-  // (tens of microseconds) instead of four passes over the fields.  Same subspace in exact arithmetic as scikit-learn's
-  // iteration on C (range of (C C^T)^q C Omega); the range basis and the projection that decides the singular values are
-  // still computed from the fields themselves.  Taken when the TSC is asked for and both fields are wider than long.
-  bool gram_route = tsc && n < P1 && n < P2 && gram_fast_ok(x) && gram_fast_ok(y) && !std::getenv("EOFX_CROSS_NO_GRAM");
-  size_t need = rsvd_scratch_bytes(std::max(x->p_pad, y->p_pad), std::max(x->p_pad, y->p_pad), l, k) +
-                (size_t)npad * L * 4 * 2 + atb_scratch_bytes(npad, std::max(x->p_pad, y->p_pad), L);
-  if (tsc) need += (size_t)npad * npad * 4 * 2 + (1 << 20);
-  const size_t need_gram = gram_fast_ok(x) && gram_fast_ok(y)
-                               ? std::max(gram_fast_scratch(ctx, x), gram_fast_scratch(ctx, y)) + (size_t)npad * L * 4 * 2 + atb_scratch_bytes(npad, npad, L)
-                               : 0;
-  const size_t need_plain = tsc ? atb_scratch_bytes(npad, std::max(x->p_pad, y->p_pad), (int)npad) : 0;
+                   "n_modes must be less than or equal to the rank of the dataset (rank = %lld).", (long long)pl.r);
+  if (pl.status == RSVD_PLAN_WIDTH) return set_err(ctx, EOFX_ERR_ARG, "sketch width %d > %d is not supported", pl.l, EOFX_MAX_SKETCH);
+  if (pl.l != pl.l_req) return set_err(ctx, EOFX_ERR_ARG, "sketch wider than rank not supported on the cross path");
+  const int l = pl.l, L = pl.L;
+  const bool transposed = pl.transposed;  // C is (p1 x p2): sklearn transposes when rows < cols
+  bool gram_route = pl.gram_route;
   if (shd) {
     // The Gram route is a collective decision (a rank's slice may not qualify), and so is an error of this rank before the first
-    // data collective (growing the arena): one vote -- 0 go on with the Gram route, 1 without it, 2 some rank failed.  The arena is
-    // sized for either route up front (+ room for the null-mode repair of a sharded factor).
-    const size_t Lo_ = (size_t)round_up(k, 32), pp_ = (size_t)std::max(x->p_pad, y->p_pad);
-    need += pp_ * Lo_ * 4 + (size_t)(gram_parts((int64_t)pp_, (int)Lo_) + 4) * Lo_ * Lo_ * 8 + (64 << 10) + std::max(need_gram, need_plain);
+    // data collective (growing the arena): one vote -- 0 go on with the Gram route, 1 without it, 2 some rank failed.
     int worst = 0;
-    CHK(comm_agree(ctx, arena_reserve(ctx, need), gram_route ? 0 : 1, "the sharded cross-covariance fit", &worst));
+    CHK(comm_agree(ctx, arena_reserve(ctx, pl.arena_bytes), gram_route ? 0 : 1, "the sharded cross-covariance fit", &worst));
     gram_route = worst == 0;
   } else {
-    need += gram_route ? need_gram : need_plain;
-    CHK(arena_reserve(ctx, need));
+    CHK(arena_reserve(ctx, pl.arena_bytes));
   }
   ArenaScope scope(ctx);
   ARENA(float, Tn, (size_t)npad * L);
+  // ---- 2. the two sample-space Gram matrices (the Gram route needs them now, the other route at the end)
   float *Gx = nullptr, *Gy = nullptr;
   if (tsc) {
     Gx = arena_alloc<float>(ctx, (size_t)npad * npad);
     Gy = arena_alloc<float>(ctx, (size_t)npad * npad);
     if (!Gx || !Gy) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (Gram matrices)");
   }
-  if (gram_route) {
-    CHK(mat_gram_fast(ctx, x, Gx));
-    if (shd) CHK(comm_allreduce(ctx, Gx, npad * npad, 0, 0));      // X X^T = sum over the slices
-    CHK(mat_gram_fast(ctx, y, Gy));
-    if (shd) CHK(comm_allreduce(ctx, Gy, npad * npad, 0, 0));
-  }
-  // C   Z = X^T (Y Z);   C^T W = Y^T (X W)     (scaling by 1/(n-1) is applied to s at the end)
+  if (gram_route) CHK(cross_sample_grams(ctx, x, y, true, shd, Gx, Gy));
+  // ---- 3. the operator: C Z = X^T (Y Z);  C^T W = Y^T (X W)     (the scaling by 1/(n-1) is applied to s at the end)
   auto C_mul = [&](const float* z2, float* out1, int LL, int pr) {
     CHK(panel_mul(ctx, y, z2, Tn, LL, pr));
-    CHK(reduce_panel(Tn, npad * LL));
+    CHK(cross_reduce_panel(ctx, shd, Tn, npad * LL));
     return panel_tmul(ctx, x, Tn, out1, LL, pr);
   };
   auto Ct_mul = [&](const float* z1, float* out2, int LL, int pr) {
     CHK(panel_mul(ctx, x, z1, Tn, LL, pr));
-    CHK(reduce_panel(Tn, npad * LL));
+    CHK(cross_reduce_panel(ctx, shd, Tn, npad * LL));
     return panel_tmul(ctx, y, Tn, out2, LL, pr);
   };
-  LinOp op;
-  if (transposed)
-    op = {p2, p1, y->p_pad, x->p_pad, Ct_mul, C_mul};  // A = C^T (p2 x p1)
-  else
-    op = {p1, p2, x->p_pad, y->p_pad, C_mul, Ct_mul};  // A = C   (p1 x p2)
+  LinOp op = {pl.tall, pl.small, pl.tall_pad, pl.small_pad, C_mul, Ct_mul};      // A = C   (p1 x p2)
+  if (transposed) std::swap(op.fwd, op.bwd);                                      // A = C^T (p2 x p1)
+  GramReduce reduce_gram;
   if (shd) {
+    reduce_gram = [&](double* Gm, int64_t count) { return comm_allreduce(ctx, Gm, count, 1, 0); };
     op.reduce_tall_gram = reduce_gram;
     op.reduce_small_gram = reduce_gram;
     op.rule_tall_pad = round_up(transposed ? P2 : P1, ATB_BM);
   }
-  // the sketch is asked for only now: on the Gram route ~18 ms of matrix work are already queued behind which the caller's
-  // generator (scikit-learn's legacy stream: ~5 ms for 129 600 x 30 deviates) finishes unnoticed
+  // ---- 4. the range finder.  The sketch is asked for only now: on the Gram route ~18 ms of matrix work are already queued behind
+  // which the caller's generator (scikit-learn's legacy stream: ~5 ms for 129 600 x 30 deviates) finishes unnoticed
   if (!omega) {
     omega = omega_fn(omega_user);
     if (!omega) return set_err(ctx, EOFX_ERR_ARG, "the sketch callback returned no matrix");
   }
-  std::vector<float> om_eye;
-  if (l == r && !shd) {   // full-width sketch: identity (see eofx_rsvd_f32); a sharded caller hands over its rows of it
+  std::vector<float> eye;
+  if (pl.full_width && !shd) {   // (a sharded caller hands over its rows of the identity)
     if ((transposed ? x : y)->masked)
       return set_err(ctx, EOFX_ERR_ARG, "a sketch as wide as the rank on a masked in-place matrix is not supported (compact the field)");
-    om_eye.assign((size_t)op.small * l, 0.f);
-    for (int64_t i = 0; i < l; ++i) om_eye[(size_t)i * l + i] = 1.f;
-    omega = om_eye.data();
+    omega = identity_sketch(op.small, l, eye);
   }
-  RsvdOut ro;
-  if (gram_route) {
-    const eofx_mat* ft = transposed ? y : x;     // field on the tall side of A
-    const eofx_mat* fs = transposed ? x : y;
-    const float* Gt = transposed ? Gy : Gx;
-    const float* Gs = transposed ? Gx : Gy;
-    RangeFinder range = [&](const float* Zs, float* Yt, int LL) -> int {
-      ArenaScope inner(ctx);
-      ARENA(float, T2, (size_t)npad * LL);
-      ARENA(double, Gd, (size_t)LL * LL);
-      auto orth = [&](const float* in, float* outp) -> int {     // Cholesky-QR of an n x l panel (float64 Gram matrix)
-        CHK(launch_gram(ctx, in, npad, LL, Gd));
-        return launch_cholqr(ctx, in, npad, LL, l, Gd, outp);
-      };
-      // exact-f32 MFMA products with the symmetric Gram matrices (G^T T = G T): 100 MB each, tens of microseconds
-      auto gmul = [&](const float* Gm, const float* in, float* outp) -> int {
-        return launch_atb(ctx, Gm, npad, npad, npad, in, LL, LL, outp, EOFX_PREC_F32);
-      };
-      CHK(panel_mul(ctx, fs, Zs, Tn, LL, ctx->prec_power));      // T = Fs Z
-      CHK(reduce_panel(Tn, npad * LL));
-      for (int it = 0; it < n_iter; ++it) {
-        CHK(orth(Tn, T2));
-        CHK(gmul(Gt, T2, Tn));
-        CHK(orth(Tn, T2));
-        CHK(gmul(Gs, T2, Tn));
-      }
-      CHK(orth(Tn, T2));
-      return panel_tmul(ctx, ft, T2, Yt, LL, ctx->prec_power);   // Yt = Ft^T T
+  RangeFinder range;
+  if (gram_route)
+    range = [&](const float* Zs, float* Yt, int LL) -> int {      // (the field on the tall side of A first)
+      return cross_gram_range(ctx, transposed ? y : x, transposed ? x : y, transposed ? Gy : Gx, transposed ? Gx : Gy, shd, Tn, l, pl.n_iter, Zs,
+                              Yt, LL);
     };
-    CHK(rsvd_core(ctx, op, k, l, n_iter, omega, ro, nullptr, &range));
-  } else {
-    CHK(rsvd_core(ctx, op, k, l, n_iter, omega, ro));
-  }
-  // (more modes than the cross-covariance has rank)
-  if (shd)
-    CHK(fix_null_modes(ctx, ro, transposed ? p2 : p1, transposed ? p1 : p2, k, &reduce_gram, transposed ? P2 : P1, &reduce_gram,
-                       transposed ? P1 : P2));
-  else
-    CHK(fix_null_modes(ctx, ro, transposed ? p2 : p1, transposed ? p1 : p2, k));
-  const float* Q1p = transposed ? ro.Svec : ro.Tvec;  // left vectors of C  (p1)
-  const float* Q2p = transposed ? ro.Tvec : ro.Svec;  // right vectors of C (p2)
+  // ---- 5. the decomposition
+  RsvdOut ro;
+  CHK(rsvd_core(ctx, op, k, l, pl.n_iter, omega, ro, nullptr, gram_route ? &range : nullptr));
+  // ---- 6. finish: the left vectors of C (p1), the right ones (p2), s / (n - 1)
+  const FactorShards shards{&reduce_gram, transposed ? P2 : P1, &reduce_gram, transposed ? P1 : P2};
   std::vector<double> sign;
-  if (flip) CHK(sign_rule(ctx, Q2p, p2, ro.Lo, k, sign, shd));
-  const double* sg = flip ? sign.data() : nullptr;
-  CHK(export_panel(ctx, Q1p, p1, ro.Lo, k, sg, Q1));
-  CHK(export_panel(ctx, Q2p, p2, ro.Lo, k, sg, Q2));
-  if (s) {
-    std::vector<float> hs(k);
-    for (int j = 0; j < k; ++j) hs[j] = (float)(ro.s[j] / (double)(n - 1));
-    HIPCHK(hipMemcpy(s, hs.data(), sizeof(float) * k, hipMemcpyDefault));
-  }
-  // scores and norms (cpcca.py:204-208)
+  CHK(rsvd_finish(ctx, ro, transposed, p1, p2, k, flip, Q1, s, Q2, (double)(n - 1), shd ? &shards : nullptr, &sign));
+  // ---- 7. scores and norms
   if (scores1 || scores2 || norm1 || norm2) {
+    const double* sg = flip ? sign.data() : nullptr;
     ARENA(float, Sn, (size_t)npad * ro.Lo);
     ARENA(double, Gs, (size_t)ro.Lo * ro.Lo);
-    for (int which = 0; which < 2; ++which) {
-      const eofx_mat* mm = which ? y : x;
-      const float* Qp = which ? Q2p : Q1p;
-      float* sc = which ? scores2 : scores1;
-      float* nr = which ? norm2 : norm1;
-      if (!sc && !nr) continue;
-      CHK(panel_mul(ctx, mm, Qp, Sn, ro.Lo, ctx->prec_final));
-      CHK(reduce_panel(Sn, npad * ro.Lo));
-      CHK(export_panel(ctx, Sn, n, ro.Lo, k, sg, sc));
-      if (nr) {
-        CHK(launch_gram(ctx, Sn, npad, ro.Lo, Gs));
-        std::vector<double> hg((size_t)ro.Lo * ro.Lo);
-        HIPCHK(hipMemcpyAsync(hg.data(), Gs, sizeof(double) * hg.size(), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        std::vector<float> hn(k);
-        for (int j = 0; j < k; ++j) hn[j] = (float)std::sqrt(hg[(size_t)j * ro.Lo + j]);
-        HIPCHK(hipMemcpy(nr, hn.data(), sizeof(float) * k, hipMemcpyDefault));
-      }
-    }
+    CHK(cross_scores(ctx, x, shd, transposed ? ro.Svec : ro.Tvec, ro.Lo, k, sg, Sn, Gs, scores1, norm1));
+    CHK(cross_scores(ctx, y, shd, transposed ? ro.Tvec : ro.Svec, ro.Lo, k, sg, Sn, Gs, scores2, norm2));
   }
-  // total squared covariance ||X^T Y||_F^2/(n-1)^2 = <X X^T, Y Y^T>/(n-1)^2 : two n x n Grams (cpcca.py:197,991-1000)
+  // ---- 8. total squared covariance ||X^T Y||_F^2/(n-1)^2 = <X X^T, Y Y^T>/(n-1)^2 : two n x n Grams (cpcca.py:197,991-1000)
   if (tsc) {
-    if (!gram_route) {
-      CHK(sample_gram(ctx, x, Gx));
-      if (shd) CHK(comm_allreduce(ctx, Gx, npad * npad, 0, 0));
-      CHK(sample_gram(ctx, y, Gy));
-      if (shd) CHK(comm_allreduce(ctx, Gy, npad * npad, 0, 0));
-    }
+    if (!gram_route) CHK(cross_sample_grams(ctx, x, y, false, shd, Gx, Gy));
     double t = 0.0;
     CHK(device_dot(ctx, Gx, Gy, npad * npad, &t));
     *tsc = t / ((double)(n - 1) * (double)(n - 1));

@@ -187,6 +187,93 @@ inline bool orth_tall_rule(int64_t tall_pad, int L, int prec_power) {
   return prec_power == EOFX_PREC_F64 || (size_t)tall_pad * L * sizeof(float) <= EOFX_ORTH_TALL_BYTES;
 }
 
+// ---- the real decompositions (eofx_rsvd_f32, eofx_fit_f32, eofx_fit_sharded_f32, the cross-covariance entries) -----------------
+// fix_null_columns on a factor of rows_pad x Lo: the panel's copy, the partial Gram matrices and four Lo x Lo matrices
+inline size_t null_repair_bytes(int64_t rows_pad, int Lo) {
+  return (size_t)rows_pad * Lo * 4 + (size_t)(gram_parts(rows_pad, Lo) + 4) * Lo * Lo * 8 + (64 << 10);
+}
+// the blocked device Cholesky inverse of a sketch wider than one wavefront: 2 Lb^2 + Lb^2 / 2 + 64^2 + Lb doubles
+inline size_t rinv_blocked_bytes(int l) {
+  const size_t Lb = (size_t)round_up(l, 64);
+  return (2 * Lb * Lb + Lb * Lb / 2 + 64 * 64 + Lb) * sizeof(double) + 8192;
+}
+// everything rsvd_core carves for a tall_pad x small_pad operator, a sketch of l columns and k modes
+inline size_t rsvd_scratch_bytes(int64_t tall_pad, int64_t small_pad, int l, int k) {
+  const size_t L = (size_t)round_up(l, 32), Lo = (size_t)round_up(k, 32);
+  size_t b = 0;
+  b += 2 * small_pad * L * 4 + 2 * tall_pad * L * 4 + tall_pad * Lo * 4 + small_pad * Lo * 4;
+  b += atb_scratch_bytes(small_pad, tall_pad, (int)L);        // split-K partials (small side)
+  b += atb_scratch_bytes(tall_pad, small_pad, (int)L);        // split-K partials (tall side)
+  b += atb_scratch_bytes(small_pad, tall_pad, (int)Lo);
+  b += (size_t)(4 * gram_parts(std::max(tall_pad, small_pad), (int)L) + 8) * L * L * 8 + 2 * L * Lo * 8 + 4096;  // gram partials, Rinv, G0, R2, M1, M2
+  b += (size_t)std::max(tall_pad, small_pad) * (Lo + L) * 4;  // export / import staging
+  if (l > 64) b += rinv_blocked_bytes(l);                     // blocked device Cholesky of a wide sketch
+  b += 4 << 20;
+  return b;
+}
+
+enum { RSVD_PLAN_OK = 0, RSVD_PLAN_RANK, RSVD_PLAN_WIDTH };
+// The sketch rules of a rows x cols matrix (the counts the rank and the orientation are decided on: valid features of a masked
+// matrix, features over all ranks of a sharded one -- eofx_fit_sharded_f32 passes (n, P_total) with n < P_total, so r = n).
+// n_iter < 0: scikit-learn's count.  status: the first check that failed, in the order the entries report them; every field is
+// set either way (the fit entries do not look at the status: the two-step path reports it once the field is compacted).
+struct RsvdPlan {
+  int status;
+  int64_t r;                  // rank bound min(rows, cols)
+  int l_req, l;               // sketch width asked for (k + n_oversamples), used (<= r)
+  int L, Lo;                  // columns of the sketch panels / of the output panels (multiples of 32)
+  int n_iter;                 // resolved
+  bool transposed;            // rows < cols: the operator is the transpose (scikit-learn: n_samples < n_features)
+  bool full_width;            // l == r: the sketch spans everything, the identity replaces the Gaussian draw
+};
+inline RsvdPlan rsvd_plan(int64_t rows, int64_t cols, int k, int n_oversamples, int n_iter) {
+  RsvdPlan pl{};
+  pl.r = std::min(rows, cols);
+  pl.l_req = k + n_oversamples;
+  pl.l = (int)std::min<int64_t>(pl.l_req, pl.r);
+  pl.status = k > pl.r ? RSVD_PLAN_RANK : pl.l > EOFX_MAX_SKETCH ? RSVD_PLAN_WIDTH : RSVD_PLAN_OK;
+  pl.L = (int)round_up(pl.l, 32);
+  pl.Lo = (int)round_up(k, 32);
+  pl.n_iter = n_iter < 0 ? rsvd_auto_iters(k, rows, cols) : n_iter;
+  pl.transposed = rows < cols;
+  pl.full_width = pl.l == pl.r;
+  return pl;
+}
+
+// The cross-covariance driver: C = X^T Y of two n-sample matrices of p1 / p2 columns (physical widths; P1 / P2 are the counts the
+// rules see).  fast1 / fast2: gram_fast_ok of either matrix; fast_scratch1 / 2: gram_fast_scratch (0 where the route is refused).
+// gram_route is THIS rank's wish (the ranks of a sharded fit vote on it); the sharded arena holds either route and the null-mode
+// repair of a sharded factor, the local one the route taken.  arena_bytes is 0 unless status is RSVD_PLAN_OK.
+struct CrossPlan : RsvdPlan {
+  int64_t tall, small, tall_pad, small_pad;      // the operator A = C (p1 x p2), or C^T when transposed
+  bool gram_route;
+  size_t arena_bytes;
+};
+inline CrossPlan cross_plan(int64_t n, int64_t n_pad, int64_t p1, int64_t p1_pad, int64_t p2, int64_t p2_pad, int64_t P1, int64_t P2,
+                            bool sharded, bool want_tsc, bool fast1, bool fast2, size_t fast_scratch1, size_t fast_scratch2, int k,
+                            int n_oversamples, int n_iter, bool no_gram) {
+  CrossPlan pl{};
+  static_cast<RsvdPlan&>(pl) = rsvd_plan(P1, P2, k, n_oversamples, n_iter);
+  pl.tall = pl.transposed ? p2 : p1;
+  pl.small = pl.transposed ? p1 : p2;
+  pl.tall_pad = pl.transposed ? p2_pad : p1_pad;
+  pl.small_pad = pl.transposed ? p1_pad : p2_pad;
+  pl.gram_route = want_tsc && n < P1 && n < P2 && fast1 && fast2 && !no_gram;
+  if (pl.status != RSVD_PLAN_OK) return pl;
+  const int64_t pp = std::max(p1_pad, p2_pad);
+  const size_t panels = (size_t)n_pad * pl.L * 4 * 2;
+  size_t need = rsvd_scratch_bytes(pp, pp, pl.l, k) + panels + atb_scratch_bytes(n_pad, pp, pl.L);
+  if (want_tsc) need += (size_t)n_pad * n_pad * 4 * 2 + (1 << 20);      // the two sample-space Gram matrices
+  const size_t need_gram = fast1 && fast2 ? std::max(fast_scratch1, fast_scratch2) + panels + atb_scratch_bytes(n_pad, n_pad, pl.L) : 0;
+  const size_t need_plain = want_tsc ? atb_scratch_bytes(n_pad, pp, (int)n_pad) : 0;
+  if (sharded)
+    need += null_repair_bytes(pp, pl.Lo) + std::max(need_gram, need_plain);
+  else
+    need += pl.gram_route ? need_gram : need_plain;
+  pl.arena_bytes = need;
+  return pl;
+}
+
 // ---- the complex decomposition (eofx_rsvd_c64 and its Hilbert / sharded forms) ----------------------------------------------
 // Scratch of one pass of the complex operator on a panel of L real columns, either direction: the split-K partials of the two
 // streaming products, twice each (the two parts of a two-launch pass).
@@ -303,6 +390,13 @@ inline bool matmul_nt_ok(int64_t rows, int L, int Lo) {
 inline bool fit_first_eligible(int keep_raw, int prec_power, bool aligned16, int64_t n, int64_t P, int l) {
   return keep_raw == 2 && prec_power == EOFX_PREC_F16X3 && n < P && l > 0 && l < n && round_up(l, 32) <= 64 && l % 32 != 0 &&
          P % 4 == 0 && aligned16 && n < ((int64_t)1 << 31) && !std::getenv("EOFX_NO_FUSED_FIT");
+}
+// the whole fused fit (eofx_fit_f32, eofx_fit_sharded_f32): the first pass as above, an unclamped sketch of the plan `sk` and a
+// host sketch matrix with a row for every sample
+inline bool fused_fit_eligible(int keep_raw, int prec_power, bool aligned16, int64_t n, int64_t P, int k, const RsvdPlan& sk,
+                               int64_t omega_rows, bool omega_on_device) {
+  return fit_first_eligible(keep_raw, prec_power, aligned16, n, P, sk.l) && k <= n && sk.l == sk.l_req && omega_rows >= n &&
+         !omega_on_device;
 }
 
 // ---- preprocessing statistics ----------------------------------------------------------------------------------------------
