@@ -1953,6 +1953,9 @@ static int launch_rinv_blocked(eofx_ctx* ctx, const double* G, int L, int l, dou
 }
 static int launch_rinv(eofx_ctx* ctx, const double* G, int L, int l, double* Rinv) {
   if (l <= 64) {
+    // the kernel stores one 64 x 64 block (inside launch_rinv_blocked its neighbours belong to other blocks): a wider Rinv is
+    // zeroed here -- "zero elsewhere" of eofx.h, and launch_matmul reads all L rows of it
+    if (L > 64) HIPCHK(hipMemsetAsync(Rinv, 0, sizeof(double) * (size_t)L * L, ctx->stream));
     hipLaunchKernelGGL(chol_rinv_kernel, dim3(1), dim3(256), 0, ctx->stream, G, L, l, Rinv, 1e-13, (const double*)nullptr);
     KCHK();
   } else if (ctx->arena_size - ctx->arena_off >= rinv_blocked_bytes(l) && !std::getenv("EOFX_HOST_RINV")) {
