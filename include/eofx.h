@@ -525,6 +525,24 @@ int eofx_lagcov_f64(eofx_ctx *ctx, const float *S, int64_t n, int p, int64_t ld,
  * h = 0 (w = [1]) gives Y = S.  EOFX_ERR_ARG unless n >= 2, 0 <= h <= n - 1 and p >= 1; EOFX_ERR_SHAPE for p > 1024.        */
 int eofx_lowpass_cov_f64(eofx_ctx *ctx, const float *S, int64_t n, int p, int64_t ld, const double *w, int h,
                          const double *trend, double *R, double *Y);
+/* ---- rank-order operator of trend EOF analysis (Hannachi 2007; xeofs_amd/single/trend_eof.py, csrc/eofx_orderpos.hpp) ----
+ * T [p x n]: a SERIES-MAJOR float32 device panel, row j the n samples of series j, row stride ld >= n.
+ *   Qi[j, r] (int32, device, row stride ldq >= n) = the 0-based time index of the r-th smallest value of series j, equal
+ *       values in ascending time: numpy.argsort(kind="stable") with -0.0 equal to +0.0 and every NaN last, in time order;
+ *   Zt[j, r] (float32, device, row stride ldz >= n) = (Qi[j, r] - (n - 1) / 2) * scale[j], the float64 product rounded once.
+ * scale [p] float64 (host|device), NULL for ones.  Either output may be NULL, not both.  One workgroup sorts a series in LDS
+ * as 64-bit (value image, time index) keys -- all different, so the result does not depend on the network and two runs are
+ * equal bit for bit; a series is read once and written once, nothing is written past column n of a row, no atomics.
+ * p == 0 is a no-op.  EOFX_ERR_ARG for n < 1, a stride below n or both outputs NULL; EOFX_ERR_SHAPE for n > 16384 (the
+ * keys of a series fill 128 KiB of LDS there).                                                                          */
+int eofx_orderpos_f32(eofx_ctx *ctx, const float *T, int64_t p, int64_t n, int64_t ld, const double *scale, int32_t *Qi,
+                      int64_t ldq, float *Zt, int64_t ldz);
+/* The same operator on a resident matrix: *out = a NEW resident matrix of the shape of m whose column j holds Zt[j, :] of
+ * column j of m.  The kernel reads the sample-contiguous layout of m where it lies (built on demand and kept: the caller may
+ * release it again) and writes the sample-contiguous layout of *out directly, zero padded; the feature-contiguous
+ * layout of *out is the tiled transpose of it.  No dense (n x p) intermediate.  scale [m.p] float64 (host|device) or NULL.
+ * EOFX_ERR_ARG for a masked in-place matrix (layout mode 3); EOFX_ERR_SHAPE for more than 16384 samples.               */
+int eofx_mat_orderpos_f32(eofx_ctx *ctx, const eofx_mat *m, const double *scale, eofx_mat **out);
 /* ---- PC-space product of principal oscillation pattern analysis (xeofs/single/pop.py:185-198, csrc/eofx_pcmul.hpp) ---
  * Y [rows x b] = X [rows x a] M [a x b]: X a device panel of float32 or float64 (x_dtype) with row stride ldx >= a, M
  * float64 row-major (host|device), Y a device panel of float64 or float32 (y_dtype) with row stride ldy >= b.  Accumulated

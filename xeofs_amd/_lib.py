@@ -120,7 +120,9 @@ SIGNATURES = {
     "eofx_spca_prox_f64": (_int, [_vp, _vp, _vp, C.c_double, _i64, _int, C.c_double, _vp]),
     "eofx_lagcov_f64": (_int, [_vp, _vp, _i64, _int, _i64, _vp, _int, _vp]),
     "eofx_lowpass_cov_f64": (_int, [_vp, _vp, _i64, _int, _i64, _vp, _int, _vp, _vp, _vp]),
-    "eofx_pcmul_f64": (_int, [_vp, _vp, _int, _i64, _int, _i64, _vp, _int, _vp, _int, _i64]),
+    "eofx_orderpos_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64]),
+    "eofx_mat_orderpos_f32": (_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
+    "eofx_pcmul_f64":(_int, [_vp, _vp, _int, _i64, _int, _i64, _vp, _int, _vp, _int, _i64]),
     "eofx_viewcov_f64": (_int, [_vp, _vp, _i64, _int, _i64, _vp, _vp, _int, _int, _vp, _i64]),
     "eofx_gapmask_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _pi64]),
     "eofx_lrfill_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _int, _vp]),

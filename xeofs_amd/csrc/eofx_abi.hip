@@ -14,6 +14,7 @@
 #include "eofx_spca.hpp"
 #include "eofx_lagcov.hpp"
 #include "eofx_lowpass.hpp"
+#include "eofx_orderpos.hpp"
 #include "eofx_pcmul.hpp"
 #include "eofx_viewcov.hpp"
 #include "eofx_lrfill.hpp"
@@ -5485,6 +5486,90 @@ extern "C" int eofx_lowpass_cov_f64(eofx_ctx* ctx, const float* S, int64_t n, in
     KCHK();
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));       // (the staged weights are a pageable host buffer; the arena is handed back)
+  return EOFX_OK;
+}
+
+// ---- rank-order operator of trend EOF analysis (csrc/eofx_orderpos.hpp) -------------------------------------------------
+// scale: NULL, or [p] float64 host|device (a host vector is staged in the arena, which the caller has reserved)
+static int launch_orderpos(eofx_ctx* ctx, const float* T, int64_t p, int64_t n, int64_t ld, const double* scale, int* Qi,
+                           int64_t ldq, float* Zt, int64_t ldz) {
+  const OrderposPlan pl = orderpos_plan(n);
+  const double* sd = scale;
+  if (scale && !is_device_ptr(scale)) {
+    double* st = arena_alloc<double>(ctx, (size_t)p);
+    if (!st) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (scale)");
+    HIPCHK(hipMemcpyAsync(st, scale, (size_t)p * 8, hipMemcpyHostToDevice, ctx->stream));
+    sd = st;
+  }
+  static int cu_count = 0;
+  if (cu_count <= 0) {
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, ctx->device));
+    cu_count = prop.multiProcessorCount;
+  }
+  HIPCHK(hipFuncSetAttribute((const void*)orderpos_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+  const int64_t groups = (p + pl.spb - 1) / pl.spb;
+  const unsigned grid = (unsigned)std::min<int64_t>(groups, (int64_t)cu_count * pl.per_cu);
+  hipLaunchKernelGGL(orderpos_kernel, dim3(grid), dim3(pl.threads), pl.lds, ctx->stream, T, p, (int)n, ld, sd, Qi, ldq, Zt, ldz,
+                     pl.m, pl.tps, pl.spb, pl.keys);
+  KCHK();
+  return EOFX_OK;
+}
+
+extern "C" int eofx_orderpos_f32(eofx_ctx* ctx, const float* T, int64_t p, int64_t n, int64_t ld, const double* scale,
+                                 int32_t* Qi, int64_t ldq, float* Zt, int64_t ldz) {
+  if (!ctx) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (!Qi && !Zt) return set_err(ctx, EOFX_ERR_ARG, "one of Qi and Zt must be given");
+  if (n < 1 || p < 0) return set_err(ctx, EOFX_ERR_ARG, "n must be >= 1 and p >= 0 (n = %lld, p = %lld)", (long long)n, (long long)p);
+  if (n > ORDERPOS_NMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the rank-order kernel sorts series of at most %d samples in LDS, got n = %lld", ORDERPOS_NMAX, (long long)n);
+  if (ld < n || (Qi && ldq < n) || (Zt && ldz < n))
+    return set_err(ctx, EOFX_ERR_ARG, "a row stride is below n = %lld (ld = %lld, ldq = %lld, ldz = %lld)", (long long)n, (long long)ld,
+                   (long long)ldq, (long long)ldz);
+  if (p == 0) return EOFX_OK;
+  if (!T || !is_device_ptr(T) || (Qi && !is_device_ptr(Qi)) || (Zt && !is_device_ptr(Zt)))
+    return set_err(ctx, EOFX_ERR_ARG, "T, Qi and Zt must be device buffers");
+  ENTER(ctx);
+  CHK(arena_reserve(ctx, (size_t)p * 8 + 256));
+  ArenaScope scope(ctx);
+  CHK(launch_orderpos(ctx, T, p, n, ld, scale, Qi, ldq, Zt, ldz));
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // (a staged scale is a pageable host buffer; the arena is handed back)
+  return EOFX_OK;
+}
+
+extern "C" int eofx_mat_orderpos_f32(eofx_ctx* ctx, const eofx_mat* m, const double* scale, eofx_mat** out) {
+  if (!ctx || !m || !out) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (m->masked) return set_err(ctx, EOFX_ERR_ARG, "the rank-order operator does not take a masked in-place matrix: compact it first");
+  if (m->n > ORDERPOS_NMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the rank-order kernel sorts series of at most %d samples in LDS, got n = %lld", ORDERPOS_NMAX, (long long)m->n);
+  ENTER(ctx);
+  CHK(ensure_Xt(ctx, m));
+  eofx_mat* z = nullptr;
+  CHK(mat_alloc(ctx, m->n, m->p, &z, false, true));
+  const auto run = [&]() -> int {
+    CHK(arena_reserve(ctx, (size_t)m->p * 8 + 256));
+    ArenaScope scope(ctx);
+    // the padding of the new layout: the samples n .. n_pad - 1 of every series, then the rows p .. p_pad - 1
+    if (z->n_pad > z->n)
+      HIPCHK(hipMemset2DAsync(z->Xt + z->n, (size_t)z->n_pad * sizeof(float), 0, (size_t)(z->n_pad - z->n) * sizeof(float), (size_t)z->p, ctx->stream));
+    if (z->p_pad > z->p)
+      HIPCHK(hipMemsetAsync(z->Xt + z->p * z->n_pad, 0, (size_t)(z->p_pad - z->p) * z->n_pad * sizeof(float), ctx->stream));
+    CHK(launch_orderpos(ctx, m->Xt, m->p, m->n, m->n_pad, scale, nullptr, 0, z->Xt, z->n_pad));
+    const int64_t total4 = z->n_pad * (z->p_pad / 4);
+    hipLaunchKernelGGL(panel_absmax_kernel, dim3((int)std::max<int64_t>(1, std::min<int64_t>((total4 + 1023) / 1024, 1024))), dim3(256), 0,
+                       ctx->stream, z->Xt, z->p_pad, (int)z->n_pad, z->n_pad, z->absmax_dev);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(&z->absmax, z->absmax_dev, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    CHK(ensure_X(ctx, z));                          // the feature-contiguous layout: the tiled transpose of the one just written
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return EOFX_OK;
+  };
+  const int rc = run();
+  if (rc != EOFX_OK) {
+    eofx_mat_destroy(ctx, z);
+    return rc;
+  }
+  *out = z;
   return EOFX_OK;
 }
 

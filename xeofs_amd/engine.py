@@ -1417,6 +1417,66 @@ def lowpass(ctx: Context, S, w, trend=None):
 
 
 # --------------------------------------------------------------------------- #
+# rank-order operator of trend EOF analysis (eofx_orderpos_f32, eofx_mat_orderpos_f32, csrc/eofx_orderpos.hpp)   #
+# --------------------------------------------------------------------------- #
+ORDERPOS_NMAX = 16384     # samples of a series the kernel sorts in LDS
+
+
+def _orderpos_scale(scale, p: int):
+    """the per-series factors as a float64 host vector or device tensor of p entries, or None"""
+    if scale is None:
+        return None
+    if hasattr(scale, "data_ptr"):
+        scale = scale.to(_torch().float64).contiguous()
+    else:
+        scale = np.ascontiguousarray(scale, dtype=np.float64)
+    if tuple(scale.shape) != (p,):
+        raise ValueError(f"scale must have one entry per series ({p}), got shape {tuple(scale.shape)}")
+    return scale
+
+
+def order_positions(ctx: Context, T, scale=None, want: str = "z", out=None):
+    """The inverse ranks of every row of the SERIES-MAJOR float32 panel T [p x n] -- a host array or a device tensor, whose row
+    stride may exceed n: q [p x n] (int32 device tensor), q[j, r] the 0-based time index of the r-th smallest value of
+    series j, equal values in ascending time (numpy.argsort(kind="stable"), -0.0 equal to +0.0, NaNs last), and
+    z [p x n] (float32 device tensor) = (q - (n - 1) / 2) * scale[j], the float64 product rounded once.  scale: [p] or None
+    (ones).  want: "z", "q" or "both" (-> (q, z)).  out: the device tensor to write (a pair for "both"), whose row stride
+    may exceed n."""
+    torch = _torch()
+    if want not in ("z", "q", "both"):
+        raise ValueError(f'want must be "z", "q" or "both", got {want!r}')
+    T = device_panel(ctx, T, "T", (torch.float32,))
+    p, n = T.shape
+    scale = _orderpos_scale(scale, p)
+    outs = (None, None) if out is None else (tuple(out) if want == "both" else ((out, None) if want == "q" else (None, out)))
+    if len(outs) != 2:
+        raise ValueError('out must be the pair (q, z) for want="both"')
+    q, z = outs
+    if want != "z":
+        q = (torch.empty((p, n), dtype=torch.int32, device=T.device) if q is None
+             else _check_out(q, p, n, (torch.int32,), "int32"))
+    if want != "q":
+        z = (torch.empty((p, n), dtype=torch.float32, device=T.device) if z is None
+             else _check_out(z, p, n, (torch.float32,), "float32"))
+    ld = lambda a: n if a is None else a.stride(0)
+    if p:       # (an empty tensor has no address to pass: p == 0 is a no-op of the entry as well)
+        raise_for(ctx.lib.eofx_orderpos_f32(ctx.handle, ptr(T), p, n, ld(T), ptr(scale), ptr(q), ld(q), ptr(z), ld(z)), ctx.handle)
+    return (q, z) if want == "both" else (q if want == "q" else z)
+
+
+def rank_matrix(ctx: Context, mat: ResidentMatrix, weights=None) -> ResidentMatrix:
+    """The resident matrix Z of `mat`: column j of Z = (the inverse ranks of column j of mat - (n - 1) / 2) * weights[j]
+    (order_positions along the samples of every feature).  Reads the sample-contiguous layout of `mat` where it lies (built on
+    demand; `mat.release_sample_layout()` drops it again) and writes the new matrix directly: no dense intermediate."""
+    if mat.masked:
+        raise ValueError("rank_matrix does not take a masked in-place matrix: compact it first")
+    weights = _orderpos_scale(weights, mat.p)
+    h = C.c_void_p()
+    raise_for(ctx.lib.eofx_mat_orderpos_f32(ctx.handle, mat.handle, ptr(weights), C.byref(h)), ctx.handle)
+    return ResidentMatrix(ctx, h)
+
+
+# --------------------------------------------------------------------------- #
 # PC-space product of principal oscillation pattern analysis (eofx_pcmul_f64, csrc/eofx_pcmul.hpp)   #
 # --------------------------------------------------------------------------- #
 PCMUL_AMAX = 1024         # inner length the kernel takes (the PCA modes)
