@@ -543,6 +543,25 @@ int eofx_orderpos_f32(eofx_ctx *ctx, const float *T, int64_t p, int64_t n, int64
  * layout of *out is the tiled transpose of it.  No dense (n x p) intermediate.  scale [m.p] float64 (host|device) or NULL.
  * EOFX_ERR_ARG for a masked in-place matrix (layout mode 3); EOFX_ERR_SHAPE for more than 16384 samples.               */
 int eofx_mat_orderpos_f32(eofx_ctx *ctx, const eofx_mat *m, const double *scale, eofx_mat **out);
+/* ---- quadratic-form operator of empirical orthogonal teleconnections (van den Dool et al. 2000; xeofs_amd/single/eot.py,
+ * csrc/eofx_colquad.hpp) ----
+ * T [p x n]: a SERIES-MAJOR float32 device panel, row j the n samples of series j, row stride ld >= n.
+ * A [n x n]: a float32 device matrix, row-major, row stride lda >= n -- ANY square matrix, no symmetry is assumed.
+ *   q[j] (float64, device, p entries) = sum_s sum_t T[j, s] A[s, t] T[j, t].
+ * Y = T_tile A is formed on the matrix cores with float32 operands and float32 accumulators (v_mfma_f32_32x32x2_f32: every
+ * Y[j, s] a float32 fma chain over t ascending) and never written; the accumulators are converted to float64, multiplied by
+ * T[j, s] in float64 and summed over s in float64.  Where the columns of A are shared among several workgroups their float64
+ * partials are added in ascending order by a second kernel.  No atomics: the grid and every order of summation are functions
+ * of (n, p) alone, so two runs are equal bit for bit.  q[j] depends on series j and on A only: a NaN or an infinity in one
+ * series reaches no other series' q.  Nothing but q[0 .. p) is written; T and A are read only, and nothing past column n of a
+ * row of either is read.
+ * p == 0 is a no-op.  EOFX_ERR_ARG for n < 1 or a stride below n; EOFX_ERR_SHAPE for n > 16384 (A is 1 GB there).          */
+int eofx_colquad_f32(eofx_ctx *ctx, const float *T, int64_t p, int64_t n, int64_t ld, const float *A, int64_t lda, double *q);
+/* The same operator on a resident matrix: series j = column j of m, n = the samples of m, q [m.p] float64 device.  The kernel
+ * reads the sample-contiguous layout of m where it lies (built on demand and kept: the caller may release it again); the
+ * field is read only.  EOFX_ERR_ARG for a masked in-place matrix (layout mode 3) or lda below the samples of m;
+ * EOFX_ERR_SHAPE for more than 16384 samples.                                                                           */
+int eofx_mat_colquad_f32(eofx_ctx *ctx, const eofx_mat *m, const float *A, int64_t lda, double *q);
 /* ---- PC-space product of principal oscillation pattern analysis (xeofs/single/pop.py:185-198, csrc/eofx_pcmul.hpp) ---
  * Y [rows x b] = X [rows x a] M [a x b]: X a device panel of float32 or float64 (x_dtype) with row stride ldx >= a, M
  * float64 row-major (host|device), Y a device panel of float64 or float32 (y_dtype) with row stride ldy >= b.  Accumulated

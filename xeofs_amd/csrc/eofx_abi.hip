@@ -15,6 +15,7 @@
 #include "eofx_lagcov.hpp"
 #include "eofx_lowpass.hpp"
 #include "eofx_orderpos.hpp"
+#include "eofx_colquad.hpp"
 #include "eofx_pcmul.hpp"
 #include "eofx_viewcov.hpp"
 #include "eofx_lrfill.hpp"
@@ -5570,6 +5571,64 @@ extern "C" int eofx_mat_orderpos_f32(eofx_ctx* ctx, const eofx_mat* m, const dou
     return rc;
   }
   *out = z;
+  return EOFX_OK;
+}
+
+// ---- quadratic-form operator of empirical orthogonal teleconnections (csrc/eofx_colquad.hpp) ---------------------------
+// q [p] float64 device.  The partials of a split grid live in the arena, which the caller has reserved.
+static int launch_colquad(eofx_ctx* ctx, const float* T, int64_t p, int64_t n, int64_t ld, const float* A, int64_t lda, double* q) {
+  const ColquadPlan pl = colquad_plan(n, p);
+  double* out = q;
+  if (pl.splits > 1) {
+    out = arena_alloc<double>(ctx, (size_t)pl.splits * (size_t)p);
+    if (!out) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (colquad partials)");
+  }
+  hipLaunchKernelGGL(colquad_kernel, dim3((unsigned)pl.row_tiles, (unsigned)pl.splits), dim3(256), 0, ctx->stream, T, p, (int)n, ld, A,
+                     lda, out, pl.col_blocks);
+  KCHK();
+  if (pl.splits > 1) {
+    hipLaunchKernelGGL(colquad_sum_kernel, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, out, pl.splits, p, q);
+    KCHK();
+  }
+  return EOFX_OK;
+}
+
+static size_t colquad_arena_bytes(int64_t n, int64_t p) { return (size_t)colquad_plan(n, p).splits * (size_t)p * 8 + 256; }
+
+extern "C" int eofx_colquad_f32(eofx_ctx* ctx, const float* T, int64_t p, int64_t n, int64_t ld, const float* A, int64_t lda,
+                                double* q) {
+  if (!ctx) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (n < 1 || p < 0) return set_err(ctx, EOFX_ERR_ARG, "n must be >= 1 and p >= 0 (n = %lld, p = %lld)", (long long)n, (long long)p);
+  if (n > COLQUAD_NMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the quadratic-form kernel takes series of at most %d samples, got n = %lld", COLQUAD_NMAX, (long long)n);
+  if (ld < n || lda < n)
+    return set_err(ctx, EOFX_ERR_ARG, "a row stride is below n = %lld (ld = %lld, lda = %lld)", (long long)n, (long long)ld, (long long)lda);
+  if (p == 0) return EOFX_OK;
+  if (!T || !A || !q || !is_device_ptr(T) || !is_device_ptr(A) || !is_device_ptr(q))
+    return set_err(ctx, EOFX_ERR_ARG, "T, A and q must be device buffers");
+  ENTER(ctx);
+  CHK(arena_reserve(ctx, colquad_arena_bytes(n, p)));
+  ArenaScope scope(ctx);
+  CHK(launch_colquad(ctx, T, p, n, ld, A, lda, q));
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // (the arena is handed back)
+  return EOFX_OK;
+}
+
+extern "C" int eofx_mat_colquad_f32(eofx_ctx* ctx, const eofx_mat* m, const float* A, int64_t lda, double* q) {
+  if (!ctx || !m) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (m->masked) return set_err(ctx, EOFX_ERR_ARG, "the quadratic-form operator does not take a masked in-place matrix: compact it first");
+  if (m->n < 1) return set_err(ctx, EOFX_ERR_ARG, "n must be >= 1 (n = %lld)", (long long)m->n);
+  if (m->n > COLQUAD_NMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the quadratic-form kernel takes series of at most %d samples, got n = %lld", COLQUAD_NMAX, (long long)m->n);
+  if (lda < m->n) return set_err(ctx, EOFX_ERR_ARG, "a row stride is below n = %lld (lda = %lld)", (long long)m->n, (long long)lda);
+  if (m->p == 0) return EOFX_OK;
+  if (!A || !q || !is_device_ptr(A) || !is_device_ptr(q)) return set_err(ctx, EOFX_ERR_ARG, "A and q must be device buffers");
+  ENTER(ctx);
+  CHK(ensure_Xt(ctx, m));
+  CHK(arena_reserve(ctx, colquad_arena_bytes(m->n, m->p)));
+  ArenaScope scope(ctx);
+  CHK(launch_colquad(ctx, m->Xt, m->p, m->n, m->n_pad, A, lda, q));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   return EOFX_OK;
 }
 

@@ -1477,6 +1477,51 @@ def rank_matrix(ctx: Context, mat: ResidentMatrix, weights=None) -> ResidentMatr
 
 
 # --------------------------------------------------------------------------- #
+# quadratic-form operator of empirical orthogonal teleconnections (eofx_colquad_f32, eofx_mat_colquad_f32, csrc/eofx_colquad.hpp) #
+# --------------------------------------------------------------------------- #
+COLQUAD_NMAX = 16384      # samples the kernel takes: A is 1 GB there
+
+
+def _colquad_operands(ctx: Context, A, n: int, p: int, out):
+    """A [n x n] as a float32 device tensor (strides honoured) and the float64 device vector of p entries to write"""
+    torch = _torch()
+    A = device_panel(ctx, A, "A", (torch.float32,))
+    if tuple(A.shape) != (n, n):
+        raise ValueError(f"A must be a square matrix of the {n} samples, got shape {tuple(A.shape)}")
+    if out is None:
+        out = torch.empty(p, dtype=torch.float64, device=A.device)
+    elif (not hasattr(out, "data_ptr") or tuple(out.shape) != (p,) or out.dtype != torch.float64 or not out.is_cuda
+          or (p > 1 and out.stride(0) != 1)):
+        raise ValueError(f"out must be a contiguous float64 device vector of {p} entries")
+    return A, out
+
+
+def colquad(ctx: Context, T, A, out=None):
+    """q[j] = sum_s sum_t T[j, s] A[s, t] T[j, t] for every row of the SERIES-MAJOR float32 panel T [p x n] and any square
+    float32 matrix A [n x n] -- host arrays or device tensors, whose row strides may exceed n.  -> a float64 device tensor of p
+    entries (`out` when given).  float32 products and fma chains on the matrix cores, float64 from there on; no atomics: two
+    calls are equal bit for bit, and q[j] depends on series j alone."""
+    torch = _torch()
+    T = device_panel(ctx, T, "T", (torch.float32,))
+    p, n = T.shape
+    A, out = _colquad_operands(ctx, A, n, p, out)
+    if p:       # (an empty tensor has no address to pass: p == 0 is a no-op of the entry as well)
+        raise_for(ctx.lib.eofx_colquad_f32(ctx.handle, ptr(T), p, n, T.stride(0), ptr(A), A.stride(0), ptr(out)), ctx.handle)
+    return out
+
+
+def mat_colquad(ctx: Context, mat: ResidentMatrix, A, out=None):
+    """colquad on the columns of a resident matrix: q[j] = x_j^T A x_j, x_j the n samples of feature j.  Reads the
+    sample-contiguous layout of `mat` where it lies (built on demand; `mat.release_sample_layout()` drops it again)."""
+    if mat.masked:
+        raise ValueError("mat_colquad does not take a masked in-place matrix: compact it first")
+    A, out = _colquad_operands(ctx, A, mat.n, mat.p, out)
+    if mat.p:
+        raise_for(ctx.lib.eofx_mat_colquad_f32(ctx.handle, mat.handle, ptr(A), A.stride(0), ptr(out)), ctx.handle)
+    return out
+
+
+# --------------------------------------------------------------------------- #
 # PC-space product of principal oscillation pattern analysis (eofx_pcmul_f64, csrc/eofx_pcmul.hpp)   #
 # --------------------------------------------------------------------------- #
 PCMUL_AMAX = 1024         # inner length the kernel takes (the PCA modes)
