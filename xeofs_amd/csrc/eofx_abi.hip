@@ -5384,53 +5384,84 @@ extern "C" int eofx_spca_prox_f64(eofx_ctx* ctx, const double* X, const double* 
   return EOFX_OK;
 }
 
+// ---- small operands that may lie on the host or on the device ---------------------------------------------------------
+// `count` entries (weights, offsets) into a host vector; a device operand costs one synchronisation
+template <class T>
+static int fetch_small(eofx_ctx* ctx, const T* src, size_t count, std::vector<T>& out) {
+  out.resize(count);
+  if (is_device_ptr(src)) {
+    HIPCHK(hipMemcpyAsync(out.data(), src, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  } else {
+    std::copy(src, src + count, out.begin());
+  }
+  return EOFX_OK;
+}
+// `count` entries where a kernel can read them -> *dev: a device operand where it lies; one `on_host` (a buffer of the entry's
+// own, or !is_device_ptr of the caller's) copied into the arena (reserved by the caller; `what` names it in the error).  The
+// hazard, for every entry that stages: the source may be a pageable host buffer that the asynchronous copy still reads when
+// the call returns, and the arena is handed back when the entry leaves its scope.  So an entry that staged an operand
+// `on_host` synchronises the stream before it returns.
+template <class T>
+static int stage_small(eofx_ctx* ctx, const T* src, size_t count, const char* what, bool on_host, const T** dev) {
+  *dev = src;
+  if (!on_host) return EOFX_OK;
+  T* st = arena_alloc<T>(ctx, count);
+  if (!st) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (%s)", what);
+  HIPCHK(hipMemcpyAsync(st, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+  *dev = st;
+  return EOFX_OK;
+}
+// out [count] = the sum of the G partials part [G x count], in a fixed order
+static int reduce_partials(eofx_ctx* ctx, const double* part, int G, size_t count, double* out) {
+  hipLaunchKernelGGL(f64_reduce_kernel, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, ctx->stream, part, out, (int64_t)count, G);
+  KCHK();
+  return EOFX_OK;
+}
+
+// ---- the filter covariances: the checks on the panel (`noun` names the kernels) and the grid of a written-panel filter ----
+static int filter_check(eofx_ctx* ctx, int64_t n, int p, int64_t ld, const char* noun) {
+  if (n < 2 || ld < p) return set_err(ctx, EOFX_ERR_ARG, "n must be >= 2 and ld >= p (n = %lld, p = %d, ld = %lld)", (long long)n, p, (long long)ld);
+  if (p < 1) return set_err(ctx, EOFX_ERR_ARG, "p must be >= 1, got %d", p);
+  if (p > LAGCOV_PMAX) return set_err(ctx, EOFX_ERR_SHAPE, "the %s covariance kernels take p <= %d, got %d", noun, LAGCOV_PMAX, p);
+  return EOFX_OK;
+}
+static dim3 fir_grid(int64_t n, int p) { return dim3((unsigned)(((n + FIR_WIN - 1) / FIR_WIN * p + 255) / 256)); }
+
 // ---- lag-summed covariance of optimal persistence analysis (csrc/eofx_lagcov.hpp) --------------------------------------
 extern "C" int eofx_lagcov_f64(eofx_ctx* ctx, const float* S, int64_t n, int p, int64_t ld, const double* w, int ntau, double* M) {
   if (!ctx || !S || !w || !M) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
-  if (n < 2 || ld < p) return set_err(ctx, EOFX_ERR_ARG, "n must be >= 2 and ld >= p (n = %lld, p = %d, ld = %lld)", (long long)n, p, (long long)ld);
-  if (p < 1) return set_err(ctx, EOFX_ERR_ARG, "p must be >= 1, got %d", p);
-  if (p > LAGCOV_PMAX) return set_err(ctx, EOFX_ERR_SHAPE, "the lag covariance kernels take p <= %d, got %d", LAGCOV_PMAX, p);
+  CHK(filter_check(ctx, n, p, ld, "lag"));
   if (ntau < 1 || (int64_t)ntau > n - 1)
     return set_err(ctx, EOFX_ERR_ARG, "ntau must be in [1, n - 1 = %lld] (the largest lag leaves two samples), got %d", (long long)(n - 1), ntau);
   if (!is_device_ptr(S) || !is_device_ptr(M)) return set_err(ctx, EOFX_ERR_ARG, "S and M must be device buffers");
   ENTER(ctx);
   const bool fused = ntau <= LAGCOV_FUSE_NTAU;
-  std::vector<double> wh((size_t)ntau);
-  if (is_device_ptr(w)) {
-    HIPCHK(hipMemcpyAsync(wh.data(), w, wh.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  } else {
-    std::copy(w, w + ntau, wh.begin());
-  }
+  std::vector<double> wh;
+  CHK(fetch_small(ctx, w, (size_t)ntau, wh));
   const FilterPlan pl = lagcov_plan(n, p, wh.data(), ntau);       // the zero-padded copy of the weights (host)
   const int ny = pl.ny, G = pl.G;
   const size_t nw = pl.w.size(), pp = (size_t)p * p;
   CHK(arena_reserve(ctx, (nw + pp * G + (fused ? 0 : (size_t)n * p)) * 8 + 3 * 256));
   ArenaScope scope(ctx);
-  ARENA(double, wpad, nw);
+  const double* wpad = nullptr;
+  CHK(stage_small(ctx, pl.w.data(), nw, "wpad", true, &wpad));
   ARENA(double, part, pp * G);
-  double* Y = nullptr;
-  HIPCHK(hipMemcpyAsync(wpad, pl.w.data(), nw * 8, hipMemcpyHostToDevice, ctx->stream));
   if (fused) {
     const size_t lds = LAGCOV_LDS_Y + LAGCOV_LDS_S;
     HIPCHK(hipFuncSetAttribute((const void*)lagcov_cross_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(lagcov_cross_kernel<true>, dim3((unsigned)G, (unsigned)ny), dim3(256), lds, ctx->stream, S, n, p, ld,
-                       (const double*)wpad, ntau, (const double*)nullptr, part);
+    hipLaunchKernelGGL(lagcov_cross_kernel<true>, dim3((unsigned)G, (unsigned)ny), dim3(256), lds, ctx->stream, S, n, p, ld, wpad,
+                       ntau, (const double*)nullptr, part);
   } else {
-    Y = arena_alloc<double>(ctx, (size_t)n * p);
-    if (!Y) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (Y)");
-    const int64_t threads = (n + LAGCOV_WIN - 1) / LAGCOV_WIN * p;
-    hipLaunchKernelGGL(lagcov_fir_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, S, n, p, ld,
-                       (const double*)wpad, ntau, Y);
+    ARENA(double, Y, (size_t)n * p);
+    hipLaunchKernelGGL(lagcov_fir_kernel, fir_grid(n, p), dim3(256), 0, ctx->stream, S, n, p, ld, wpad, ntau, Y);
     KCHK();
     hipLaunchKernelGGL(lagcov_cross_kernel<false>, dim3((unsigned)G, (unsigned)ny), dim3(256), LAGCOV_LDS_Y, ctx->stream, S, n, p,
-                       ld, (const double*)wpad, ntau, (const double*)Y, part);
+                       ld, wpad, ntau, (const double*)Y, part);
   }
   KCHK();
-  hipLaunchKernelGGL(f64_reduce_kernel, dim3((unsigned)((pp + 63) / 64)), dim3(256), 0, ctx->stream, (const double*)part, M,
-                     (int64_t)pp, G);
-  KCHK();
-  HIPCHK(hipStreamSynchronize(ctx->stream));       // (the staged weights are a pageable host buffer; the arena is handed back)
+  CHK(reduce_partials(ctx, part, G, pp, M));
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // (stage_small)
   return EOFX_OK;
 }
 
@@ -5438,43 +5469,28 @@ extern "C" int eofx_lagcov_f64(eofx_ctx* ctx, const float* S, int64_t n, int p, 
 extern "C" int eofx_lowpass_cov_f64(eofx_ctx* ctx, const float* S, int64_t n, int p, int64_t ld, const double* w, int h,
                                     const double* trend, double* R, double* Y) {
   if (!ctx || !S || !w || (!R && !Y)) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
-  if (n < 2 || ld < p) return set_err(ctx, EOFX_ERR_ARG, "n must be >= 2 and ld >= p (n = %lld, p = %d, ld = %lld)", (long long)n, p, (long long)ld);
-  if (p < 1) return set_err(ctx, EOFX_ERR_ARG, "p must be >= 1, got %d", p);
-  if (p > LAGCOV_PMAX) return set_err(ctx, EOFX_ERR_SHAPE, "the low-pass covariance kernels take p <= %d, got %d", LAGCOV_PMAX, p);
+  CHK(filter_check(ctx, n, p, ld, "low-pass"));
   if (h < 0 || (int64_t)h > n - 1)
     return set_err(ctx, EOFX_ERR_ARG, "h must be in [0, n - 1 = %lld] (one reflection about either end), got %d", (long long)(n - 1), h);
   if (!is_device_ptr(S) || (R && !is_device_ptr(R)) || (Y && !is_device_ptr(Y))) return set_err(ctx, EOFX_ERR_ARG, "S, R and Y must be device buffers");
   ENTER(ctx);
-  // the symmetric, zero-padded copy of the weights (host)
-  std::vector<double> wh((size_t)h + 1);
-  if (is_device_ptr(w)) {
-    HIPCHK(hipMemcpyAsync(wh.data(), w, wh.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  } else {
-    std::copy(w, w + h + 1, wh.begin());
-  }
-  const FilterPlan pl = lowpass_plan(n, p, wh.data(), h);
+  std::vector<double> wh;
+  CHK(fetch_small(ctx, w, (size_t)h + 1, wh));
+  const FilterPlan pl = lowpass_plan(n, p, wh.data(), h);         // the symmetric, zero-padded copy of the weights (host)
   const int ny = pl.ny, G = pl.G;
   const size_t nw = pl.w.size(), pp = (size_t)p * p;
   const bool own_y = !Y;                           // a caller who wants R alone: Y lives in the arena
   CHK(arena_reserve(ctx, (nw + (trend ? 2 * (size_t)p : 0) + (R ? pp * G : 0) + (own_y ? (size_t)n * p : 0)) * 8 + 4 * 256));
   ArenaScope scope(ctx);
-  ARENA(double, wsym, nw);
-  HIPCHK(hipMemcpyAsync(wsym, pl.w.data(), nw * 8, hipMemcpyHostToDevice, ctx->stream));
-  double* td = nullptr;
-  if (trend) {
-    td = arena_alloc<double>(ctx, 2 * (size_t)p);
-    if (!td) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (trend)");
-    HIPCHK(hipMemcpyAsync(td, trend, 2 * (size_t)p * 8, is_device_ptr(trend) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-  }
+  const double *wsym = nullptr, *td = nullptr;
+  CHK(stage_small(ctx, pl.w.data(), nw, "wsym", true, &wsym));
+  if (trend) CHK(stage_small(ctx, trend, 2 * (size_t)p, "trend", !is_device_ptr(trend), &td));
   double* Yd = Y;
   if (own_y) {
     Yd = arena_alloc<double>(ctx, (size_t)n * p);
     if (!Yd) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (Y)");
   }
-  const int64_t threads = (n + LOWPASS_WIN - 1) / LOWPASS_WIN * p;
-  hipLaunchKernelGGL(lowpass_fir_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, S, n, p, ld,
-                     (const double*)wsym, h, (const double*)td, Yd);
+  hipLaunchKernelGGL(lowpass_fir_kernel, fir_grid(n, p), dim3(256), 0, ctx->stream, S, n, p, ld, wsym, h, td, Yd);
   KCHK();
   if (R) {
     ARENA(double, part, pp * G);
@@ -5482,26 +5498,19 @@ extern "C" int eofx_lowpass_cov_f64(eofx_ctx* ctx, const float* S, int64_t n, in
     hipLaunchKernelGGL(lowpass_gram_kernel, dim3((unsigned)G, (unsigned)ny), dim3(256), LOWPASS_LDS_Y, ctx->stream,
                        (const double*)Yd, n, p, part);
     KCHK();
-    hipLaunchKernelGGL(f64_reduce_kernel, dim3((unsigned)((pp + 63) / 64)), dim3(256), 0, ctx->stream, (const double*)part, R,
-                       (int64_t)pp, G);
-    KCHK();
+    CHK(reduce_partials(ctx, part, G, pp, R));
   }
-  HIPCHK(hipStreamSynchronize(ctx->stream));       // (the staged weights are a pageable host buffer; the arena is handed back)
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // (stage_small)
   return EOFX_OK;
 }
 
 // ---- rank-order operator of trend EOF analysis (csrc/eofx_orderpos.hpp) -------------------------------------------------
-// scale: NULL, or [p] float64 host|device (a host vector is staged in the arena, which the caller has reserved)
+// scale: NULL, or [p] float64 host|device (stage_small: the caller has reserved the arena and synchronises before it returns)
 static int launch_orderpos(eofx_ctx* ctx, const float* T, int64_t p, int64_t n, int64_t ld, const double* scale, int* Qi,
                            int64_t ldq, float* Zt, int64_t ldz) {
   const OrderposPlan pl = orderpos_plan(n);
-  const double* sd = scale;
-  if (scale && !is_device_ptr(scale)) {
-    double* st = arena_alloc<double>(ctx, (size_t)p);
-    if (!st) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (scale)");
-    HIPCHK(hipMemcpyAsync(st, scale, (size_t)p * 8, hipMemcpyHostToDevice, ctx->stream));
-    sd = st;
-  }
+  const double* sd = nullptr;
+  if (scale) CHK(stage_small(ctx, scale, (size_t)p, "scale", !is_device_ptr(scale), &sd));
   static int cu_count = 0;
   if (cu_count <= 0) {
     hipDeviceProp_t prop;
@@ -5534,7 +5543,7 @@ extern "C" int eofx_orderpos_f32(eofx_ctx* ctx, const float* T, int64_t p, int64
   CHK(arena_reserve(ctx, (size_t)p * 8 + 256));
   ArenaScope scope(ctx);
   CHK(launch_orderpos(ctx, T, p, n, ld, scale, Qi, ldq, Zt, ldz));
-  HIPCHK(hipStreamSynchronize(ctx->stream));       // (a staged scale is a pageable host buffer; the arena is handed back)
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // (stage_small)
   return EOFX_OK;
 }
 
@@ -5656,14 +5665,10 @@ extern "C" int eofx_pcmul_f64(eofx_ctx* ctx, const void* X, int x_dtype, int64_t
   ENTER(ctx);
   const bool host_m = !is_device_ptr(M);
   ArenaScope scope(ctx);
-  const double* Md = M;
-  if (host_m) {
-    const size_t ab = (size_t)a * b;
-    CHK(arena_reserve(ctx, ab * 8 + 256));
-    ARENA(double, Mc, ab);
-    HIPCHK(hipMemcpyAsync(Mc, M, ab * 8, hipMemcpyHostToDevice, ctx->stream));
-    Md = Mc;
-  }
+  const size_t ab = (size_t)a * b;
+  if (host_m) CHK(arena_reserve(ctx, ab * 8 + 256));
+  const double* Md = nullptr;
+  CHK(stage_small(ctx, M, ab, "Mc", host_m, &Md));
   if (x_dtype == EOFX_PCMUL_F32) {
     if (y_dtype == EOFX_PCMUL_F32) launch_pcmul<float, float>(ctx, X, rows, a, ldx, Md, b, Y, ldy);
     else launch_pcmul<float, double>(ctx, X, rows, a, ldx, Md, b, Y, ldy);
@@ -5672,7 +5677,7 @@ extern "C" int eofx_pcmul_f64(eofx_ctx* ctx, const void* X, int x_dtype, int64_t
     else launch_pcmul<double, double>(ctx, X, rows, a, ldx, Md, b, Y, ldy);
   }
   KCHK();
-  if (host_m) HIPCHK(hipStreamSynchronize(ctx->stream));       // (M may be a pageable host buffer; the arena is handed back)
+  if (host_m) HIPCHK(hipStreamSynchronize(ctx->stream));       // (stage_small; a device M returns without one)
   return EOFX_OK;
 }
 
@@ -5690,13 +5695,8 @@ extern "C" int eofx_viewcov_f64(eofx_ctx* ctx, const float* Z, int64_t n, int p,
   if (!is_device_ptr(Z) || !is_device_ptr(C) || (mean && !is_device_ptr(mean)))
     return set_err(ctx, EOFX_ERR_ARG, "Z, mean and C must be device buffers");
   ENTER(ctx);
-  std::vector<int> offh((size_t)m + 1);
-  if (is_device_ptr(off)) {
-    HIPCHK(hipMemcpyAsync(offh.data(), off, offh.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  } else {
-    std::copy(off, off + m + 1, offh.begin());
-  }
+  std::vector<int> offh;
+  CHK(fetch_small(ctx, off, (size_t)m + 1, offh));
   ViewcovPlan pl;      // the view of every column, the tiles that hold a wanted output, the split of the samples
   int v = 0;
   const int bad = viewcov_plan(n, p, offh.data(), m, keep_diag != 0, pl, &v);
@@ -5710,13 +5710,13 @@ extern "C" int eofx_viewcov_f64(eofx_ctx* ctx, const float* Z, int64_t n, int p,
   const size_t npart = split ? (size_t)ntiles * G * VIEWCOV_TT : 0;
   CHK(arena_reserve(ctx, host.size() * sizeof(int) + npart * 8 + 2 * 256));
   ArenaScope scope(ctx);
-  ARENA(int, dev, host.size());
+  const int* dev = nullptr;
+  CHK(stage_small(ctx, host.data(), host.size(), "dev", true, &dev));
   double* part = nullptr;
   if (split) {
     part = arena_alloc<double>(ctx, npart);
     if (!part) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (part)");
   }
-  HIPCHK(hipMemcpyAsync(dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   const int* view = dev;
   const int* tiles = dev + p;
   hipLaunchKernelGGL(viewcov_zero_kernel, dim3((unsigned)((p + 255) / 256), (unsigned)p), dim3(256), 0, ctx->stream, C, p, ldc);
@@ -5734,7 +5734,7 @@ extern "C" int eofx_viewcov_f64(eofx_ctx* ctx, const float* Z, int64_t n, int p,
     }
     KCHK();
   }
-  HIPCHK(hipStreamSynchronize(ctx->stream));       // (the staged lists are a pageable host buffer; the arena is handed back)
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // (stage_small)
   return EOFX_OK;
 }
 

@@ -17,6 +17,7 @@
 // Both filters slide a window of 16 outputs per thread along the samples: one read of S feeds 16 fused multiply-adds, and
 // every Y[t, j] is summed over tau ascending.  The weights are read from a copy padded with 15 zeros on either side
 // (wpad[15 + tau] = w[tau]), so the window needs no bounds test; the products with the padding are exact zeros.
+// The low-pass covariance (eofx_lowpass.hpp) is built from the same fir16, fir_thread, fir_store and fir_stage_tile.
 // Float64 throughout, no atomics, the grid a function of the shape alone: two runs are equal bit for bit.  gfx950 only.
 #pragma once
 #include "eofx.h"
@@ -24,39 +25,62 @@
 
 namespace eofx {
 
-constexpr int LAGCOV_SROWS = LAGCOV_R + LAGCOV_FUSE_NTAU - 1;      // 128 staged rows of 64 float32
-constexpr int LAGCOV_YLD = 80;           // row stride of the Y tile in doubles: rows 4 s + lk, lk = 0, 1 on disjoint banks
-constexpr size_t LAGCOV_LDS_Y = (size_t)LAGCOV_R * LAGCOV_YLD * sizeof(double);
+constexpr int LAGCOV_SROWS = FIR_R + LAGCOV_FUSE_NTAU - 1;         // 128 staged rows of 64 float32
+constexpr size_t LAGCOV_LDS_Y = (size_t)FIR_R * MFMA64_TILE_LD * sizeof(double);
 constexpr size_t LAGCOV_LDS_S = (size_t)LAGCOV_SROWS * 64 * sizeof(float);
 
-// acc[a] = sum_tau w[tau] s(a + tau) for the 16 outputs a of a window, load(u) = s(u), u < ntau + 15.
-// Output a sees s(u) with weight wpad[15 + u - a]: w[u - a] inside 0 <= u - a < ntau, an exact zero outside.
+// acc[a] = sum_{i < taps} wpad[15 + i] s(a + i) for the 16 outputs a of a window, load(u) = s(u), u < taps + 15, summed over
+// u ascending.  Output a sees s(u) with weight wpad[15 + u - a]: a weight inside 0 <= u - a < taps, an exact zero outside.
 template <class Load>
-__device__ __forceinline__ void lagcov_fir16(Load load, const double* __restrict__ wpad, int ntau, double (&acc)[LAGCOV_WIN]) {
+__device__ __forceinline__ void fir16(Load load, const double* __restrict__ wpad, int taps, double (&acc)[FIR_WIN]) {
 #pragma unroll
-  for (int a = 0; a < LAGCOV_WIN; ++a) acc[a] = 0.0;
+  for (int a = 0; a < FIR_WIN; ++a) acc[a] = 0.0;
 #pragma unroll 4
-  for (int u = 0; u < ntau + LAGCOV_PADW; ++u) {
+  for (int u = 0; u < taps + FIR_PADW; ++u) {
     const double s = load(u);
-    const double* wu = wpad + LAGCOV_PADW + u;          // (wave-uniform: scalar loads)
+    const double* wu = wpad + FIR_PADW + u;             // (wave-uniform: scalar loads)
 #pragma unroll
-    for (int a = 0; a < LAGCOV_WIN; ++a) acc[a] = fma(wu[-a], s, acc[a]);
+    for (int a = 0; a < FIR_WIN; ++a) acc[a] = fma(wu[-a], s, acc[a]);
   }
 }
 
-// grid ceil(ceil(n / 16) p / 256), block 256: thread (window g, column j) writes Y[16 g .. 16 g + 15][j] (Y [n x p], tight)
-__global__ __launch_bounds__(256) void lagcov_fir_kernel(const float* __restrict__ S, int64_t n, int p, int64_t ld,
-                                                          const double* __restrict__ wpad, int ntau, double* __restrict__ Y) {
+// A written-panel filter runs on a grid ceil(ceil(n / 16) p / 256), block 256: thread (window g, column j) owns the outputs
+// Y[t0 .. t0 + 15][j], t0 = 16 g, of the tight panel Y [n x p] (none where t0 >= n) and stores Y[t0 + a][j] = value(a, t0 + a).
+struct FirThread {
+  int64_t t0;
+  int j;
+};
+__device__ __forceinline__ FirThread fir_thread(int p) {
   const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t g = id / p;
-  const int j = (int)(id - g * p);
-  const int64_t t0 = g * LAGCOV_WIN;
-  if (t0 >= n) return;
-  double acc[LAGCOV_WIN];
-  lagcov_fir16([&](int u) { const int64_t t = t0 + u; return t < n ? (double)S[t * ld + j] : 0.0; }, wpad, ntau, acc);
+  return {g * FIR_WIN, (int)(id - g * p)};
+}
+template <class Value>
+__device__ __forceinline__ void fir_store(double* __restrict__ Y, int64_t n, int p, FirThread th, Value value) {
 #pragma unroll
-  for (int a = 0; a < LAGCOV_WIN; ++a)
-    if (t0 + a < n) Y[(t0 + a) * p + j] = acc[a];
+  for (int a = 0; a < FIR_WIN; ++a) {
+    const int64_t t = th.t0 + a;
+    if (t < n) Y[t * p + th.j] = value(a, t);
+  }
+}
+
+// the 64 x 64 tile at rows r0 .. r0 + 63 of column block b of the tight panel Y [n x p] into dst [64][MFMA64_TILE_LD] (LDS),
+// by the 256 threads of a workgroup; rows past n and columns past p are exact zeros
+__device__ __forceinline__ void fir_stage_tile(const double* __restrict__ Y, int64_t n, int p, int b, int64_t r0, double* dst) {
+  for (int e = threadIdx.x; e < FIR_R * 64; e += 256) {
+    const int64_t t = r0 + (e >> 6);
+    const int gj = 64 * b + (e & 63);
+    dst[(e >> 6) * MFMA64_TILE_LD + (e & 63)] = (t < n && gj < p) ? Y[t * p + gj] : 0.0;
+  }
+}
+
+__global__ __launch_bounds__(256) void lagcov_fir_kernel(const float* __restrict__ S, int64_t n, int p, int64_t ld,
+                                                          const double* __restrict__ wpad, int ntau, double* __restrict__ Y) {
+  const FirThread th = fir_thread(p);
+  if (th.t0 >= n) return;
+  double acc[FIR_WIN];
+  fir16([&](int u) { const int64_t t = th.t0 + u; return t < n ? (double)S[t * ld + th.j] : 0.0; }, wpad, ntau, acc);
+  fir_store(Y, n, p, th, [&](int a, int64_t) { return acc[a]; });
 }
 
 // grid (G, nb * ceil(nb / 4)), nb = ceil(p / 64), block 256, dynamic LDS LAGCOV_LDS_Y (+ LAGCOV_LDS_S when FUSED).
@@ -67,20 +91,20 @@ __global__ __launch_bounds__(256, 2) void lagcov_cross_kernel(const float* __res
                                                               const double* __restrict__ wpad, int ntau,
                                                               const double* __restrict__ Y, double* __restrict__ part) {
   extern __shared__ double lagcov_lds[];
-  double* Ys = lagcov_lds;                                                    // [64][LAGCOV_YLD]
-  float* Sh = reinterpret_cast<float*>(lagcov_lds + LAGCOV_R * LAGCOV_YLD);   // [LAGCOV_SROWS][64] (FUSED)
+  double* Ys = lagcov_lds;                                                    // [64][MFMA64_TILE_LD]
+  float* Sh = reinterpret_cast<float*>(lagcov_lds + FIR_R * MFMA64_TILE_LD);   // [LAGCOV_SROWS][64] (FUSED)
   const int nb = (p + 63) / 64;
   const int bj = blockIdx.y % nb, bi = 4 * (blockIdx.y / nb) + (threadIdx.x >> 6);
   const Mfma64Lane ln = mfma64_lane();
   const int lc = ln.c, lk = ln.k;
-  const int64_t ntiles = (n + LAGCOV_R - 1) / LAGCOV_R;
+  const int64_t ntiles = (n + FIR_R - 1) / FIR_R;
   f64x4 acc[4][4];
   mfma64_zero(acc);
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t r0 = tile * LAGCOV_R;
+    const int64_t r0 = tile * FIR_R;
     // this wave's rows of S, eight k-steps at a time: the first half is in flight while the tile of Y is made, the second
     // while the products of the first issue (all sixteen at once spill next to the accumulators)
-    constexpr int H = LAGCOV_R / 8;
+    constexpr int H = FIR_R / 8;
     float av[2][H][4];
     auto fetch = [&](int h) {
 #pragma unroll
@@ -94,7 +118,7 @@ __global__ __launch_bounds__(256, 2) void lagcov_cross_kernel(const float* __res
     };
     fetch(0);
     if constexpr (FUSED) {
-      const int srows = LAGCOV_R + ntau - 1;       // the tile and its halo (<= LAGCOV_SROWS): all the windows read; past n: zeros
+      const int srows = FIR_R + ntau - 1;       // the tile and its halo (<= LAGCOV_SROWS): all the windows read; past n: zeros
       for (int e = threadIdx.x; e < srows * 64; e += 256) {
         const int64_t t = r0 + (e >> 6);
         const int gj = 64 * bj + (e & 63);
@@ -102,16 +126,12 @@ __global__ __launch_bounds__(256, 2) void lagcov_cross_kernel(const float* __res
       }
       __syncthreads();
       const int j = threadIdx.x & 63, g = threadIdx.x >> 6;
-      double y[LAGCOV_WIN];
-      lagcov_fir16([&](int u) { return (double)Sh[(LAGCOV_WIN * g + u) * 64 + j]; }, wpad, ntau, y);
+      double y[FIR_WIN];
+      fir16([&](int u) { return (double)Sh[(FIR_WIN * g + u) * 64 + j]; }, wpad, ntau, y);
 #pragma unroll
-      for (int a = 0; a < LAGCOV_WIN; ++a) Ys[(LAGCOV_WIN * g + a) * LAGCOV_YLD + j] = y[a];
+      for (int a = 0; a < FIR_WIN; ++a) Ys[(FIR_WIN * g + a) * MFMA64_TILE_LD + j] = y[a];
     } else {
-      for (int e = threadIdx.x; e < LAGCOV_R * 64; e += 256) {
-        const int64_t t = r0 + (e >> 6);
-        const int gj = 64 * bj + (e & 63);
-        Ys[(e >> 6) * LAGCOV_YLD + (e & 63)] = (t < n && gj < p) ? Y[t * p + gj] : 0.0;
-      }
+      fir_stage_tile(Y, n, p, bj, r0, Ys);
     }
     __syncthreads();
     if (bi < nb) {
@@ -124,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void lagcov_cross_kernel(const float* __res
 #pragma unroll
           for (int x = 0; x < 4; ++x) a[x] = (double)av[h][s][x];
 #pragma unroll
-          for (int y = 0; y < 4; ++y) b[y] = Ys[(4 * (H * h + s) + lk) * LAGCOV_YLD + 16 * y + lc];
+          for (int y = 0; y < 4; ++y) b[y] = Ys[(4 * (H * h + s) + lk) * MFMA64_TILE_LD + 16 * y + lc];
           mfma64_step(acc, a, b, Mfma64All{});
         }
     }

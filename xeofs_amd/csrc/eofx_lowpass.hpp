@@ -5,14 +5,14 @@
 //
 // (S [n x p] float32; w [h + 1], the trend [2 x p], Y and R float64), refl the mirror of an index about the first and the
 // last sample: refl(u) = -u below 0, 2 (n - 1) - u above n - 1.  h <= n - 1, so one reflection lands inside.
-//   lowpass_fir_kernel    Y [n x p] float64, written once.  A thread slides a window of 16 outputs along the samples as the
-//                         lag covariance does (eofx_lagcov.hpp): one read of S feeds 16 fused multiply-adds, the weights
+//   lowpass_fir_kernel    Y [n x p] float64, written once.  A thread slides the window of 16 outputs of the lag covariance
+//                         along the samples (fir16, eofx_lagcov.hpp): one read of S feeds 16 fused multiply-adds, the weights
 //                         are read from the symmetric copy wsym[15 + h + k] = w[|k|] padded with 15 zeros on either side
 //                         (no bounds test; the products with the padding are exact zeros), and every Y[t, j] is summed
 //                         over k ascending from -h.
 //   lowpass_gram_kernel   R = Y^T Y of the written panel: one workgroup per row group and PAIR (bi, bj), bi <= bj, of
-//                         64-column blocks of Y.  Per row tile of 64 samples the two tiles of Y are staged in LDS (one when
-//                         bi == bj); wave w owns rows 16 w .. 16 w + 15 of the 64 x 64 block: four accumulators on the fp64
+//                         64-column blocks of Y.  Per row tile of 64 samples the two tiles of Y are staged in LDS
+//                         (fir_stage_tile; one when bi == bj); wave w owns rows 16 w .. 16 w + 15 of the 64 x 64 block: four accumulators on the fp64
 //                         matrix cores (eofx_mfma64.hpp); on a diagonal pair the 16 x 16 blocks below the diagonal are
 //                         skipped.  A workgroup walks its row tiles in ascending order and writes one partial, every
 //                         value with gi <= gj together with its mirror image from the same register; f64_reduce_kernel
@@ -20,8 +20,7 @@
 // A route that filtered the tiles in LDS (Y never written) was built and measured slower at every shape: both operands of
 // Y^T Y are filtered tiles, so every pair of column blocks repeats the filter of its two blocks, and the 2 h + 1 multiply-adds
 // per entry cost more than the one write and read of Y they save (docs/EXPERIMENTS.md).
-// LDS of the Gram kernel: 2 x 64 x 80 doubles = 80 KiB (row stride 80: rows k and k + 1 on disjoint halves of the banks, as
-// LAGCOV_YLD): two workgroups of four waves fit the 160 KiB of a CU.
+// LDS of the Gram kernel: 2 x 64 x MFMA64_TILE_LD doubles = 80 KiB: two workgroups of four waves fit the 160 KiB of a CU.
 // Float64 throughout, no atomics, the grid a function of the shape alone: two runs are equal bit for bit.  gfx950 only.
 #pragma once
 #include "eofx.h"
@@ -30,8 +29,7 @@
 
 namespace eofx {
 
-constexpr int LOWPASS_YLD = LAGCOV_YLD;   // row stride of a Y tile in doubles
-constexpr size_t LOWPASS_LDS_Y = (size_t)2 * LOWPASS_R * LOWPASS_YLD * sizeof(double);
+constexpr size_t LOWPASS_LDS_Y = (size_t)2 * FIR_R * MFMA64_TILE_LD * sizeof(double);
 
 // the mirrored sample of u, or -1 where one reflection does not land in 0 .. n - 1 (rows no stored output reads)
 __device__ __forceinline__ int64_t lowpass_refl(int64_t u, int64_t n) {
@@ -40,46 +38,24 @@ __device__ __forceinline__ int64_t lowpass_refl(int64_t u, int64_t n) {
   return (u >= 0 && u < n) ? u : -1;
 }
 
-// acc[a] = sum_k w[|k|] d(a + h + k) for the 16 outputs a of a window, load(u) = d(u), u < 2 h + 1 + 15.
-// Output a sees d(u) with weight wsym[15 + u - a]: w[|u - a - h|] inside 0 <= u - a <= 2 h, an exact zero outside.
-template <class Load>
-__device__ __forceinline__ void lowpass_fir16(Load load, const double* __restrict__ wsym, int h, double (&acc)[LOWPASS_WIN]) {
-#pragma unroll
-  for (int a = 0; a < LOWPASS_WIN; ++a) acc[a] = 0.0;
-#pragma unroll 4
-  for (int u = 0; u < 2 * h + 1 + LOWPASS_PADW; ++u) {
-    const double s = load(u);
-    const double* wu = wsym + LOWPASS_PADW + u;         // (wave-uniform: scalar loads)
-#pragma unroll
-    for (int a = 0; a < LOWPASS_WIN; ++a) acc[a] = fma(wu[-a], s, acc[a]);
-  }
-}
-
-// grid ceil(ceil(n / 16) p / 256), block 256: thread (window g, column j) writes Y[16 g .. 16 g + 15][j] (Y [n x p], tight).
-// trend [2 x p] (a then b) or NULL.
+// The thread map of a written panel (fir_thread), the window over the 2 h + 1 taps of wsym: load(u) = d(t0 - h + u), so that
+// output a sees d(t0 + a + k) with weight w[|k|].  trend [2 x p] (a then b) or NULL.
 __global__ __launch_bounds__(256) void lowpass_fir_kernel(const float* __restrict__ S, int64_t n, int p, int64_t ld,
                                                            const double* __restrict__ wsym, int h,
                                                            const double* __restrict__ trend, double* __restrict__ Y) {
-  const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t g = id / p;
-  const int j = (int)(id - g * p);
-  const int64_t t0 = g * LOWPASS_WIN;
-  if (t0 >= n) return;
-  const double ta = trend ? trend[j] : 0.0, tb = trend ? trend[p + j] : 0.0;
-  double acc[LOWPASS_WIN];
-  lowpass_fir16(
+  const FirThread th = fir_thread(p);
+  if (th.t0 >= n) return;
+  const double ta = trend ? trend[th.j] : 0.0, tb = trend ? trend[p + th.j] : 0.0;
+  double acc[FIR_WIN];
+  fir16(
       [&](int u) {
-        const int64_t r = lowpass_refl(t0 - h + u, n);
+        const int64_t r = lowpass_refl(th.t0 - h + u, n);
         if (r < 0) return 0.0;
-        const double s = (double)S[r * ld + j];
+        const double s = (double)S[r * ld + th.j];
         return trend ? s - fma(tb, (double)r, ta) : s;
       },
-      wsym, h, acc);
-#pragma unroll
-  for (int a = 0; a < LOWPASS_WIN; ++a) {
-    const int64_t t = t0 + a;
-    if (t < n) Y[t * p + j] = trend ? acc[a] + fma(tb, (double)t, ta) : acc[a];
-  }
+      wsym, 2 * h + 1, acc);
+  fir_store(Y, n, p, th, [&](int a, int64_t t) { return trend ? acc[a] + fma(tb, (double)t, ta) : acc[a]; });
 }
 
 // grid (G, nb (nb + 1) / 2), nb = ceil(p / 64), block 256, dynamic LDS LOWPASS_LDS_Y.  blockIdx.y counts the pairs (bi, bj),
@@ -88,8 +64,8 @@ __global__ __launch_bounds__(256) void lowpass_fir_kernel(const float* __restric
 __global__ __launch_bounds__(256, 2) void lowpass_gram_kernel(const double* __restrict__ Y, int64_t n, int p,
                                                                double* __restrict__ part) {
   extern __shared__ double lowpass_lds[];
-  double* Ya = lowpass_lds;                                                     // [64][LOWPASS_YLD]
-  double* Yb = lowpass_lds + LOWPASS_R * LOWPASS_YLD;                           // [64][LOWPASS_YLD]
+  double* Ya = lowpass_lds;                                                     // [64][MFMA64_TILE_LD]
+  double* Yb = lowpass_lds + FIR_R * MFMA64_TILE_LD;                           // [64][MFMA64_TILE_LD]
   const int nb = (p + 63) / 64;
   int bi = 0, bj = blockIdx.y;
   while (bj >= nb - bi) {
@@ -103,30 +79,22 @@ __global__ __launch_bounds__(256, 2) void lowpass_gram_kernel(const double* __re
   const int lc = ln.c, lk = ln.k;
   const bool active = 64 * bi + 16 * wave < p;                                  // (wave-uniform)
   const auto keep = [&](int y) { return 64 * bj + 16 * y < p && !(diag && y < wave); };
-  const int64_t ntiles = (n + LOWPASS_R - 1) / LOWPASS_R;
+  const int64_t ntiles = (n + FIR_R - 1) / FIR_R;
   f64x4 acc[4];
   mfma64_zero(acc);
-  // the tile of column block b of Y at rows r0 .. r0 + 63 into dst; rows past n and columns past p are exact zeros
-  auto stage = [&](int b, int64_t r0, double* dst) {
-    for (int e = threadIdx.x; e < LOWPASS_R * 64; e += 256) {
-      const int64_t t = r0 + (e >> 6);
-      const int gj = 64 * b + (e & 63);
-      dst[(e >> 6) * LOWPASS_YLD + (e & 63)] = (t < n && gj < p) ? Y[t * p + gj] : 0.0;
-    }
-  };
   const double* B = diag ? Ya : Yb;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t r0 = tile * LOWPASS_R;
-    stage(bi, r0, Ya);
-    if (!diag) stage(bj, r0, Yb);
+    const int64_t r0 = tile * FIR_R;
+    fir_stage_tile(Y, n, p, bi, r0, Ya);
+    if (!diag) fir_stage_tile(Y, n, p, bj, r0, Yb);
     __syncthreads();
     if (active) {
 #pragma unroll 4
-      for (int s = 0; s < LOWPASS_R / 4; ++s) {
-        const double a = Ya[(4 * s + lk) * LOWPASS_YLD + 16 * wave + lc];
+      for (int s = 0; s < FIR_R / 4; ++s) {
+        const double a = Ya[(4 * s + lk) * MFMA64_TILE_LD + 16 * wave + lc];
 #pragma unroll
         for (int y = 0; y < 4; ++y)
-          if (keep(y)) mfma64_step(acc[y], a, B[(4 * s + lk) * LOWPASS_YLD + 16 * y + lc]);
+          if (keep(y)) mfma64_step(acc[y], a, B[(4 * s + lk) * MFMA64_TILE_LD + 16 * y + lc]);
       }
     }
     __syncthreads();      // the next tile overwrites the LDS

@@ -23,6 +23,10 @@ namespace eofx {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
+// Row stride, in doubles, of a 64-column operand tile in LDS whose rows are the k-steps (lane (c, k) reads row 4 s + k, column
+// 16 y + c): rows k and k + 1 lie on disjoint halves of the banks for the 32 lanes of a ds_read_b64 half-wave (k = 0, 1 | 2, 3).
+constexpr int MFMA64_TILE_LD = 80;
+
 struct Mfma64Lane {
   int c, k;
 };

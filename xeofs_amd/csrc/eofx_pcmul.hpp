@@ -10,7 +10,7 @@
 //                  (16 x 256) are fetched into registers while the products of the previous slab issue, then stored to LDS.
 //                  Row strides: 18 doubles for X (lanes (i, k) and (i, k + 1), i < 16, on 32 distinct bank pairs: 36 i mod 64
 //                  runs over the multiples of 4) and 272 for M (rows k and k + 1 on disjoint halves of the banks, as
-//                  LAGCOV_YLD).  Blocks of 16 rows or 16 columns that lie wholly outside Y are skipped (wave-uniform).
+//                  MFMA64_TILE_LD).  Blocks of 16 rows or 16 columns that lie wholly outside Y are skipped (wave-uniform).
 // Every output is summed over k ascending by one lane chain, no atomics, the grid a function of the shape alone: two runs
 // are equal bit for bit.  Rows, columns and k out of range are staged as zeros and never stored.  gfx950 only.
 #pragma once

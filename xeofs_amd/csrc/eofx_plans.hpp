@@ -29,15 +29,13 @@ constexpr int VIEWCOV_T = 128;           // rows and columns of C per tile (64 p
 constexpr int VIEWCOV_K = 16;            // samples per slab
 constexpr int VIEWCOV_WGS = 512;         // workgroups aimed at; also the bound of the partial blocks
 constexpr int VIEWCOV_SPLIT_SLABS = 16;  // a split takes at least this many slabs (256 samples)
+constexpr int FIR_R = 64;                // filter covariances (eofx_lagcov.hpp, eofx_lowpass.hpp): samples per row tile
+constexpr int FIR_WIN = 16;              // outputs per thread of the sliding window
+constexpr int FIR_PADW = FIR_WIN - 1;    // zeros on either side of the weights
+constexpr int LAGCOV_PADW = FIR_PADW, LOWPASS_PADW = FIR_PADW;      // (the names tests/plans_shim.cpp reports either plan's padding under)
 constexpr int LAGCOV_PMAX = 1024;        // columns of S (the partials stay within 8 workgroups x 8 MiB at the limit)
-constexpr int LAGCOV_R = 64;             // samples per row tile
-constexpr int LAGCOV_WIN = 16;           // outputs per thread of the sliding window
-constexpr int LAGCOV_PADW = LAGCOV_WIN - 1;
 constexpr int LAGCOV_FUSE_NTAU = 65;     // a row tile and its ntau - 1 halo rows fit the 128 staged rows up to here
 constexpr int LAGCOV_WGS = 512;          // workgroups aimed at (two per CU fit the LDS of the fused kernel)
-constexpr int LOWPASS_R = 64;             // samples per row tile
-constexpr int LOWPASS_WIN = 16;           // outputs per thread of the sliding window
-constexpr int LOWPASS_PADW = LOWPASS_WIN - 1;
 constexpr int LOWPASS_WGS = 512;          // workgroups aimed at (two per CU)
 constexpr int64_t LOWPASS_PART_MAX = (int64_t)1 << 23;      // doubles of partials (64 MiB)
 // Lags are processed in groups whose side-by-side sample panel is at most this many columns wide: the wide product then
@@ -500,33 +498,29 @@ inline int viewcov_plan(int64_t n, int p, const int* off, int m, bool keep_diag,
 
 // ---- filter covariances (eofx_lagcov.hpp, eofx_lowpass.hpp) ----------------------------------------------------------------
 // ny tile pairs of 64 columns x G splits of the row tiles (a function of the shape alone), and the weights as the kernels'
-// sliding windows read them: zero-padded by WIN - 1 on either side.
+// sliding windows read them: zero-padded by FIR_PADW on either side.
 struct FilterPlan {
   int ny, G;
   std::vector<double> w;
 };
+// ny workgroup columns, at most gmax splits of the row tiles, and wpad[15 + i] = tap(i), i < taps
+template <class Tap>
+inline FilterPlan filter_plan(int64_t n, int ny, int64_t gmax, int taps, Tap tap) {
+  FilterPlan pl{ny, (int)std::min<int64_t>((n + FIR_R - 1) / FIR_R, std::max<int64_t>(1, gmax)),
+                std::vector<double>((size_t)taps + 2 * FIR_PADW, 0.0)};
+  for (int i = 0; i < taps; ++i) pl.w[(size_t)(FIR_PADW + i)] = tap(i);
+  return pl;
+}
 // w[0 .. ntau): wpad[15 + tau] = w[tau]
 inline FilterPlan lagcov_plan(int64_t n, int p, const double* w, int ntau) {
-  FilterPlan pl;
-  const int nb = (p + 63) / 64;
-  pl.ny = nb * ((nb + 3) / 4);
-  const int64_t ntiles = (n + LAGCOV_R - 1) / LAGCOV_R;
-  pl.G = (int)std::min<int64_t>(ntiles, std::max(1, LAGCOV_WGS / pl.ny));
-  pl.w.assign((size_t)ntau + 2 * LAGCOV_PADW, 0.0);
-  std::copy(w, w + ntau, pl.w.begin() + LAGCOV_PADW);
-  return pl;
+  const int nb = (p + 63) / 64, ny = nb * ((nb + 3) / 4);
+  return filter_plan(n, ny, LAGCOV_WGS / ny, ntau, [&](int i) { return w[i]; });
 }
 // w[0 .. h]: the symmetric wsym[15 + h + k] = w[|k|], k = -h .. h
 inline FilterPlan lowpass_plan(int64_t n, int p, const double* w, int h) {
-  FilterPlan pl;
-  const int nb = (p + 63) / 64;
-  pl.ny = nb * (nb + 1) / 2;
-  const int64_t ntiles = (n + LOWPASS_R - 1) / LOWPASS_R;
-  const int64_t gmax = std::max<int64_t>(1, std::min<int64_t>(LOWPASS_WGS / pl.ny, LOWPASS_PART_MAX / ((int64_t)p * p)));
-  pl.G = (int)std::min<int64_t>(ntiles, gmax);
-  pl.w.assign((size_t)2 * h + 1 + 2 * LOWPASS_PADW, 0.0);
-  for (int k = -h; k <= h; ++k) pl.w[(size_t)(LOWPASS_PADW + h + k)] = w[(size_t)(k < 0 ? -k : k)];
-  return pl;
+  const int nb = (p + 63) / 64, ny = nb * (nb + 1) / 2;
+  return filter_plan(n, ny, std::min<int64_t>(LOWPASS_WGS / ny, LOWPASS_PART_MAX / ((int64_t)p * p)), 2 * h + 1,
+                     [&](int i) { return w[i < h ? h - i : i - h]; });
 }
 
 }  // namespace eofx

@@ -13,7 +13,7 @@
 //                           two slabs of Z (16 x 128 columns of the rows and of the columns of the tile) are fetched as
 //                           float32 into registers while the products of the previous slab issue, then converted, centred
 //                           in float64 and stored to LDS [k][column], row stride 144 doubles (rows k and k + 1 on disjoint
-//                           halves of the banks, as LAGCOV_YLD).  Inside a tile a wave is idle (wave-uniform) when its block
+//                           halves of the banks, as MFMA64_TILE_LD).  Inside a tile a wave is idle (wave-uniform) when its block
 //                           lies below the diagonal, outside C, or -- without keep_diag -- inside one view; blocks of 16 rows
 //                           or columns outside C, and the 16 x 16 blocks below the diagonal of a wave on the diagonal, are
 //                           skipped.  Every wanted C[i, j], i <= j, is written together with its mirror image C[j, i] from

@@ -1365,6 +1365,11 @@ LAGCOV_PMAX = 1024        # columns the kernels take
 LAGCOV_FUSE_NTAU = 65     # up to here the filtered panel stays in LDS; beyond, it is written once
 
 
+def _host_f64(a) -> np.ndarray:
+    """a small operand of the filter entries (weights, trend), a host array or a tensor, as a contiguous float64 host array"""
+    return np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float64)
+
+
 def lagcov(ctx: Context, S, w):
     """M [p x p] = sum_tau w[tau] S[:n - tau]^T S[tau:] (float64 device tensor) of a float32 panel S [n x p] -- a host
     array or a device tensor, whose row stride may exceed p -- and the weights w [ntau] of the lags 0 .. ntau - 1
@@ -1372,7 +1377,7 @@ def lagcov(ctx: Context, S, w):
     torch = _torch()
     S = device_panel(ctx, S, "S", (torch.float32,))
     n, p = S.shape
-    w = np.ascontiguousarray(w.detach().cpu().numpy() if hasattr(w, "detach") else w, dtype=np.float64)
+    w = _host_f64(w)
     if w.ndim != 1:
         raise ValueError(f"w must be a vector of lag weights, got shape {w.shape}")
     M = torch.empty((p, p), dtype=torch.float64, device=S.device)
@@ -1387,11 +1392,11 @@ def _lowpass(ctx: Context, S, w, trend, want_r: bool, want_y: bool):
     torch = _torch()
     S = device_panel(ctx, S, "S", (torch.float32,))
     n, p = S.shape
-    w = np.ascontiguousarray(w.detach().cpu().numpy() if hasattr(w, "detach") else w, dtype=np.float64)
+    w = _host_f64(w)
     if w.ndim != 1 or w.size < 1:
         raise ValueError(f"w must be a vector of the h + 1 weights w_0 .. w_h, got shape {w.shape}")
     if trend is not None:
-        trend = np.ascontiguousarray(trend.detach().cpu().numpy() if hasattr(trend, "detach") else trend, dtype=np.float64)
+        trend = _host_f64(trend)
         if trend.shape != (2, p):
             raise ValueError(f"trend must have shape (2, {p}): the intercepts, then the slopes, got {trend.shape}")
     R = torch.empty((p, p), dtype=torch.float64, device=S.device) if want_r else None

@@ -35,6 +35,7 @@ import numpy as np
 from .. import engine, labelled
 from ..linalg.decomposer import Decomposer
 from ..preprocessing import parse_scores
+from . import _pcspace
 from .eof import EOF, NO_EXPLAINED_VARIANCE, NO_SINGULAR_VALUES
 
 
@@ -138,7 +139,6 @@ class LFCA(EOF):
     def _fit_algorithm(self, mat, pmat=None, dec=None):
         """the module's equations on the resident, preprocessed field `mat`; the inner PCA decomposes its centred twin"""
         prm, ctx = self._params, self.ctx
-        torch = engine._torch()
         pmat = mat if pmat is None else pmat
         n, k = mat.n, int(self.n_modes)
         h = self._half_width(n)
@@ -158,32 +158,12 @@ class LFCA(EOF):
         C0 = engine.lowpass_cov(ctx, Sd, np.array([1.0])).cpu().numpy() / (n - 1.0)
         R = engine.lowpass_cov(ctx, Sd, w, trend).cpu().numpy() / (n - 1.0)
         t2 = time.perf_counter()
-        # 3. whitening with the full eigendecomposition of C0, 4. the symmetric eigenproblem
-        d, E = engine.host_eigh(C0)                                             # descending
-        # singular to the accuracy of the float32 scores: numpy.linalg.matrix_rank's rule on their singular values
-        if not d[-1] > 0.0 or np.sqrt(d[-1]) <= max(n, q) * np.finfo(np.float32).eps * np.sqrt(d[0]):
-            raise np.linalg.LinAlgError("the covariance of the PCA scores is singular: fewer independent modes than "
-                                        f"n_pca_modes={q}")
-        K = E.T / np.sqrt(d)[:, None]
-        Tm = K @ R @ K.T
-        r, Uo = engine.host_eigh(0.5 * (Tm + Tm.T))                             # descending
-        r, Uo = r[:k].copy(), np.ascontiguousarray(Uo[:, :k])
-        Vq = K.T @ Uo                                                           # q x k
-        Wq = C0 @ Vq
+        # 3. whitening with the full eigendecomposition of C0 (of full rank to float32 accuracy), 4. the symmetric eigenproblem
+        r, Uo, Vq, Wq = _pcspace.whitened_modes(C0, R, k, rank_rows=n)
         t3 = time.perf_counter()
-        # products of inner length q in float64 on the device (fixed order), rounded once
-        FW = engine.pcmul(ctx, V32, np.concatenate([Vq, Wq], axis=1))           # P x 2k
-        Pm = engine.pcmul(ctx, Sd, Vq)                                          # n x k
-        # 5. one deterministic sign per mode, from its pattern
-        W = FW[:, k:]
-        sgn = torch.where(W.amax(dim=0).abs() >= W.amin(dim=0).abs(), 1.0, -1.0).to(torch.float64)
-        FW = FW * torch.cat([sgn, sgn])
-        Pm = Pm * sgn
-        norms = torch.sqrt((Pm * Pm).sum(dim=0)).cpu().numpy()
-        sg = sgn.cpu().numpy()
-        f32 = torch.float32
-        self.data = dict(input_data=S32, components=FW[:, k:].to(f32).cpu().numpy(), scores=Pm.to(f32).cpu().numpy(),
-                         norms=norms, filter_patterns=FW[:, :k].to(f32).cpu().numpy(), low_frequency_ratio=r)
+        # 5. products of inner length q in float64 on the matrix cores (fixed order), rounded once; one sign per mode
+        proj, sg = _pcspace.signed_projection(lambda X, B: engine.pcmul(ctx, X, B), V32, Sd, Vq, Wq)
+        self.data = dict(input_data=S32, **proj, low_frequency_ratio=r)
         self._U, self._C0, self._R = Uo * sg, C0, R
         self._Vq = Vq * sg
         self._weights, self._half = w, h
@@ -197,12 +177,7 @@ class LFCA(EOF):
     def transform(self, X, normalized: bool = False):
         """new data -> the fitted preprocessing -> PC space (X V) -> the fitted combination Vq"""
         self.compute()
-        mat, fields, vs = self.preprocessor.transform(X)
-        try:
-            proj = engine.project(self.ctx, mat, self._pca_components)              # n' x q float32
-        finally:
-            mat.free()
-        Z = engine.pcmul(self.ctx, proj, self._Vq, engine._torch().float32).cpu().numpy()
+        Z, fields, vs = _pcspace.project_modes(self, X, self._Vq, engine._torch().float32)
         if normalized:
             Z = Z / self.data["norms"].astype(Z.dtype)
         return self.preprocessor.inverse_transform_scores(Z, "scores", self.attrs, fields, vs)
@@ -215,13 +190,8 @@ class LFCA(EOF):
         if normalized:
             S = S * self.data["norms"][modes - 1]
         C = self.data["components"][:, modes - 1]
-        ctx = self.ctx
-        Z = engine.device_panel(ctx, np.ascontiguousarray(S, dtype=np.float64))
-        P = C.shape[0]
-        rec = np.empty((S.shape[0], P))
-        for c0 in range(0, P, engine.PCMUL_BMAX):
-            Ct = np.ascontiguousarray(C[c0:c0 + engine.PCMUL_BMAX].T, dtype=np.float64)
-            rec[:, c0:c0 + Ct.shape[1]] = engine.pcmul(ctx, Z, Ct).cpu().numpy()
+        Z = engine.device_panel(self.ctx, np.ascontiguousarray(S, dtype=np.float64))
+        rec = _pcspace.reconstruct(self.ctx, Z, C)
         return self.preprocessor.inverse_transform_data(rec, "reconstructed_data", fields, vs)
 
     # ------------------------------------------------------------------ accessors

@@ -32,6 +32,7 @@ import numpy as np
 
 from .. import engine, labelled, spca
 from ..linalg.decomposer import Decomposer
+from . import _pcspace
 from .eof import EOF, NO_EXPLAINED_VARIANCE, NO_SINGULAR_VALUES
 
 
@@ -104,32 +105,13 @@ class OPA(EOF):
         M = engine.lagcov(ctx, Sd, w).cpu().numpy()
         t2 = time.perf_counter()
         C0 = 0.5 * (C0 + C0.T)
-        Msum = M + M.T
         # 3. whitening with the full eigendecomposition of C_0, 4. the symmetric eigenproblem (Hannachi 2021, eq. 8.20)
-        d, E = engine.host_eigh(C0)
-        if not d[-1] > 0.0:
-            raise np.linalg.LinAlgError("the covariance of the PCA scores is singular: fewer independent modes than "
-                                        f"n_pca_modes={q}")
-        K = E.T / np.sqrt(d)[:, None]
-        Tm = 0.5 * (K @ Msum @ K.T)
-        lam, Uo = engine.host_eigh(0.5 * (Tm + Tm.T))                          # descending
-        lam, Uo = lam[:k].copy(), np.ascontiguousarray(Uo[:, :k])
-        Vq = K.T @ Uo                                                           # q x k
-        Wq = C0 @ Vq
+        lam, Uo, Vq, Wq = _pcspace.whitened_modes(C0, 0.5 * (M + M.T), k)
         t3 = time.perf_counter()
-        # products of inner length q in float64 on the device (fixed order), rounded once
-        FW = spca.spca_rowmul(ctx, spca._dev64(ctx, Cmp32), np.concatenate([Vq, Wq], axis=1))       # P x 2k
-        P = spca.spca_rowmul(ctx, Sd.to(torch.float64), Vq)                                         # n x k
-        # 5. one deterministic sign per mode, from its pattern
-        W = FW[:, k:]
-        sgn = torch.where(W.amax(dim=0).abs() >= W.amin(dim=0).abs(), 1.0, -1.0).to(torch.float64)
-        FW = FW * torch.cat([sgn, sgn])
-        P = P * sgn
-        norms = torch.sqrt((P * P).sum(dim=0)).cpu().numpy()
-        sg = sgn.cpu().numpy()
-        f32 = torch.float32
-        self.data = dict(input_data=S32, components=FW[:, k:].to(f32).cpu().numpy(), scores=P.to(f32).cpu().numpy(),
-                         norms=norms, filter_patterns=FW[:, :k].to(f32).cpu().numpy(), decorrelation_time=lam)
+        # 5. products of inner length q in float64 on the device (fixed order), rounded once; one sign per mode
+        proj, sg = _pcspace.signed_projection(lambda X, B: spca.spca_rowmul(ctx, X, B), spca._dev64(ctx, Cmp32),
+                                              Sd.to(torch.float64), Vq, Wq)
+        self.data = dict(input_data=S32, **proj, decorrelation_time=lam)
         self._U, self._C0 = Uo * sg, C0                 # kept as the reference keeps them (opa.py:267-268)
         self._Vq = Vq * sg
         self._pca_scores, self._pca_components = S32, Cmp32

@@ -36,6 +36,7 @@ import numpy as np
 from .. import engine, labelled
 from ..linalg.decomposer import Decomposer
 from ..preprocessing import parse_scores
+from . import _pcspace
 from .eof import EOF, NO_EXPLAINED_VARIANCE, NO_SINGULAR_VALUES, ComplexEOF
 
 POP_QMAX = engine.PCMUL_AMAX          # PCA modes the PC-space product takes
@@ -225,13 +226,8 @@ class POP(EOF):
     def transform(self, X, normalized: bool = False):
         """pop.py:271-294: new data -> the fitted preprocessing -> PC space (X V) -> the fitted coefficient product"""
         self.compute()
-        mat, fields, vs = self.preprocessor.transform(X)
-        try:
-            proj = engine.project(self.ctx, mat, self._pca_components)             # n' x q float32
-        finally:
-            mat.free()
+        Z, fields, vs = _pcspace.project_modes(self, X, self._W)
         q = self._W.shape[0]
-        Z = engine.pcmul(self.ctx, proj, self._W).cpu().numpy()
         Z = Z[:, :q] + 1j * Z[:, q:]
         if normalized:
             Z = Z / self.data["norms"]
@@ -249,13 +245,8 @@ class POP(EOF):
         C = self.data["components"][:, modes - 1]
         ctx = self.ctx
         Zr, Zi = engine.device_panel(ctx, S.real), engine.device_panel(ctx, S.imag)      # float64, staged once for the blocks
-        P = C.shape[0]
-        rec_re, rec_im = np.empty((S.shape[0], P)), np.empty((S.shape[0], P))
-        for c0 in range(0, P, engine.PCMUL_BMAX):
-            Cr = np.ascontiguousarray(C.real[c0:c0 + engine.PCMUL_BMAX].T, dtype=np.float64)
-            Ci = np.ascontiguousarray(C.imag[c0:c0 + engine.PCMUL_BMAX].T, dtype=np.float64)
-            rec_re[:, c0:c0 + Cr.shape[1]] = (engine.pcmul(ctx, Zr, Cr) - engine.pcmul(ctx, Zi, Ci)).cpu().numpy()
-            rec_im[:, c0:c0 + Cr.shape[1]] = (engine.pcmul(ctx, Zi, Cr) + engine.pcmul(ctx, Zr, Ci)).cpu().numpy()
+        rec_re = _pcspace.reconstruct(ctx, Zr, C.real) - _pcspace.reconstruct(ctx, Zi, C.imag)
+        rec_im = _pcspace.reconstruct(ctx, Zi, C.real) + _pcspace.reconstruct(ctx, Zr, C.imag)
         pre = self.preprocessor
         re = pre.inverse_transform_data(rec_re, "reconstructed_data", fields, vs)
         mean, pre.mean_ = pre.mean_, None
