@@ -562,6 +562,28 @@ int eofx_colquad_f32(eofx_ctx *ctx, const float *T, int64_t p, int64_t n, int64_
  * field is read only.  EOFX_ERR_ARG for a masked in-place matrix (layout mode 3) or lda below the samples of m;
  * EOFX_ERR_SHAPE for more than 16384 samples.                                                                           */
 int eofx_mat_colquad_f32(eofx_ctx *ctx, const eofx_mat *m, const float *A, int64_t lda, double *q);
+/* ---- pairwise-minimum operator of the teleconnectivity map (Wallace & Gutzler 1981; xeofs_amd/single/teleconnectivity.py,
+ * csrc/eofx_pairmin.hpp) ----
+ * T [p x n]: a SERIES-MAJOR float32 device panel, row j the n samples of series j, row stride ld >= n.
+ * w [p]: a float32 device vector of scales.
+ *   d[j, i]    = sum_t T[j, t] T[i, t]     (float32 operands and accumulators on v_mfma_f32_32x32x2_f32: an fma chain, t ascending)
+ *   r[j, i]    = (d[j, i] * w[j]) * w[i]   (float32, this order)
+ *   rmin[j]    (float32, device, p entries) = min r[j, i] over i != j with w[i] > 0 and r[j, i] not NaN
+ *   partner[j] (int32, device, p entries)   = the LOWEST i that attains it
+ * and rmin[j] = NaN, partner[j] = -1 where w[j] <= 0, w[j] is NaN or no admissible i exists (p == 1 among them).  With T
+ * centred and w[j] = 1 / |T_j|, r is the correlation matrix; the operator assumes neither.  The p x p matrix is never stored:
+ * a workgroup walks its tiles of i in ascending order and keeps the running (value, index) minimum of its series, replaced on
+ * strict <, or on an equal value with a lower index; where the tiles of i are shared among several workgroups a second kernel
+ * combines their partials in ascending order by the same rule.  No atomics: the grid and every order are functions of (n, p)
+ * alone, so two runs are equal bit for bit.  A NaN or an infinity in one series reaches only the pairs that involve it.
+ * Nothing but rmin[0 .. p) and partner[0 .. p) is written; T and w are read only, and nothing past column n of a row is read.
+ * p == 0 is a no-op.  EOFX_ERR_ARG for n < 1, p < 0, p >= 2^31 or a stride below n; EOFX_ERR_SHAPE for n > 2^30.          */
+int eofx_pairmin_f32(eofx_ctx *ctx, const float *T, int64_t p, int64_t n, int64_t ld, const float *w, float *rmin,
+                     int32_t *partner);
+/* The same operator on a resident matrix: series j = column j of m, n = the samples of m, w, rmin and partner of m.p entries.
+ * The kernel reads the sample-contiguous layout of m where it lies (built on demand and kept: the caller may release it
+ * again); the field is read only.  EOFX_ERR_ARG for a masked in-place matrix (layout mode 3).                           */
+int eofx_mat_pairmin_f32(eofx_ctx *ctx, const eofx_mat *m, const float *w, float *rmin, int32_t *partner);
 /* ---- PC-space product of principal oscillation pattern analysis (xeofs/single/pop.py:185-198, csrc/eofx_pcmul.hpp) ---
  * Y [rows x b] = X [rows x a] M [a x b]: X a device panel of float32 or float64 (x_dtype) with row stride ldx >= a, M
  * float64 row-major (host|device), Y a device panel of float64 or float32 (y_dtype) with row stride ldy >= b.  Accumulated

@@ -16,6 +16,7 @@
 #include "eofx_lowpass.hpp"
 #include "eofx_orderpos.hpp"
 #include "eofx_colquad.hpp"
+#include "eofx_pairmin.hpp"
 #include "eofx_pcmul.hpp"
 #include "eofx_viewcov.hpp"
 #include "eofx_lrfill.hpp"
@@ -5637,6 +5638,68 @@ extern "C" int eofx_mat_colquad_f32(eofx_ctx* ctx, const eofx_mat* m, const floa
   CHK(arena_reserve(ctx, colquad_arena_bytes(m->n, m->p)));
   ArenaScope scope(ctx);
   CHK(launch_colquad(ctx, m->Xt, m->p, m->n, m->n_pad, A, lda, q));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return EOFX_OK;
+}
+
+// ---- pairwise-minimum operator of the teleconnectivity map (csrc/eofx_pairmin.hpp) -------------------------------------
+// rmin [p] float32, partner [p] int32, device.  The partials of a split grid live in the arena, which the caller has reserved.
+static int launch_pairmin(eofx_ctx* ctx, const float* T, int64_t p, int64_t n, int64_t ld, const float* w, float* rmin, int32_t* partner) {
+  const PairminPlan pl = pairmin_plan(n, p);
+  float* out_v = rmin;
+  int32_t* out_i = partner;
+  if (pl.splits > 1) {
+    out_v = arena_alloc<float>(ctx, (size_t)pl.splits * (size_t)p);
+    out_i = arena_alloc<int32_t>(ctx, (size_t)pl.splits * (size_t)p);
+    if (!out_v || !out_i) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (pairmin partials)");
+  }
+  hipLaunchKernelGGL(pairmin_kernel, dim3((unsigned)pl.tiles, (unsigned)pl.splits), dim3(256), 0, ctx->stream, T, p, (int)n, ld, w, out_v,
+                     out_i, pl.tiles);
+  KCHK();
+  if (pl.splits > 1) {
+    hipLaunchKernelGGL(pairmin_combine_kernel, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, out_v, out_i, pl.splits, p,
+                       rmin, partner);
+    KCHK();
+  }
+  return EOFX_OK;
+}
+
+static size_t pairmin_arena_bytes(int64_t n, int64_t p) { return (size_t)pairmin_plan(n, p).splits * (size_t)p * 8 + 512; }
+
+extern "C" int eofx_pairmin_f32(eofx_ctx* ctx, const float* T, int64_t p, int64_t n, int64_t ld, const float* w, float* rmin,
+                                int32_t* partner) {
+  if (!ctx) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (n < 1 || p < 0 || p > INT32_MAX)
+    return set_err(ctx, EOFX_ERR_ARG, "n must be >= 1 and 0 <= p < 2^31 (n = %lld, p = %lld)", (long long)n, (long long)p);
+  if (n > PAIRMIN_NMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the pairwise-minimum kernel takes series of at most %lld samples, got n = %lld", (long long)PAIRMIN_NMAX, (long long)n);
+  if (ld < n) return set_err(ctx, EOFX_ERR_ARG, "a row stride is below n = %lld (ld = %lld)", (long long)n, (long long)ld);
+  if (p == 0) return EOFX_OK;
+  if (!T || !w || !rmin || !partner || !is_device_ptr(T) || !is_device_ptr(w) || !is_device_ptr(rmin) || !is_device_ptr(partner))
+    return set_err(ctx, EOFX_ERR_ARG, "T, w, rmin and partner must be device buffers");
+  ENTER(ctx);
+  CHK(arena_reserve(ctx, pairmin_arena_bytes(n, p)));
+  ArenaScope scope(ctx);
+  CHK(launch_pairmin(ctx, T, p, n, ld, w, rmin, partner));
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // (the arena is handed back)
+  return EOFX_OK;
+}
+
+extern "C" int eofx_mat_pairmin_f32(eofx_ctx* ctx, const eofx_mat* m, const float* w, float* rmin, int32_t* partner) {
+  if (!ctx || !m) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (m->masked) return set_err(ctx, EOFX_ERR_ARG, "the pairwise-minimum operator does not take a masked in-place matrix: compact it first");
+  if (m->n < 1 || m->p > INT32_MAX)
+    return set_err(ctx, EOFX_ERR_ARG, "n must be >= 1 and p < 2^31 (n = %lld, p = %lld)", (long long)m->n, (long long)m->p);
+  if (m->n > PAIRMIN_NMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the pairwise-minimum kernel takes series of at most %lld samples, got n = %lld", (long long)PAIRMIN_NMAX, (long long)m->n);
+  if (m->p == 0) return EOFX_OK;
+  if (!w || !rmin || !partner || !is_device_ptr(w) || !is_device_ptr(rmin) || !is_device_ptr(partner))
+    return set_err(ctx, EOFX_ERR_ARG, "w, rmin and partner must be device buffers");
+  ENTER(ctx);
+  CHK(ensure_Xt(ctx, m));
+  CHK(arena_reserve(ctx, pairmin_arena_bytes(m->n, m->p)));
+  ArenaScope scope(ctx);
+  CHK(launch_pairmin(ctx, m->Xt, m->p, m->n, m->n_pad, w, rmin, partner));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return EOFX_OK;
 }

@@ -1527,6 +1527,56 @@ def mat_colquad(ctx: Context, mat: ResidentMatrix, A, out=None):
 
 
 # --------------------------------------------------------------------------- #
+# pairwise-minimum operator of the teleconnectivity map (eofx_pairmin_f32, eofx_mat_pairmin_f32, csrc/eofx_pairmin.hpp) #
+# --------------------------------------------------------------------------- #
+def _pairmin_operands(ctx: Context, w, p: int, out):
+    """w [p] as a contiguous float32 device vector (a host array or a device tensor of any stride) and the pair of
+    contiguous device vectors (float32 rmin, int32 partner) of p entries to write"""
+    torch = _torch()
+    if not hasattr(w, "data_ptr"):
+        w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32))
+    w = w.to(f"cuda:{ctx.device}")
+    if tuple(w.shape) != (p,):
+        raise ValueError(f"w must have one entry per series ({p}), got shape {tuple(w.shape)}")
+    w = w.to(torch.float32).contiguous()
+    if out is None:
+        return w, (torch.empty(p, dtype=torch.float32, device=w.device), torch.empty(p, dtype=torch.int32, device=w.device))
+    ok = isinstance(out, (tuple, list)) and len(out) == 2
+    for o, dt in zip(out if ok else (), (torch.float32, torch.int32)):
+        ok = ok and (hasattr(o, "data_ptr") and tuple(o.shape) == (p,) and o.dtype == dt and o.is_cuda
+                     and not (p > 1 and o.stride(0) != 1))
+    if not ok:
+        raise ValueError(f"out must be a pair of contiguous device vectors of {p} entries: float32 (rmin), int32 (partner)")
+    return w, tuple(out)
+
+
+def pairmin(ctx: Context, T, w, out=None):
+    """rmin[j] = min_i (d[j, i] w[j]) w[i], d[j, i] = sum_t T[j, t] T[i, t], over i != j with w[i] > 0 and a value that is not
+    NaN, and partner[j] = the lowest i that attains it, for every row of the SERIES-MAJOR float32 panel T [p x n] -- a host
+    array or a device tensor, whose row stride may exceed n -- and the float32 scales w [p].  (NaN, -1) where w[j] > 0 fails
+    or no such i exists.  -> (rmin float32, partner int32) device tensors of p entries (`out` when given).  float32 fma chains
+    on the matrix cores; the p x p matrix never exists; no atomics: two calls are equal bit for bit."""
+    torch = _torch()
+    T = device_panel(ctx, T, "T", (torch.float32,))
+    p, n = T.shape
+    w, out = _pairmin_operands(ctx, w, p, out)
+    if p:       # (an empty tensor has no address to pass: p == 0 is a no-op of the entry as well)
+        raise_for(ctx.lib.eofx_pairmin_f32(ctx.handle, ptr(T), p, n, T.stride(0), ptr(w), ptr(out[0]), ptr(out[1])), ctx.handle)
+    return out
+
+
+def mat_pairmin(ctx: Context, mat: ResidentMatrix, w, out=None):
+    """pairmin on the columns of a resident matrix: series j = the n samples of feature j.  Reads the sample-contiguous
+    layout of `mat` where it lies (built on demand; `mat.release_sample_layout()` drops it again)."""
+    if mat.masked:
+        raise ValueError("mat_pairmin does not take a masked in-place matrix: compact it first")
+    w, out = _pairmin_operands(ctx, w, mat.p, out)
+    if mat.p:
+        raise_for(ctx.lib.eofx_mat_pairmin_f32(ctx.handle, mat.handle, ptr(w), ptr(out[0]), ptr(out[1])), ctx.handle)
+    return out
+
+
+# --------------------------------------------------------------------------- #
 # PC-space product of principal oscillation pattern analysis (eofx_pcmul_f64, csrc/eofx_pcmul.hpp)   #
 # --------------------------------------------------------------------------- #
 PCMUL_AMAX = 1024         # inner length the kernel takes (the PCA modes)
