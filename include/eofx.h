@@ -584,6 +584,40 @@ int eofx_pairmin_f32(eofx_ctx *ctx, const float *T, int64_t p, int64_t n, int64_
  * The kernel reads the sample-contiguous layout of m where it lies (built on demand and kept: the caller may release it
  * again); the field is read only.  EOFX_ERR_ARG for a masked in-place matrix (layout mode 3).                           */
 int eofx_mat_pairmin_f32(eofx_ctx *ctx, const eofx_mat *m, const float *w, float *rmin, int32_t *partner);
+/* ---- the three operators of spectral EOF analysis (Towne, Schmidt & Colonius 2018; Schmidt et al. 2019;
+ * xeofs_amd/single/spectral_eof.py, csrc/eofx_spectral.hpp).  Generic linear algebra: none of them knows about Fourier. ----
+ * blockxform: T [p x n] a SERIES-MAJOR float32 device panel (row stride ld >= n), B [ncoef x n_fft] a float32 device matrix
+ * (row stride ldb >= n_fft),
+ *   Q[c][b][j] (float32, device, contiguous [ncoef][nblk][p]) = sum_t B[c, t] T[j, b hop + t]
+ * -- the transform along time of nblk blocks of n_fft samples, hop apart, of every series.  float32 operands and accumulators
+ * on v_mfma_f32_32x32x2_f32: every Q a float32 fma chain, t ascending, computed by one workgroup, so two runs are equal bit
+ * for bit.  The overlapped blocks are never materialised; block starts may have any alignment.  A NaN or an infinity in
+ * series j reaches Q[.][.][j] only.  Nothing but Q is written; nothing past sample (nblk - 1) hop + n_fft - 1 of a series and
+ * nothing past column n_fft of a row of B is read.
+ * p == 0 is a no-op.  EOFX_ERR_ARG for p < 0, ncoef < 1, n_fft < 1, nblk < 1, hop < 1, (nblk - 1) hop + n_fft > n, ld < n or
+ * ldb < n_fft; EOFX_ERR_SHAPE for n_fft > 16384 (BLOCKXFORM_NFFT_MAX) or ncoef > 8192 (BLOCKXFORM_NCOEF_MAX).            */
+int eofx_blockxform_f32(eofx_ctx *ctx, const float *T, int64_t p, int64_t n, int64_t ld, const float *B, int64_t ncoef,
+                        int64_t n_fft, int64_t ldb, int64_t hop, int64_t nblk, float *Q);
+/* The same operator on a resident matrix: series j = column j of m, n = the samples of m, Q [ncoef][nblk][m.p].  The kernel
+ * reads the sample-contiguous layout of m where it lies (built on demand and kept: the caller may release it again); the
+ * field is read only.  EOFX_ERR_ARG for a masked in-place matrix (layout mode 3).                                        */
+int eofx_mat_blockxform_f32(eofx_ctx *ctx, const eofx_mat *m, const float *B, int64_t ncoef, int64_t n_fft, int64_t ldb,
+                            int64_t hop, int64_t nblk, float *Q);
+/* rowgram: R [nb][r][p] float32 device, contiguous: nb slabs R_f [r x p].
+ *   G[f] (float64, device, contiguous [nb][r][r]) = R_f R_f^T
+ * float32 fma chains on the matrix cores over spans of 2048 features (ROWGRAM_SPAN), feature ascending; the spans are added
+ * in float64 in ascending order.  The split of the spans over workgroups and the grid are functions of (r, p, nb) alone; no
+ * atomics: two runs are equal bit for bit, and G[f] equals its transpose bit for bit (element (a, b), a <= b, is computed
+ * once and stored twice).  The partials live in the context arena.  Nothing but G is written.
+ * nb == 0 is a no-op.  EOFX_ERR_ARG for nb < 0, r < 1 or p < 1; EOFX_ERR_SHAPE for r > 512 (ROWGRAM_RMAX) or nb > 65535.    */
+int eofx_rowgram_f32(eofx_ctx *ctx, const float *R, int64_t nb, int64_t r, int64_t p, double *G);
+/* slabmul: W [nb][q][r] and R [nb][r][p] float32 device, contiguous.
+ *   out[f] (float32, device, contiguous [nb][q][p]) = W[f] R_f: every element a float32 fma chain over the r rows ascending.
+ * Bound by reading R once (q / 2 flops per byte): a VALU kernel with W[f] in LDS.  Column j of out[f] depends on column j of
+ * R_f alone.  Nothing but out is written.
+ * nb == 0 or p == 0 is a no-op.  EOFX_ERR_ARG for nb < 0, p < 0, q < 1 or r < 1; EOFX_ERR_SHAPE for q > 16 (SLABMUL_QMAX),
+ * r > 512 (SLABMUL_RMAX) or nb > 65535.                                                                                  */
+int eofx_slabmul_f32(eofx_ctx *ctx, const float *W, const float *R, int64_t nb, int64_t q, int64_t r, int64_t p, float *out);
 /* ---- PC-space product of principal oscillation pattern analysis (xeofs/single/pop.py:185-198, csrc/eofx_pcmul.hpp) ---
  * Y [rows x b] = X [rows x a] M [a x b]: X a device panel of float32 or float64 (x_dtype) with row stride ldx >= a, M
  * float64 row-major (host|device), Y a device panel of float64 or float32 (y_dtype) with row stride ldy >= b.  Accumulated

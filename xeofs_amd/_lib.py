@@ -126,6 +126,10 @@ SIGNATURES = {
     "eofx_mat_colquad_f32": (_int, [_vp, _vp, _vp, _i64, _vp]),
     "eofx_pairmin_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "eofx_mat_pairmin_f32": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "eofx_blockxform_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "eofx_mat_blockxform_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "eofx_rowgram_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp]),
+    "eofx_slabmul_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "eofx_pcmul_f64":(_int, [_vp, _vp, _int, _i64, _int, _i64, _vp, _int, _vp, _int, _i64]),
     "eofx_viewcov_f64": (_int, [_vp, _vp, _i64, _int, _i64, _vp, _vp, _int, _int, _vp, _i64]),
     "eofx_gapmask_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _pi64]),

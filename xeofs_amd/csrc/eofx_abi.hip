@@ -17,6 +17,7 @@
 #include "eofx_orderpos.hpp"
 #include "eofx_colquad.hpp"
 #include "eofx_pairmin.hpp"
+#include "eofx_spectral.hpp"
 #include "eofx_pcmul.hpp"
 #include "eofx_viewcov.hpp"
 #include "eofx_lrfill.hpp"
@@ -5700,6 +5701,108 @@ extern "C" int eofx_mat_pairmin_f32(eofx_ctx* ctx, const eofx_mat* m, const floa
   CHK(arena_reserve(ctx, pairmin_arena_bytes(m->n, m->p)));
   ArenaScope scope(ctx);
   CHK(launch_pairmin(ctx, m->Xt, m->p, m->n, m->n_pad, w, rmin, partner));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return EOFX_OK;
+}
+
+// ---- the three operators of spectral EOF analysis (csrc/eofx_spectral.hpp) ----------------------------------------------
+static int check_blockxform(eofx_ctx* ctx, int64_t p, int64_t n, int64_t ncoef, int64_t n_fft, int64_t ldb, int64_t hop, int64_t nblk) {
+  if (p < 0 || ncoef < 1 || n_fft < 1 || nblk < 1)
+    return set_err(ctx, EOFX_ERR_ARG, "p must be >= 0 and ncoef, n_fft and nblk >= 1 (p = %lld, ncoef = %lld, n_fft = %lld, nblk = %lld)",
+                   (long long)p, (long long)ncoef, (long long)n_fft, (long long)nblk);
+  if (hop < 1) return set_err(ctx, EOFX_ERR_ARG, "hop must be >= 1, got hop = %lld", (long long)hop);
+  if (n_fft > BLOCKXFORM_NFFT_MAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the block-transform kernel takes blocks of at most %d samples, got n_fft = %lld", BLOCKXFORM_NFFT_MAX, (long long)n_fft);
+  if (ncoef > BLOCKXFORM_NCOEF_MAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the block-transform kernel takes at most %d coefficient rows, got ncoef = %lld", BLOCKXFORM_NCOEF_MAX, (long long)ncoef);
+  if (n_fft > n || (nblk - 1) > (n - n_fft) / hop)
+    return set_err(ctx, EOFX_ERR_ARG, "the last block ends past the series: (nblk - 1) hop + n_fft > n (nblk = %lld, hop = %lld, n_fft = %lld, n = %lld)",
+                   (long long)nblk, (long long)hop, (long long)n_fft, (long long)n);
+  if (ldb < n_fft) return set_err(ctx, EOFX_ERR_ARG, "the row stride of B is below n_fft = %lld (ldb = %lld)", (long long)n_fft, (long long)ldb);
+  return EOFX_OK;
+}
+
+static int launch_blockxform(eofx_ctx* ctx, const float* T, int64_t p, int64_t ld, const float* B, int64_t ncoef, int64_t n_fft, int64_t ldb,
+                             int64_t hop, int64_t nblk, float* Q) {
+  const BlockxformPlan pl = blockxform_plan(p, ncoef, nblk);
+  hipLaunchKernelGGL(blockxform_kernel, dim3((unsigned)pl.stiles, (unsigned)pl.ctiles, (unsigned)pl.groups), dim3(256), 0, ctx->stream, T, p, ld,
+                     B, (int)ncoef, (int)n_fft, ldb, hop, nblk, Q);
+  KCHK();
+  return EOFX_OK;
+}
+
+extern "C" int eofx_blockxform_f32(eofx_ctx* ctx, const float* T, int64_t p, int64_t n, int64_t ld, const float* B, int64_t ncoef,
+                                   int64_t n_fft, int64_t ldb, int64_t hop, int64_t nblk, float* Q) {
+  if (!ctx) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  CHK(check_blockxform(ctx, p, n, ncoef, n_fft, ldb, hop, nblk));
+  if (ld < n) return set_err(ctx, EOFX_ERR_ARG, "a row stride is below n = %lld (ld = %lld)", (long long)n, (long long)ld);
+  if (p > (int64_t)INT32_MAX * BLOCKXFORM_TS) return set_err(ctx, EOFX_ERR_SHAPE, "too many series for one grid (p = %lld)", (long long)p);
+  if (p == 0) return EOFX_OK;
+  if (!T || !B || !Q || !is_device_ptr(T) || !is_device_ptr(B) || !is_device_ptr(Q))
+    return set_err(ctx, EOFX_ERR_ARG, "T, B and Q must be device buffers");
+  ENTER(ctx);
+  CHK(launch_blockxform(ctx, T, p, ld, B, ncoef, n_fft, ldb, hop, nblk, Q));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return EOFX_OK;
+}
+
+extern "C" int eofx_mat_blockxform_f32(eofx_ctx* ctx, const eofx_mat* m, const float* B, int64_t ncoef, int64_t n_fft, int64_t ldb,
+                                       int64_t hop, int64_t nblk, float* Q) {
+  if (!ctx || !m) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (m->masked) return set_err(ctx, EOFX_ERR_ARG, "the block-transform operator does not take a masked in-place matrix: compact it first");
+  CHK(check_blockxform(ctx, m->p, m->n, ncoef, n_fft, ldb, hop, nblk));
+  if (m->p == 0) return EOFX_OK;
+  if (!B || !Q || !is_device_ptr(B) || !is_device_ptr(Q)) return set_err(ctx, EOFX_ERR_ARG, "B and Q must be device buffers");
+  ENTER(ctx);
+  CHK(ensure_Xt(ctx, m));
+  CHK(launch_blockxform(ctx, m->Xt, m->p, m->n_pad, B, ncoef, n_fft, ldb, hop, nblk, Q));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return EOFX_OK;
+}
+
+extern "C" int eofx_rowgram_f32(eofx_ctx* ctx, const float* R, int64_t nb, int64_t r, int64_t p, double* G) {
+  if (!ctx) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (nb < 0 || r < 1 || p < 1)
+    return set_err(ctx, EOFX_ERR_ARG, "nb must be >= 0 and r and p >= 1 (nb = %lld, r = %lld, p = %lld)", (long long)nb, (long long)r, (long long)p);
+  if (r > ROWGRAM_RMAX) return set_err(ctx, EOFX_ERR_SHAPE, "the row-Gram kernel takes slabs of at most %d rows, got r = %lld", ROWGRAM_RMAX, (long long)r);
+  if (nb > ROWGRAM_NBMAX) return set_err(ctx, EOFX_ERR_SHAPE, "the row-Gram kernel takes at most %d slabs per call, got nb = %lld", ROWGRAM_NBMAX, (long long)nb);
+  if (nb == 0) return EOFX_OK;
+  if (!R || !G || !is_device_ptr(R) || !is_device_ptr(G)) return set_err(ctx, EOFX_ERR_ARG, "R and G must be device buffers");
+  const RowgramPlan pl = rowgram_plan(r, p, nb);
+  const size_t elems = (size_t)nb * (size_t)pl.splits * (size_t)r * (size_t)r;
+  ENTER(ctx);
+  CHK(arena_reserve(ctx, elems * 8 + 256));
+  ArenaScope scope(ctx);
+  double* part = arena_alloc<double>(ctx, elems);
+  if (!part) return set_err(ctx, EOFX_ERR_NOMEM, "internal: arena exhausted (rowgram partials)");
+  hipLaunchKernelGGL(rowgram_kernel, dim3((unsigned)(pl.rt * pl.rt), (unsigned)pl.splits, (unsigned)nb), dim3(256), 0, ctx->stream, R, (int)r, p,
+                     pl.rt, pl.spans, part);
+  KCHK();
+  hipLaunchKernelGGL(rowgram_finish_kernel, dim3((unsigned)((r * r + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, part, pl.splits,
+                     (int)r, G);
+  KCHK();
+  HIPCHK(hipStreamSynchronize(ctx->stream));       // (the arena is handed back)
+  return EOFX_OK;
+}
+
+extern "C" int eofx_slabmul_f32(eofx_ctx* ctx, const float* W, const float* R, int64_t nb, int64_t q, int64_t r, int64_t p, float* out) {
+  if (!ctx) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (nb < 0 || p < 0 || q < 1 || r < 1)
+    return set_err(ctx, EOFX_ERR_ARG, "nb and p must be >= 0 and q and r >= 1 (nb = %lld, p = %lld, q = %lld, r = %lld)", (long long)nb, (long long)p,
+                   (long long)q, (long long)r);
+  if (q > SLABMUL_QMAX) return set_err(ctx, EOFX_ERR_SHAPE, "the slab-product kernel takes at most %d rows of W, got q = %lld", SLABMUL_QMAX, (long long)q);
+  if (r > SLABMUL_RMAX) return set_err(ctx, EOFX_ERR_SHAPE, "the slab-product kernel takes slabs of at most %d rows, got r = %lld", SLABMUL_RMAX, (long long)r);
+  if (nb > SLABMUL_NBMAX) return set_err(ctx, EOFX_ERR_SHAPE, "the slab-product kernel takes at most %d slabs per call, got nb = %lld", SLABMUL_NBMAX, (long long)nb);
+  if (nb == 0 || p == 0) return EOFX_OK;
+  if (!W || !R || !out || !is_device_ptr(W) || !is_device_ptr(R) || !is_device_ptr(out))
+    return set_err(ctx, EOFX_ERR_ARG, "W, R and out must be device buffers");
+  ENTER(ctx);
+  const dim3 grid((unsigned)((p + SLABMUL_TP - 1) / SLABMUL_TP), (unsigned)nb);
+  if (slabmul_qt(q) == 8)
+    hipLaunchKernelGGL(slabmul_kernel<8>, grid, dim3(256), 0, ctx->stream, W, R, (int)q, (int)r, p, out);
+  else
+    hipLaunchKernelGGL(slabmul_kernel<16>, grid, dim3(256), 0, ctx->stream, W, R, (int)q, (int)r, p, out);
+  KCHK();
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return EOFX_OK;
 }

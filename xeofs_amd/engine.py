@@ -1577,6 +1577,115 @@ def mat_pairmin(ctx: Context, mat: ResidentMatrix, w, out=None):
 
 
 # --------------------------------------------------------------------------- #
+# the operators of spectral EOF analysis (eofx_blockxform_f32, eofx_mat_blockxform_f32, eofx_rowgram_f32, eofx_slabmul_f32, csrc/eofx_spectral.hpp) #
+# --------------------------------------------------------------------------- #
+BLOCKXFORM_NFFT_MAX = 16384       # samples per block
+BLOCKXFORM_NCOEF_MAX = 8192       # rows of the coefficient matrix
+ROWGRAM_RMAX = 512                # rows of a slab
+ROWGRAM_SPAN = 2048               # features per float32 chain of rowgram
+SLABMUL_QMAX = 16                 # rows of W[f]
+SPECTRAL_NBMAX = 65535            # slabs per call of rowgram and slabmul
+
+
+def _blockxform_operands(ctx: Context, B, p: int, hop, nblk, out):
+    """B [ncoef x n_fft] as a float32 device tensor (strides honoured), hop and nblk as ints, and the contiguous float32 device
+    tensor [ncoef x nblk x p] to write"""
+    torch = _torch()
+    B = device_panel(ctx, B, "B", (torch.float32,))
+    ncoef = B.shape[0]
+    hop, nblk = int(hop), int(nblk)
+    if ncoef < 1 or B.shape[1] < 1 or nblk < 1:
+        raise ValueError(f"B must have at least one row and one column and nblk must be >= 1, got B {tuple(B.shape)}, nblk = {nblk}")
+    if out is None:
+        out = torch.empty((ncoef, nblk, p), dtype=torch.float32, device=B.device)
+    elif (not hasattr(out, "data_ptr") or tuple(out.shape) != (ncoef, nblk, p) or out.dtype != torch.float32 or not out.is_cuda
+          or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float32 device tensor of shape ({ncoef}, {nblk}, {p})")
+    return B, hop, nblk, out
+
+
+def blockxform(ctx: Context, T, B, hop: int, nblk: int, out=None):
+    """Q[c, b, j] = sum_t B[c, t] T[j, b hop + t] for every row of the SERIES-MAJOR float32 panel T [p x n] and the float32
+    coefficient matrix B [ncoef x n_fft] -- host arrays or device tensors, whose row strides may exceed their columns: the
+    transform along time of nblk blocks of n_fft samples, hop apart.  -> a float32 device tensor [ncoef x nblk x p] (`out`
+    when given), j contiguous.  float32 fma chains over t ascending on the matrix cores; the overlapped blocks are never
+    materialised; two calls are equal bit for bit, and Q[:, :, j] depends on series j alone."""
+    torch = _torch()
+    T = device_panel(ctx, T, "T", (torch.float32,))
+    p, n = T.shape
+    B, hop, nblk, out = _blockxform_operands(ctx, B, p, hop, nblk, out)
+    if p:       # (an empty tensor has no address to pass: p == 0 is a no-op of the entry as well)
+        raise_for(ctx.lib.eofx_blockxform_f32(ctx.handle, ptr(T), p, n, T.stride(0), ptr(B), B.shape[0], B.shape[1], B.stride(0),
+                                              hop, nblk, ptr(out)), ctx.handle)
+    return out
+
+
+def mat_blockxform(ctx: Context, mat: ResidentMatrix, B, hop: int, nblk: int, out=None):
+    """blockxform on the columns of a resident matrix: series j = the n samples of feature j.  Reads the sample-contiguous
+    layout of `mat` where it lies (built on demand; `mat.release_sample_layout()` drops it again)."""
+    if mat.masked:
+        raise ValueError("mat_blockxform does not take a masked in-place matrix: compact it first")
+    B, hop, nblk, out = _blockxform_operands(ctx, B, mat.p, hop, nblk, out)
+    if mat.p:
+        raise_for(ctx.lib.eofx_mat_blockxform_f32(ctx.handle, mat.handle, ptr(B), B.shape[0], B.shape[1], B.stride(0), hop, nblk,
+                                                  ptr(out)), ctx.handle)
+    return out
+
+
+def _slabs(ctx: Context, R, name: str = "R"):
+    """a batch of slabs [nb x r x p] as a contiguous float32 device tensor (a host array or a device tensor of any stride)"""
+    torch = _torch()
+    if not hasattr(R, "data_ptr"):
+        R = torch.from_numpy(np.ascontiguousarray(R, dtype=np.float32))
+    R = R.to(f"cuda:{ctx.device}")
+    if R.dim() != 3:
+        raise ValueError(f"{name} must be a batch of matrices [nb x rows x columns], got {R.dim()} dimensions")
+    return R.to(torch.float32).contiguous()
+
+
+def _check_out3(out, shape, dtype, what: str):
+    if (not hasattr(out, "data_ptr") or tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_cuda
+            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {what} device tensor of shape {tuple(shape)}")
+    return out
+
+
+def rowgram(ctx: Context, R, out=None):
+    """G[f] = R[f] R[f]^T (float64 device tensor [nb x r x r], `out` when given) of a batch of float32 slabs R [nb x r x p] --
+    a host array or a device tensor.  float32 fma chains on the matrix cores over spans of ROWGRAM_SPAN features, the spans
+    added in float64 in a fixed order; no atomics: two calls are equal bit for bit, and G[f] equals its transpose bit for
+    bit."""
+    torch = _torch()
+    R = _slabs(ctx, R)
+    nb, r, p = R.shape
+    if r < 1 or p < 1:
+        raise ValueError(f"R must have at least one row and one column per slab, got shape {tuple(R.shape)}")
+    out = (torch.empty((nb, r, r), dtype=torch.float64, device=R.device) if out is None
+           else _check_out3(out, (nb, r, r), torch.float64, "float64"))
+    if nb:
+        raise_for(ctx.lib.eofx_rowgram_f32(ctx.handle, ptr(R), nb, r, p, ptr(out)), ctx.handle)
+    return out
+
+
+def slabmul(ctx: Context, W, R, out=None):
+    """out[f] = W[f] R[f] (float32 device tensor [nb x q x p], `out` when given) of the float32 batches W [nb x q x r] and
+    R [nb x r x p] -- host arrays or device tensors.  float32 fma chains over the r rows ascending; column j of out[f]
+    depends on column j of R[f] alone."""
+    torch = _torch()
+    R = _slabs(ctx, R)
+    W = _slabs(ctx, W, "W")
+    nb, r, p = R.shape
+    if W.shape[0] != nb or W.shape[2] != r or W.shape[1] < 1 or r < 1:
+        raise ValueError(f"W must have shape ({nb}, q >= 1, {r}) to multiply R of shape {tuple(R.shape)}, got {tuple(W.shape)}")
+    q = W.shape[1]
+    out = (torch.empty((nb, q, p), dtype=torch.float32, device=R.device) if out is None
+           else _check_out3(out, (nb, q, p), torch.float32, "float32"))
+    if nb and p:
+        raise_for(ctx.lib.eofx_slabmul_f32(ctx.handle, ptr(W), ptr(R), nb, q, r, p, ptr(out)), ctx.handle)
+    return out
+
+
+# --------------------------------------------------------------------------- #
 # PC-space product of principal oscillation pattern analysis (eofx_pcmul_f64, csrc/eofx_pcmul.hpp)   #
 # --------------------------------------------------------------------------- #
 PCMUL_AMAX = 1024         # inner length the kernel takes (the PCA modes)

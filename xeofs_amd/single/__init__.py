@@ -7,6 +7,7 @@ from .lfca import LFCA  # noqa: F401
 from .opa import OPA  # noqa: F401
 from .pop import POP  # noqa: F401
 from .sparse_pca import SparsePCA  # noqa: F401
+from .spectral_eof import SpectralEOF  # noqa: F401
 from .teleconnectivity import Teleconnectivity  # noqa: F401
 from .trend_eof import TrendEOF  # noqa: F401
 from .eof_rotator import ComplexEOFRotator, EOFRotator, HilbertEOFRotator  # noqa: F401
