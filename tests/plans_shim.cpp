@@ -1,6 +1,6 @@
 // extern "C" wrappers around the GPU-free headers of the engine (xeofs_amd/csrc/eofx_plans.hpp, eofx_sketch.hpp,
-// eofx_hilbert_host.hpp, eofx_gwplan.hpp) for tests/test_plans_cpu.py, test_sketch_cpu.py, test_hilbert_host_cpu.py and
-// test_gwplan_cpu.py, which compile this file with the host C++ compiler (tests/plans_shim.py) and load it through ctypes.
+// eofx_hilbert_host.hpp, eofx_gwplan.hpp) for tests/test_plans_cpu.py, test_gram_plan_cpu.py, test_sketch_cpu.py,
+// test_hilbert_host_cpu.py and test_gwplan_cpu.py, which compile this file with the host C++ compiler (tests/plans_shim.py) and load it through ctypes.
 // With -DPLANS_SELFTEST the file is a stand-alone program that runs every wrapper on fixed inputs (for a sanitizer build:
 // c++ -fsanitize=address,undefined, or -fsanitize=thread -pthread).
 #include <cstdio>
@@ -59,6 +59,27 @@ int pl_lag_groups(int E, int L, int* out) {
 int pl_tmul_nt_ok(int64_t n, int64_t p_pad, int has_source, int L) { return tmul_nt_ok(n, p_pad, has_source != 0, L) ? 1 : 0; }
 int pl_matmul_nt_ok(int64_t rows, int L, int Lo) { return matmul_nt_ok(rows, L, Lo) ? 1 : 0; }
 int pl_gram_fast_ok(int64_t n_pad, int64_t p, int has_source) { return gram_fast_ok(n_pad, p, has_source != 0) ? 1 : 0; }
+// The work list of gram_nt_kernel (S <= 0: the plan's own choice).  head [4] = {S, st_per_split, T, grid}; items [grid][5] = {bi, bj,
+// st0, nst, slot} when grid <= cap_items; tiles [T][2] when T <= cap_tiles (call with zero capacities for the sizes) -> 0, or 1
+// when a list did not fit, or -1 when a padding word of an item is not zero
+int pl_gram_plan(int nti, int ntj, int sym, int nst_total, int S, int* head, int* items, int64_t cap_items, int* tiles, int64_t cap_tiles) {
+  GramPlan pl;
+  gram_plan_build(nti, ntj, sym != 0, nst_total, S, pl);
+  const int h[] = {pl.S, pl.st_per_split, pl.T, pl.grid};
+  std::copy(h, h + 4, head);
+  if ((int64_t)pl.items.size() != pl.grid || (int64_t)pl.tiles.size() != pl.T || pl.nti != nti || pl.ntj != ntj) return -1;
+  if (pl.grid > cap_items || pl.T > cap_tiles) return 1;
+  for (const GramItem& it : pl.items) {
+    if (it.pad0 | it.pad1 | it.pad2) return -1;
+    const int o[] = {it.bi, it.bj, it.st0, it.nst, it.slot};
+    items = std::copy(o, o + 5, items);
+  }
+  for (const GramTile& t : pl.tiles) {
+    *tiles++ = t.x;
+    *tiles++ = t.y;
+  }
+  return 0;
+}
 int pl_fit_first_eligible(int keep_raw, int prec, int aligned16, int64_t n, int64_t P, int l) {
   return fit_first_eligible(keep_raw, prec, aligned16 != 0, n, P, l) ? 1 : 0;
 }
@@ -254,6 +275,35 @@ int main() {
   expect(pl_gram_parts(130000, 1536) >= 1 && pl_rsvd_auto_iters(3, 100, 200) == 7 && pl_orth_tall_rule(512, 32, EOFX_PREC_F32) == 1, "rules");
   expect(pl_spca_grid(100000, 64) >= 1 && pl_lag_blocks(0) == 1 && pl_tmul_nt_ok(1037, 2560, 1, 512) == 1, "rules");
   expect(pl_matmul_nt_ok(1024, 512, 256) == 1 && pl_gram_fast_ok(512, 1000, 1) == 1 && pl_fit_first_eligible(2, EOFX_PREC_F16X3, 1, 120, 132, 16) == 1, "predicates");
+  // the work list of gram_nt_kernel: the splits of every tile cover the stages once, the forced S is normalised
+  for (int sym = 0; sym < 2; ++sym)
+    for (int nt : {1, 3, 8, 128})
+      for (int nst : {2, 26, 2050})
+        for (int S : {0, 1, 5, 40}) {
+          int head[4];
+          expect(pl_gram_plan(nt, nt == 128 ? 7 : nt, sym, nst, S, head, nullptr, 0, nullptr, 0) == 1, "gram_plan sizes");
+          std::vector<int> items(5 * (size_t)head[3]), tiles(2 * (size_t)head[2]);
+          expect(pl_gram_plan(nt, nt == 128 ? 7 : nt, sym, nst, S, head, items.data(), head[3], tiles.data(), head[2]) == 0, "gram_plan");
+          std::vector<int> covered((size_t)head[2], 0);
+          for (int b = 0; b < head[3]; ++b) {
+            const int* it = &items[5 * (size_t)b];
+            if (it[3] <= 0) continue;
+            const int tile = it[4] / head[0];
+            expect(it[4] >= 0 && tile < head[2] && it[3] % 2 == 0 && it[2] == it[4] % head[0] * head[1] && tiles[2 * (size_t)tile] == it[0] &&
+                       tiles[2 * (size_t)tile + 1] == it[1],
+                   "gram_plan item");
+            if (tile < head[2]) covered[(size_t)tile] += it[3];
+          }
+          for (int c : covered) expect(c == nst, "gram_plan covers every stage of every tile once");
+          expect(S <= 0 || head[0] == (nst + head[1] - 1) / head[1], "gram_plan normalises a forced S");
+        }
+  {
+    int head[4];
+    (void)pl_gram_plan(2, 2, 1, 26, 40, head, nullptr, 0, nullptr, 0);
+    expect(head[0] == 13 && head[1] == 2, "gram_plan: S = 40 of 26 stages");
+    (void)pl_gram_plan(2, 2, 1, 26, 5, head, nullptr, 0, nullptr, 0);
+    expect(head[0] == 5 && head[1] == 6, "gram_plan: S = 5 of 26 stages");
+  }
   int64_t cs[5];
   int ap[5];
   for (int64_t n : {2, 63, 64, 700, 5000})

@@ -22,7 +22,7 @@ SIGNATURES = {
     "pl_rsvd_auto_iters": (I, [I, I64, I64]), "pl_orth_tall_rule": (I, [I64, I, I]), "pl_spca_grid": (I, [I64, I64]),
     "pl_lag_blocks": (I, [I64]), "pl_lag_groupsize": (I, [I, I]), "pl_lag_groups": (I, [I, I, P]),
     "pl_tmul_nt_ok": (I, [I64, I64, I, I]), "pl_matmul_nt_ok": (I, [I64, I, I]), "pl_gram_fast_ok": (I, [I64, I64, I]),
-    "pl_fit_first_eligible": (I, [I, I, I, I64, I64, I]), "pl_colstats_plan": (None, [I64, I64, I64, I, I, I, P]),
+    "pl_gram_plan": (I, [I, I, I, I, I, P, P, I64, P, I64]), "pl_fit_first_eligible": (I, [I, I, I, I64, I64, I]), "pl_colstats_plan": (None, [I64, I64, I64, I, I, I, P]),
     "pl_colstats_scratch": (I64, [I64, I64]), "pl_summary_blocks": (I, [I64]),
     "pl_apply_plan": (None, [I64, I64, I64, I64, I, I, I, I, P]), "pl_viewcov_plan": (I, [I64, I, P, I, I, P, P, I, P]),
     "pl_lagcov_plan": (I, [I64, I, P, I, P, P]), "pl_lowpass_plan": (I, [I64, I, P, I, P, P]),

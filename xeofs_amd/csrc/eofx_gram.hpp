@@ -153,10 +153,14 @@ __global__ __launch_bounds__(256) void planes_split_t_kernel(const float* __rest
   *reinterpret_cast<u32x4*>(line + 80) = lo[1];
 }
 
-// work item of gram_nt_kernel: tile (bi, bj), first stage, number of stages (EVEN), output slot (tile-major: slot = tile * S + split)
-struct GramItem {
-  int bi, bj, st0, nst, slot, pad0, pad1, pad2;
-};
+// The work list (GramItem, GramTile, gram_plan_build) is host code without HIP: eofx_plans.hpp.  The kernels below load an item as
+// one 32-byte record and read the tile list as int2.
+static_assert(sizeof(GramItem) == 32 && offsetof(GramItem, bi) == 0 && offsetof(GramItem, bj) == 4 && offsetof(GramItem, st0) == 8 &&
+                  offsetof(GramItem, nst) == 12 && offsetof(GramItem, slot) == 16,
+              "gram_nt_kernel reads GramItem as {bi, bj, st0, nst, slot, 3 x pad}");
+static_assert(sizeof(GramTile) == sizeof(int2) && sizeof(int2) == 8 && alignof(GramTile) <= alignof(int2) && offsetof(GramTile, x) == 0 &&
+                  offsetof(GramTile, y) == 4,
+              "the finish kernels read the tile list {bi, bj} as int2 {x, y}");
 
 #define EOFX_GLDS16(gp, lp)                                                                               \
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) unsigned*)(gp), \
@@ -384,75 +388,6 @@ __global__ __launch_bounds__(256) void nt_finish_kernel(const float* __restrict_
       for (int e = 0; e < 4; ++e)
         if (gc + e < ncols) C[gr * ldc + gc + e] = v[e];
     }
-  }
-}
-
-}  // namespace eofx
-
-// ---- host side: the work list of gram_nt_kernel -----------------------------------------------------------------
-#include <algorithm>
-#include <vector>
-
-namespace eofx {
-
-struct GramPlan {
-  int nti = 0, ntj = 0, T = 0, S = 1, st_per_split = 0, grid = 0;
-  std::vector<GramItem> items;   // [grid]: workgroup b -> item (XCD b % 8 walks its own patch of tiles split by split)
-  std::vector<int2> tiles;       // [T]: slot order
-};
-
-static inline unsigned gram_morton(unsigned i, unsigned j) {
-  unsigned m = 0;
-  for (int b = 0; b < 12; ++b) m |= ((i >> b) & 1u) << (2 * b + 1) | ((j >> b) & 1u) << (2 * b);
-  return m;
-}
-
-// sym: only tiles bi <= bj (C = A A^T).  nst_total: stages (32 features each) of the contraction.
-// S <= 0: chosen here (rounds of 32 workgroups per XCD x stages per split, ~40 stages of fixed cost per item).
-static inline void gram_plan_build(int nti, int ntj, bool sym, int nst_total, int S, GramPlan& pl) {
-  pl.nti = nti;
-  pl.ntj = ntj;
-  pl.tiles.clear();
-  for (int i = 0; i < nti; ++i)
-    for (int j = sym ? i : 0; j < ntj; ++j) pl.tiles.push_back(int2{i, j});
-  std::sort(pl.tiles.begin(), pl.tiles.end(), [](const int2& a, const int2& b) {
-    return gram_morton((unsigned)a.x, (unsigned)a.y) < gram_morton((unsigned)b.x, (unsigned)b.y);
-  });
-  const int T = (int)pl.tiles.size();
-  pl.T = T;
-  int lo[9];
-  for (int x = 0; x <= 8; ++x) lo[x] = (int)((int64_t)T * x / 8);
-  int cmax = 0;
-  for (int x = 0; x < 8; ++x) cmax = std::max(cmax, lo[x + 1] - lo[x]);
-  if (S <= 0) {
-    double best = 1e300;
-    for (int s = 1; s <= 16 && s <= nst_total; ++s) {
-      const int sps = ((nst_total + s - 1) / s + 1) / 2 * 2;
-      const int s_eff = (nst_total + sps - 1) / sps;
-      if (s_eff != s) continue;
-      const double rounds = (double)((cmax * s + 31) / 32);
-      const double cost = rounds * (sps + 40.0) + 2.0 * s;
-      if (cost < best * 0.97) {
-        best = cost;
-        S = s;
-      }
-    }
-  }
-  const int sps = ((nst_total + S - 1) / S + 1) / 2 * 2;     // even (nst_total is: kpad % 64 == 0)
-  S = (nst_total + sps - 1) / sps;
-  pl.S = S;
-  pl.st_per_split = sps;
-  const int W = cmax * S;
-  pl.grid = 8 * W;
-  pl.items.assign((size_t)pl.grid, GramItem{0, 0, 0, 0, 0, 0, 0, 0});
-  for (int x = 0; x < 8; ++x) {
-    const int cnt = lo[x + 1] - lo[x];
-    for (int s = 0; s < S; ++s)
-      for (int t = 0; t < cnt; ++t) {
-        const int w = s * cnt + t, tile = lo[x] + t;
-        const int st0 = s * sps, nst = std::min(sps, nst_total - st0);
-        pl.items[(size_t)8 * w + x] = GramItem{pl.tiles[tile].x, pl.tiles[tile].y, st0, nst, tile * S + s, 0, 0, 0};
-      }
   }
 }
 

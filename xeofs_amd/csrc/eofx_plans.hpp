@@ -384,6 +384,76 @@ inline bool matmul_nt_ok(int64_t rows, int L, int Lo) {
   return L >= 512 && Lo >= 256 && Lo % 4 == 0 && L % 4 == 0 && rows >= 1024 && rows % GR_BM == 0 &&
          kpad * 4 * GR_BM < ((int64_t)1 << 32) && !std::getenv("EOFX_NO_MATMUL_NT");
 }
+// The work list of gram_nt_kernel (eofx_gram.hpp; tests/test_gram_plan_cpu.py holds its invariants).  The kernels read GramItem and GramTile as they stand here (GramTile in place
+// of HIP's int2: eofx_gram.hpp asserts size and layout).
+// work item: tile (bi, bj), first stage, number of stages (EVEN), output slot (tile-major: slot = tile * S + split)
+struct GramItem {
+  int bi, bj, st0, nst, slot, pad0, pad1, pad2;
+};
+struct GramTile {
+  int x, y;      // {bi, bj}
+};
+struct GramPlan {
+  int nti = 0, ntj = 0, T = 0, S = 1, st_per_split = 0, grid = 0;
+  std::vector<GramItem> items;   // [grid]: workgroup b -> item (XCD b % 8 walks its own patch of tiles split by split)
+  std::vector<GramTile> tiles;   // [T]: slot order
+};
+
+inline unsigned gram_morton(unsigned i, unsigned j) {
+  unsigned m = 0;
+  for (int b = 0; b < 12; ++b) m |= ((i >> b) & 1u) << (2 * b + 1) | ((j >> b) & 1u) << (2 * b);
+  return m;
+}
+
+// sym: only tiles bi <= bj (C = A A^T).  nst_total: stages (32 features each) of the contraction.
+// S <= 0: chosen here (rounds of 32 workgroups per XCD x stages per split, ~40 stages of fixed cost per item).
+inline void gram_plan_build(int nti, int ntj, bool sym, int nst_total, int S, GramPlan& pl) {
+  pl.nti = nti;
+  pl.ntj = ntj;
+  pl.tiles.clear();
+  for (int i = 0; i < nti; ++i)
+    for (int j = sym ? i : 0; j < ntj; ++j) pl.tiles.push_back(GramTile{i, j});
+  std::sort(pl.tiles.begin(), pl.tiles.end(), [](const GramTile& a, const GramTile& b) {
+    return gram_morton((unsigned)a.x, (unsigned)a.y) < gram_morton((unsigned)b.x, (unsigned)b.y);
+  });
+  const int T = (int)pl.tiles.size();
+  pl.T = T;
+  int lo[9];
+  for (int x = 0; x <= 8; ++x) lo[x] = (int)((int64_t)T * x / 8);
+  int cmax = 0;
+  for (int x = 0; x < 8; ++x) cmax = std::max(cmax, lo[x + 1] - lo[x]);
+  if (S <= 0) {
+    double best = 1e300;
+    for (int s = 1; s <= 16 && s <= nst_total; ++s) {
+      const int sps = ((nst_total + s - 1) / s + 1) / 2 * 2;
+      const int s_eff = (nst_total + sps - 1) / sps;
+      if (s_eff != s) continue;
+      const double rounds = (double)((cmax * s + 31) / 32);
+      const double cost = rounds * (sps + 40.0) + 2.0 * s;
+      if (cost < best * 0.97) {
+        best = cost;
+        S = s;
+      }
+    }
+  }
+  const int sps = ((nst_total + S - 1) / S + 1) / 2 * 2;     // even (nst_total is: kpad % 64 == 0)
+  S = (nst_total + sps - 1) / sps;
+  pl.S = S;
+  pl.st_per_split = sps;
+  const int W = cmax * S;
+  pl.grid = 8 * W;
+  pl.items.assign((size_t)pl.grid, GramItem{0, 0, 0, 0, 0, 0, 0, 0});
+  for (int x = 0; x < 8; ++x) {
+    const int cnt = lo[x + 1] - lo[x];
+    for (int s = 0; s < S; ++s)
+      for (int t = 0; t < cnt; ++t) {
+        const int w = s * cnt + t, tile = lo[x] + t;
+        const int st0 = s * sps, nst = std::min(sps, nst_total - st0);
+        pl.items[(size_t)8 * w + x] = GramItem{pl.tiles[tile].x, pl.tiles[tile].y, st0, nst, tile * S + s, 0, 0, 0};
+      }
+  }
+}
+
 // the statistics-carrying first pass of the fused fit (eofx_fit.hpp): in-place layout, the f16x3 passes, a 16-byte aligned field
 inline bool fit_first_eligible(int keep_raw, int prec_power, bool aligned16, int64_t n, int64_t P, int l) {
   return keep_raw == 2 && prec_power == EOFX_PREC_F16X3 && n < P && l > 0 && l < n && round_up(l, 32) <= 64 && l % 32 != 0 &&

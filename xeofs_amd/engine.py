@@ -184,16 +184,19 @@ class ResidentMatrix:
         raise_for(self.ctx.lib.eofx_mat_sumsq_f64(self.ctx.handle, self.handle, C.byref(out)), self.ctx.handle)
         return out.value
 
-    def gram(self, side: int = 0):
+    def gram(self, side: int = 0, out=None):
         """side 0: X X^T as an [n_pad, n_pad] float32 device tensor; side 1: X^T X [p_pad, p_pad]
-        (rows/columns beyond n / p are zero)."""
+        (rows/columns beyond n / p are zero).  out: a contiguous float32 device tensor of that shape to write into."""
         torch = _torch()
         if side and self.masked:
             raise NotImplementedError("feature-space Gram matrix of a masked in-place matrix")
         d = self.p_pad if side else self.n_pad
-        G = torch.empty((d, d), dtype=torch.float32, device=f"cuda:{self.ctx.device}")
-        raise_for(self.ctx.lib.eofx_mat_gram_f32(self.ctx.handle, self.handle, int(side), ptr(G)), self.ctx.handle)
-        return G
+        if out is None:
+            out = torch.empty((d, d), dtype=torch.float32, device=f"cuda:{self.ctx.device}")
+        elif tuple(out.shape) != (d, d) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 device tensor of shape ({d}, {d})")
+        raise_for(self.ctx.lib.eofx_mat_gram_f32(self.ctx.handle, self.handle, int(side), ptr(out)), self.ctx.handle)
+        return out
 
     def sample_gram(self):
         return self.gram(0)
