@@ -733,11 +733,18 @@ int eofx_panel_colargminmax_f32(eofx_ctx *ctx, const float *P, int64_t rows, int
  *   G = X^T (b * (b^2 - aux)), aux[j] = alpha * sum_r b_rj^2;  mode 1 (Promax regression terms,
  *   _rotation.py:62-69): G = B^T ((b/aux) |b/aux|^(power-1)), aux[j] = max_r |b_rj|.
  *   R, aux, G are device float64 (L x L, L, L x L); L = 32, 64 (one workgroup per row tile) or 128, 256 (G cut
- *   into column blocks of 64, one workgroup each; aux must be padded with 0 (even modes) / 1 (odd modes)).
+ *   into column blocks of 64, one workgroup each).  X has rows_pad rows of L floats; any row count is accepted.
+ *   Padding, at every width: with m < L modes the columns >= m of X, the rows and columns >= m of R are zero, and all L
+ *   entries of aux are read as they are: pad aux with 0 in the even modes and with 1 in the odd modes.  On a padding
+ *   column b = 0, so the even modes give t = 0 * (0 - aux) = 0 for any finite padding value, but the odd modes divide
+ *   by aux: a zero there is 0 / 0 and fills that column of G with NaN -- in both kernels alike, neither replaces the
+ *   value.  (The one difference: a 32-wide panel runs in the 64-column kernel, which supplies the padding of the 32
+ *   columns the panel does not have.)  With this padding the rows and columns >= m of G are exact zeros.
  *   modes 2 / 3: the same two steps for COMPLEX loadings held as a [Re (L/2) | Im (L/2)] panel, L >= 64 (the rotation of
  *   ComplexEOF / HilbertEOF models, eof_rotator.py:294-400): R is the real L x L embedding [[Rr, Ri], [-Ri, Rr]] of the
  *   complex rotation matrix (L x L), aux[j] = aux[j + L/2] the per-mode value, |b_j|^2 pairs column j with j + L/2, and G holds
- *   the four real blocks of X^H T = (Xr^T Tr + Xi^T Ti) + i (Xr^T Ti - Xi^T Tr).
+ *   the four real blocks of X^H T = (Xr^T Tr + Xi^T Ti) + i (Xr^T Ti - Xi^T Tr).  The padding rule above holds within
+ *   each half: columns [m, L/2) and [L/2 + m, L).
  * eofx_cpanel_colabsmax_f32: max over the rows of |column| for the L/2 complex columns of such a panel (device out). */
 int eofx_panel_row_normalize_f32(eofx_ctx *ctx, const float *P, int64_t rows_pad, int L, float *out);
 int eofx_panel_rot_step_f64(eofx_ctx *ctx, const float *X, int64_t rows_pad, int L, const double *R,
