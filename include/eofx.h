@@ -713,6 +713,12 @@ int eofx_hilbert_sumsq_f64(eofx_ctx *ctx, const eofx_mat *a, int padding, double
  * it never exposes its matvec).  final_pass selects the context's final-pass precision.                          */
 int eofx_cmat_mul_f32(eofx_ctx *ctx, const eofx_mat *A, const eofx_mat *B, int conj_left, const float *P_in, int L,
                       int final_pass, float *P_out);
+/* The same pass for the analytic signal Z = (I + i Hc) A of a resident real matrix, the way eofx_rsvd_hilbert_c64 runs it:
+ * Z^H W = A^T (W - i Hc^T W), Z Y = (I + i Hc)(A Y) with the resident operator of eofx_hilbert_operator_f32 (padding /
+ * decay_factor as in eofx_hilbert_f32) -- the imaginary part is never written.  Panels, L and final_pass as above; A may be
+ * an in-place matrix; n <= 16384 and a positive decay_factor with padding (EOFX_ERR_ARG otherwise).                  */
+int eofx_hilbert_cmat_mul_f32(eofx_ctx *ctx, const eofx_mat *A, int padding, double decay_factor, int conj_left,
+                              const float *P_in, int L, int final_pass, float *P_out);
 
 /* Complex panels are real panels [Re | Im] (Re in columns [0, L/2), Im in [L/2, L)).
  * With P1 = op(A) W and P2 = op(B) W for a complex matrix Z = A + iB (A, B real resident):

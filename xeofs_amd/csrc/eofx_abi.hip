@@ -4205,6 +4205,34 @@ extern "C" int eofx_cmat_mul_f32(eofx_ctx* ctx, const eofx_mat* A, const eofx_ma
   return EOFX_OK;
 }
 
+// The same pass for the analytic signal Z = (I + i Hc) A in operator mode (CplxOps::Hop, as inside eofx_rsvd_hilbert_c64): the
+// imaginary part is never written, Hc acts on the sample-side panel.  Limits as eofx_rsvd_hilbert_c64.
+extern "C" int eofx_hilbert_cmat_mul_f32(eofx_ctx* ctx, const eofx_mat* A, int padding, double decay_factor, int conj_left,
+                                         const float* Pin, int L, int final_pass, float* Pout) {
+  if (!ctx || !A || !Pin || !Pout) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (L != 64 && L != 128) return set_err(ctx, EOFX_ERR_ARG, "complex panels are 64 or 128 real columns wide");
+  if (padding && !(decay_factor > 0.0)) return set_err(ctx, EOFX_ERR_ARG, "decay_factor must be positive");
+  if (A->n > EOFX_HILBERT_OP_MAX_N)
+    return set_err(ctx, EOFX_ERR_ARG, "the resident Hilbert operator is limited to %d samples (got %lld)", EOFX_HILBERT_OP_MAX_N,
+                   (long long)A->n);
+  ENTER(ctx);
+  const int prec = final_pass ? ctx->prec_final : ctx->prec_power;
+  const eofx_mat* Hop = nullptr;
+  CHK(get_hilbert_operator(ctx, A->n, padding ? 1 : 0, decay_factor, &Hop));
+  const int64_t big = std::max(A->n_pad, A->p_pad);
+  // (the pass itself and the n x n x L product with the operator)
+  CHK(arena_reserve(ctx, c64_mul_scratch_bytes(A->n, A->p, A->n_pad, A->p_pad, L) +
+                             atb_scratch_bytes(A->n_pad, round_up(A->n, ATB_KG), L)));
+  ArenaScope scope(ctx);
+  ARENA(float, rot, (size_t)big * L);
+  ARENA(float, tmp, (size_t)big * L);
+  CplxOps ops{ctx, A, nullptr, L, rot, tmp, A->absmax};
+  ops.Hop = Hop;
+  CHK(conj_left ? ops.zh_mul(Pin, Pout, prec) : ops.z_mul(Pin, Pout, prec));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return EOFX_OK;
+}
+
 // U [n x k] and V [p x k] are complex64, row-major, interleaved (re, im); s [k] float32; all host|device.
 // omega: [min(n, p) x (k + n_oversamples)] REAL Gaussian start (host), as the reference's random_state would draw.
 //

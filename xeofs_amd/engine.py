@@ -972,12 +972,24 @@ def hilbert(ctx: Context, mat: ResidentMatrix, padding="exp", decay_factor: floa
     return B, (ResidentMatrix(ctx, hr) if want_real else None)
 
 
-def cmat_mul(ctx: Context, A: ResidentMatrix, B: ResidentMatrix, P, conj_left: bool, final: bool = False):
+def cmat_mul(ctx: Context, A: ResidentMatrix, B: ResidentMatrix, P, conj_left: bool, final: bool = False, out=None):
     """one pass of Z = A + iB over a [Re | Im] panel: Z^H P (conj_left, P on the sample side) or Z P -- one launch"""
     torch = _torch()
-    out = torch.empty((A.p_pad if conj_left else A.n_pad, P.shape[1]), dtype=torch.float32, device=P.device)
+    if out is None:
+        out = torch.empty((A.p_pad if conj_left else A.n_pad, P.shape[1]), dtype=torch.float32, device=P.device)
     raise_for(ctx.lib.eofx_cmat_mul_f32(ctx.handle, A.handle, B.handle, int(conj_left), ptr(P), P.shape[1], int(final),
                                         ptr(out)), ctx.handle)
+    return out
+
+
+def hilbert_cmat_mul(ctx: Context, A: ResidentMatrix, P, conj_left: bool, padding="exp", decay_factor: float = 0.2,
+                     final: bool = False, out=None):
+    """the same pass for Z = (I + i Hc) A, Hc the resident Hilbert operator (eofx_hilbert_cmat_mul_f32): Im is never written"""
+    torch = _torch()
+    if out is None:
+        out = torch.empty((A.p_pad if conj_left else A.n_pad, P.shape[1]), dtype=torch.float32, device=P.device)
+    raise_for(ctx.lib.eofx_hilbert_cmat_mul_f32(ctx.handle, A.handle, int(padding == "exp"), float(decay_factor),
+                                                int(conj_left), ptr(P), P.shape[1], int(final), ptr(out)), ctx.handle)
     return out
 
 
