@@ -584,6 +584,36 @@ int eofx_pairmin_f32(eofx_ctx *ctx, const float *T, int64_t p, int64_t n, int64_
  * The kernel reads the sample-contiguous layout of m where it lies (built on demand and kept: the caller may release it
  * again); the field is read only.  EOFX_ERR_ARG for a masked in-place matrix (layout mode 3).                           */
 int eofx_mat_pairmin_f32(eofx_ctx *ctx, const eofx_mat *m, const float *w, float *rmin, int32_t *partner);
+/* ---- the two operators of archetypal analysis (Cutler & Breiman 1994; Morup & Hansen 2012; xeofs_amd/single/archetypal.py,
+ * csrc/eofx_simplex.hpp) ----
+ * simplex_rows: V [r x m] a float32 device matrix (row stride ldv >= m), G the same shape (row stride ldg >= m) or NULL,
+ *   u[i, j]   = fmaf(-step, G[i, j], V[i, j])      (float32; u = V when G is NULL)
+ *   out[i, :] (float32, device, row stride ldo >= m) = the Euclidean projection of u[i, :] onto the probability simplex
+ *             {x >= 0, sum x = 1}: out[i, j] = max(u[i, j] - tau_i, 0), tau_i the solution of sum_j max(u[i, j] - tau, 0) = 1.
+ * tau_i comes from Michelot's fixed point in its monotone form: S = all j; tau = (sum_{j in S} u[i, j] - 1) / |S| in float64 with
+ * a fixed summation order; thr = the largest tau so far; S <- {j : u[i, j] > thr}; until |S| stands still (at most m rounds).
+ * tau_i is the last tau -- evaluated over its own active set -- and out[i, j] = (float)((double)u[i, j] - tau_i) for j in S,
+ * 0 elsewhere: rounded once.  A row whose u holds a NaN or an infinity comes back all NaN; no other row changes.  Where
+ * float64 cannot tell tau from the largest entry (S comes out empty) the limit is returned: 1 / c at the c entries equal to
+ * the largest, 0 elsewhere; m = 1 gives 1.  Rows of up to 1024 entries stay in the registers of one wave or a share of one,
+ * longer rows take one workgroup each with the row resident in LDS, read once and written once (simplex_plan).  No atomics:
+ * two runs are equal bit for bit.  out may alias V.  Nothing but out[i, 0 .. m) is written, nothing past column m of a row is
+ * read.  r == 0 is a no-op.  EOFX_ERR_ARG for m < 1, r < 0 or a stride below m; EOFX_ERR_SHAPE for m > 16384 (SIMPLEX_MMAX).  */
+int eofx_simplex_rows_f32(eofx_ctx *ctx, const float *V, int64_t r, int64_t m, int64_t ldv, const float *G, int64_t ldg,
+                          float step, float *out, int64_t ldo);
+/* simplex_pg: A and Q [n x k] float32 device matrices (row strides lda, ldq >= k), M [k x k] float64 row-major (host|device),
+ * rounded once to float32.  For every row i independently, iters times:
+ *   acc[j] = sum_l a[l] M[l, j]                    (a float32 fmaf chain from 0, l ascending)
+ *   u[j]   = fmaf(-inv_L, acc[j] - Q[i, j], a[j])  (float32)
+ *   a      = the projection of u onto the probability simplex, as above (float64 sums, j ascending)
+ * starting from a = A[i, :]; out[i, :] (float32, device, row stride ldo >= k) = the last a.  This is projected gradient descent
+ * on |x_i - a Z|^2 / 2 with Q = X Z^T and M = Z Z^T; with inv_L <= 1 / lambda_max(M) it never increases the objective.  a, Q[i, :]
+ * and u stay in the registers of one thread and M in LDS across the iterations: one launch.  A row that holds a NaN or an
+ * infinity comes back all NaN; no other row changes.  No atomics: two runs are equal bit for bit.  out may alias A.  Nothing
+ * past column k of a row is read or written.  n == 0 is a no-op.  EOFX_ERR_ARG for k < 1, iters < 1, n < 0 or a stride below k;
+ * EOFX_ERR_SHAPE for k > 32 (SIMPLEX_KMAX).                                                                               */
+int eofx_simplex_pg_f32(eofx_ctx *ctx, const float *A, int64_t lda, const float *Q, int64_t ldq, const double *M, float inv_L,
+                        int iters, int64_t n, int k, float *out, int64_t ldo);
 /* ---- the three operators of spectral EOF analysis (Towne, Schmidt & Colonius 2018; Schmidt et al. 2019;
  * xeofs_amd/single/spectral_eof.py, csrc/eofx_spectral.hpp).  Generic linear algebra: none of them knows about Fourier. ----
  * blockxform: T [p x n] a SERIES-MAJOR float32 device panel (row stride ld >= n), B [ncoef x n_fft] a float32 device matrix

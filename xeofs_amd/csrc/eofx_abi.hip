@@ -17,6 +17,7 @@
 #include "eofx_orderpos.hpp"
 #include "eofx_colquad.hpp"
 #include "eofx_pairmin.hpp"
+#include "eofx_simplex.hpp"
 #include "eofx_spectral.hpp"
 #include "eofx_pcmul.hpp"
 #include "eofx_viewcov.hpp"
@@ -5730,6 +5731,87 @@ extern "C" int eofx_mat_pairmin_f32(eofx_ctx* ctx, const eofx_mat* m, const floa
   ArenaScope scope(ctx);
   CHK(launch_pairmin(ctx, m->Xt, m->p, m->n, m->n_pad, w, rmin, partner));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  return EOFX_OK;
+}
+
+// ---- the two operators of archetypal analysis (csrc/eofx_simplex.hpp) ---------------------------------------------------
+template <int E>
+static void launch_simplex_reg(eofx_ctx* ctx, const SimplexPlan& pl, const float* V, int64_t r, int m, int64_t ldv, const float* G,
+                               int64_t ldg, float step, float* out, int64_t ldo) {
+  hipLaunchKernelGGL((simplex_rows_reg_kernel<E>), dim3((unsigned)pl.grid), dim3(pl.threads), 0, ctx->stream, V, r, m, ldv, G, ldg, step,
+                     out, ldo, pl.lanes);
+}
+
+extern "C" int eofx_simplex_rows_f32(eofx_ctx* ctx, const float* V, int64_t r, int64_t m, int64_t ldv, const float* G, int64_t ldg,
+                                     float step, float* out, int64_t ldo) {
+  if (!ctx) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (m < 1 || r < 0) return set_err(ctx, EOFX_ERR_ARG, "m must be >= 1 and r >= 0 (m = %lld, r = %lld)", (long long)m, (long long)r);
+  if (m > SIMPLEX_MMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the simplex projection takes rows of at most %d entries, got m = %lld", SIMPLEX_MMAX, (long long)m);
+  if (ldv < m || ldo < m || (G && ldg < m))
+    return set_err(ctx, EOFX_ERR_ARG, "a row stride is below m = %lld (ldv = %lld, ldg = %lld, ldo = %lld)", (long long)m, (long long)ldv,
+                   (long long)ldg, (long long)ldo);
+  const SimplexPlan pl = simplex_plan(r, m);
+  if (pl.grid > (int64_t)INT32_MAX) return set_err(ctx, EOFX_ERR_SHAPE, "too many rows for one launch: %lld", (long long)r);
+  if (r == 0) return EOFX_OK;
+  if (!V || !out || !is_device_ptr(V) || !is_device_ptr(out) || (G && !is_device_ptr(G)))
+    return set_err(ctx, EOFX_ERR_ARG, "V, G and out must be device buffers");
+  ENTER(ctx);
+  if (pl.tier == 0) {
+    switch (pl.epl) {
+      case 1: launch_simplex_reg<1>(ctx, pl, V, r, (int)m, ldv, G, ldg, step, out, ldo); break;
+      case 2: launch_simplex_reg<2>(ctx, pl, V, r, (int)m, ldv, G, ldg, step, out, ldo); break;
+      case 4: launch_simplex_reg<4>(ctx, pl, V, r, (int)m, ldv, G, ldg, step, out, ldo); break;
+      case 8: launch_simplex_reg<8>(ctx, pl, V, r, (int)m, ldv, G, ldg, step, out, ldo); break;
+      default: launch_simplex_reg<16>(ctx, pl, V, r, (int)m, ldv, G, ldg, step, out, ldo); break;
+    }
+  } else {
+    HIPCHK(hipFuncSetAttribute((const void*)simplex_rows_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SIMPLEX_MMAX * (int)sizeof(float)));
+    hipLaunchKernelGGL(simplex_rows_lds_kernel, dim3((unsigned)pl.grid), dim3(pl.threads), pl.lds, ctx->stream, V, r, (int)m, ldv, G, ldg,
+                       step, out, ldo);
+  }
+  KCHK();
+  return EOFX_OK;
+}
+
+template <int KP>
+static void launch_simplex_pg(eofx_ctx* ctx, const float* A, int64_t lda, const float* Q, int64_t ldq, const double* M, float inv_L, int iters,
+                              int64_t n, int k, float* out, int64_t ldo) {
+  hipLaunchKernelGGL((simplex_pg_kernel<KP>), dim3((unsigned)((n + SIMPLEX_PG_WG - 1) / SIMPLEX_PG_WG)), dim3(SIMPLEX_PG_WG), 0, ctx->stream, A,
+                     lda, Q, ldq, M, inv_L, iters, n, k, out, ldo);
+}
+
+extern "C" int eofx_simplex_pg_f32(eofx_ctx* ctx, const float* A, int64_t lda, const float* Q, int64_t ldq, const double* M, float inv_L,
+                                   int iters, int64_t n, int k, float* out, int64_t ldo) {
+  if (!ctx) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (k < 1 || n < 0 || iters < 1)
+    return set_err(ctx, EOFX_ERR_ARG, "k and iters must be >= 1 and n >= 0 (k = %d, iters = %d, n = %lld)", k, iters, (long long)n);
+  if (k > SIMPLEX_KMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the projected-gradient solver takes at most %d variables, got k = %d", SIMPLEX_KMAX, k);
+  if (lda < k || ldq < k || ldo < k)
+    return set_err(ctx, EOFX_ERR_ARG, "a row stride is below k = %d (lda = %lld, ldq = %lld, ldo = %lld)", k, (long long)lda, (long long)ldq,
+                   (long long)ldo);
+  if ((n + SIMPLEX_PG_WG - 1) / SIMPLEX_PG_WG > (int64_t)INT32_MAX) return set_err(ctx, EOFX_ERR_SHAPE, "too many rows for one launch: %lld", (long long)n);
+  if (n == 0) return EOFX_OK;
+  if (!A || !Q || !M || !out) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (!is_device_ptr(A) || !is_device_ptr(Q) || !is_device_ptr(out)) return set_err(ctx, EOFX_ERR_ARG, "A, Q and out must be device buffers");
+  ENTER(ctx);
+  const bool host_m = !is_device_ptr(M);
+  ArenaScope scope(ctx);
+  const size_t kk = (size_t)k * k;
+  if (host_m) CHK(arena_reserve(ctx, kk * 8 + 256));
+  const double* Md = nullptr;
+  CHK(stage_small(ctx, M, kk, "M", host_m, &Md));
+  switch (simplex_pg_width(k)) {
+    case 1: launch_simplex_pg<1>(ctx, A, lda, Q, ldq, Md, inv_L, iters, n, k, out, ldo); break;
+    case 2: launch_simplex_pg<2>(ctx, A, lda, Q, ldq, Md, inv_L, iters, n, k, out, ldo); break;
+    case 4: launch_simplex_pg<4>(ctx, A, lda, Q, ldq, Md, inv_L, iters, n, k, out, ldo); break;
+    case 8: launch_simplex_pg<8>(ctx, A, lda, Q, ldq, Md, inv_L, iters, n, k, out, ldo); break;
+    case 16: launch_simplex_pg<16>(ctx, A, lda, Q, ldq, Md, inv_L, iters, n, k, out, ldo); break;
+    default: launch_simplex_pg<32>(ctx, A, lda, Q, ldq, Md, inv_L, iters, n, k, out, ldo); break;
+  }
+  KCHK();
+  if (host_m) HIPCHK(hipStreamSynchronize(ctx->stream));       // (stage_small; a device M returns without one)
   return EOFX_OK;
 }
 

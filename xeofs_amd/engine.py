@@ -1592,6 +1592,72 @@ def mat_pairmin(ctx: Context, mat: ResidentMatrix, w, out=None):
 
 
 # --------------------------------------------------------------------------- #
+# the operators of archetypal analysis (eofx_simplex_rows_f32, eofx_simplex_pg_f32, csrc/eofx_simplex.hpp)       #
+# --------------------------------------------------------------------------- #
+SIMPLEX_MMAX = 16384        # entries of a row of simplex_rows
+SIMPLEX_KMAX = 32           # variables of a problem of simplex_pg
+
+
+def _simplex_out(out, like, what: str):
+    """`out` of a simplex operator: None (a new contiguous tensor), or a float32 device tensor of the shape of `like` with unit
+    column stride -- `like` itself among them (the operators work in place)"""
+    torch = _torch()
+    rows, cols = like.shape
+    if out is None:
+        return torch.empty((rows, cols), dtype=torch.float32, device=like.device)
+    return _check_out(out, rows, cols, (torch.float32,), what)
+
+
+def simplex_rows(ctx: Context, V, G=None, step: float = 0.0, out=None):
+    """out[i] = the Euclidean projection of u[i] = fmaf(-step, G[i], V[i]) (u = V without G) onto the probability simplex
+    {x >= 0, sum x = 1}, for every row of the float32 matrix V [r x m] -- a host array or a device tensor whose row stride may
+    exceed m; G the same shape.  -> a float32 device tensor [r x m] (`out` when given; it may be V).  tau in float64 from
+    Michelot's fixed point, the result rounded once; a row with a NaN or an infinity comes back all NaN; no atomics: two calls
+    are equal bit for bit (include/eofx.h)."""
+    torch = _torch()
+    V = device_panel(ctx, V, "V", (torch.float32,))
+    r, m = V.shape
+    if G is not None:
+        G = device_panel(ctx, G, "G", (torch.float32,))
+        if tuple(G.shape) != (r, m):
+            raise ValueError(f"G must have the shape of V {(r, m)}, got {tuple(G.shape)}")
+    out = _simplex_out(out, V, "float32")
+    if m < 1:
+        raise ValueError(f"rows of at least one entry are required, got m = {m}")
+    if r:       # (an empty tensor has no address to pass: r == 0 is a no-op of the entry as well)
+        raise_for(ctx.lib.eofx_simplex_rows_f32(ctx.handle, ptr(V), r, m, V.stride(0), ptr(G), G.stride(0) if G is not None else 0,
+                                                float(step), ptr(out), out.stride(0)), ctx.handle)
+    return out
+
+
+def simplex_pg(ctx: Context, A, Q, M, inv_L: float, iters: int, out=None):
+    """`iters` steps of projected gradient descent on |x_i - a Z|^2 / 2 over the probability simplex, for every row i
+    independently, in one launch: a <- P(a - inv_L (a M - Q[i])) from a = A[i], with Q = X Z^T [n x k] and M = Z Z^T [k x k].
+    A, Q: float32, host arrays or device tensors whose row stride may exceed k; M: float64, a host array or a device tensor
+    (rounded once to float32).  -> a float32 device tensor [n x k] (`out` when given; it may be A).  float32 fmaf chains, the
+    projection of simplex_rows; rows are independent; two calls are equal bit for bit (include/eofx.h)."""
+    torch = _torch()
+    A = device_panel(ctx, A, "A", (torch.float32,))
+    Q = device_panel(ctx, Q, "Q", (torch.float32,))
+    n, k = A.shape
+    if tuple(Q.shape) != (n, k):
+        raise ValueError(f"Q must have the shape of A {(n, k)}, got {tuple(Q.shape)}")
+    if hasattr(M, "data_ptr"):
+        M = M.to(torch.float64).contiguous()
+    else:
+        M = np.ascontiguousarray(M, dtype=np.float64)
+    if tuple(M.shape) != (k, k):
+        raise ValueError(f"M must be {(k, k)}, got {tuple(M.shape)}")
+    out = _simplex_out(out, A, "float32")
+    if k < 1:
+        raise ValueError(f"at least one variable is required, got k = {k}")
+    if n:
+        raise_for(ctx.lib.eofx_simplex_pg_f32(ctx.handle, ptr(A), A.stride(0), ptr(Q), Q.stride(0), ptr(M), float(inv_L), int(iters), n, k,
+                                              ptr(out), out.stride(0)), ctx.handle)
+    return out
+
+
+# --------------------------------------------------------------------------- #
 # the operators of spectral EOF analysis (eofx_blockxform_f32, eofx_mat_blockxform_f32, eofx_rowgram_f32, eofx_slabmul_f32, csrc/eofx_spectral.hpp) #
 # --------------------------------------------------------------------------- #
 BLOCKXFORM_NFFT_MAX = 16384       # samples per block

@@ -1,3 +1,4 @@
+from .archetypal import ArchetypalAnalysis  # noqa: F401
 from .dineof import DINEOF  # noqa: F401
 from .eeof import ExtendedEOF  # noqa: F401
 from .eof import EOF, ComplexEOF, HilbertEOF  # noqa: F401
