@@ -366,6 +366,22 @@ int eofx_panel_tmul_f32(eofx_ctx *ctx, const eofx_mat *m, const float *Zn, float
                         int precision); /* Yp[p_pad x L] = X^T Zn[n_pad x L]; EOFX_PREC_* */
 int eofx_panel_mul_f32(eofx_ctx *ctx, const eofx_mat *m, const float *Yp, float *Wn, int L,
                        int precision);
+/* The in-place X Y pass through the LDS-DMA kernel reads its panel as two fp16 planes.  Inside the single-matrix rSVD drivers
+ * the kernel that PRODUCES such a panel writes the planes itself, with a scale from a bound on max |panel| known beforehand
+ * (2 for a Cholesky-QR output; 2 sqrt(n) max |x'| for X'^T Z with Z orthonormal), instead of one more pass that splits the
+ * finished panel.  eofx_ctx_plane_stats: counts4 = {panels produced as planes by the X^T Z kernel, by the Cholesky-QR's product, X Y
+ * passes that took them as written, passes verified}, slack2 = {min, max} of bound / measured maximum over the verified passes (EOFX_AXB_CHECK_BOUND=1 in the
+ * environment: producers keep the float32 panel, every such pass measures it and fails if it exceeds the bound); the
+ * counters restart at every call.
+ * eofx_axb_planes_probe_f32 (tests): Y = X^T Zn [p_pad x L] (producer 0) or its Cholesky-QR (producer 1) on an in-place
+ * matrix, produced as planes with `bound` (0: the drivers' own), then W = X Y from those planes (w_prod), from the planes
+ * of the splitting pass with the same bound (w_split), from the register kernel with the same bound (w_reg) and with the
+ * measured maximum (w_max); planes_prod / planes_split: both sets of planes (host, plane_bytes each); y_out (device,
+ * optional): the float32 panel; bound_out (optional): the bound used.                                                  */
+int eofx_ctx_plane_stats(eofx_ctx *ctx, int64_t *counts4, double *slack2);
+int eofx_axb_planes_probe_f32(eofx_ctx *ctx, const eofx_mat *m, const float *Zn, int L, int producer, float bound,
+                              void *planes_prod, void *planes_split, size_t plane_bytes, float *w_prod, float *w_split,
+                              float *w_reg, float *w_max, float *y_out, float *bound_out);
 /* G[L x L] (device, float64) = P^T P, accumulated in float64 with a fixed tree. */
 int eofx_panel_gram_f64(eofx_ctx *ctx, const float *P, int64_t rows_pad, int L, double *G);
 /* Cholesky-QR step from a (possibly all-reduced) Gram matrix: out = P R^-1 with
@@ -791,8 +807,12 @@ int eofx_cpanel_colabsmax_f32(eofx_ctx *ctx, const float *P, int64_t rows, int L
  * out[rows x cols] (host float32) = np.random.RandomState(seed).normal(size=(rows, cols))
  * .astype(float32), bit for bit -- the Gaussian test matrix scikit-learn's randomized_svd draws
  * (MT19937 + numpy's legacy polar method), so `random_state=seed` means what it means in the
- * reference (decomposer.py:141-146).                                                        */
+ * reference (decomposer.py:141-146).
+ * The matrix is a function of (seed, rows, cols) alone: the last one drawn is kept in a process-wide
+ * cache (one entry, at most 64 MiB, thread safe) and a repeated call copies it out, the same bits.
+ * eofx_sketch_cache_drop releases that entry.                                                */
 int eofx_sketch_gaussian_f32(uint32_t seed, int64_t rows, int64_t cols, float *out);
+int eofx_sketch_cache_drop(void);
 
 /* ---- small host linear algebra used by the drivers ---------------------- */
 /* symmetric eigen-decomposition (Householder tridiagonalisation + implicit QL, float64):

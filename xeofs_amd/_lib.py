@@ -60,6 +60,8 @@ SIGNATURES = {
                                            _vp, _vp, _vp, _pd]),
     "eofx_panel_tmul_f32": (_int, [_vp, _vp, _vp, _vp, _int, _int]),
     "eofx_panel_mul_f32": (_int, [_vp, _vp, _vp, _vp, _int, _int]),
+    "eofx_ctx_plane_stats": (_int, [_vp, _vp, _vp]),
+    "eofx_axb_planes_probe_f32": (_int, [_vp, _vp, _vp, _int, _int, C.c_float, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eofx_panel_gram_f64": (_int, [_vp, _vp, _i64, _int, _vp]),
     "eofx_panel_cholqr_f32": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "eofx_panel_rinv_f64": (_int, [_vp, _vp, _int, _int, _vp]),
@@ -148,6 +150,7 @@ SIGNATURES = {
     "eofx_panel_rot_step_f64": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _int, C.c_double, _vp]),
     "eofx_cpanel_colabsmax_f32": (_int, [_vp, _vp, _i64, _int, _vp]),
     "eofx_sketch_gaussian_f32": (_int, [C.c_uint32, _i64, _i64, _vp]),
+    "eofx_sketch_cache_drop": (_int, []),
     "eofx_host_eigh_f64": (_int, [_vp, _int, _vp, _vp]),
     "eofx_host_zheigh_top_f64": (_int, [_vp, _vp, _int, _int, _vp, _vp, _vp]),
 }

@@ -162,6 +162,21 @@ struct eofx_ctx {
   _Float16* axb_planes = nullptr;
   size_t axb_planes_bytes = 0;
   int axb_dma = -1;   // -1 not decided, 0 off, 1 by size, 2 always (EOFX_AXB_DMA)
+  // The planes as already written by the panel's PRODUCER (atb_f16_kernel<.., PLANES>, panel_matmul_kernel<false, true>): which
+  // panel axb_planes holds, split with the scale of `bound` (a bound on max |panel| known before the producer ran; the panel's
+  // amax word holds it).  Kept beside amax_known and dropped with it: by amax_forget / amax_new of the panel and by the scopes.
+  struct PlanesKnown {
+    const float* panel = nullptr;
+    int L = 0;
+    int64_t K_all = 0;
+    float bound = 0.f;
+    bool f32 = false;     // the float32 panel was written as well
+  } planes_known;
+  int plane_check = -1;   // EOFX_AXB_CHECK_BOUND=1: producers keep the float32 panel and launch_axb verifies max |panel| <= bound
+  // counters of the producer route (eofx_ctx_plane_stats): panels produced as planes, X Y passes that took them as written,
+  // passes verified, and the smallest bound / true maximum seen by the verification
+  int64_t plane_produced[2] = {0, 0}, plane_consumed = 0, plane_checked = 0;   // produced: [0] by atb_f16_kernel, [1] by panel_matmul_kernel
+  double plane_min_slack = 0.0, plane_max_slack = 0.0;
   // the last eofx_fit_f32: [0] 1 when the statistics rode on the first pass, [1] ms of the non-pass work of the
   // fused preprocessor (probe, finalize, correction; HIP events, only with profiling on), [2] fallback reason
   double fit_info[4] = {0.0, 0.0, 0.0, 0.0};
@@ -483,6 +498,7 @@ struct AmaxScope {
   explicit AmaxScope(eofx_ctx* c) : ctx(c) {
     if (ctx->amax_depth++ == 0) {
       ctx->amax_known.clear();
+      ctx->planes_known = {};
       ctx->amax_next = 0;
       if (!ctx->amax_slots && hipMalloc((void**)&ctx->amax_slots, sizeof(unsigned) * EOFX_AMAX_SLOTS) != hipSuccess) {
         (void)hipGetLastError();
@@ -496,10 +512,14 @@ struct AmaxScope {
     }
   }
   ~AmaxScope() {
-    if (--ctx->amax_depth == 0) ctx->amax_known.clear();
+    if (--ctx->amax_depth == 0) {
+      ctx->amax_known.clear();
+      ctx->planes_known = {};
+    }
   }
 };
 static void amax_forget(eofx_ctx* ctx, const float* panel) {
+  if (ctx->planes_known.panel == panel) ctx->planes_known = {};
   for (size_t i = 0; i < ctx->amax_known.size(); ++i)
     if (ctx->amax_known[i].first == panel) {
       ctx->amax_known.erase(ctx->amax_known.begin() + i);
@@ -552,13 +572,39 @@ struct AffView {
   int64_t cols = 0;    // valid columns
   bool masked = false; // some features carry scale 0 = all-NaN grid points kept as zero columns (MASK kernels)
 };
+static bool axb_planes_reserve(eofx_ctx* ctx, size_t need);
+static bool plane_check_on(eofx_ctx* ctx);
+// A request to launch_atb: write the product ALSO as the fp16 planes of the in-place X Y pass that will read it next (see
+// eofx_ctx::planes_known).  bound: a bound on max |C| known before the launch (the scale comes from it); keep_f32: something besides
+// that pass reads the float32 panel.  Honoured for the raw view with one split, otherwise ignored (the pass splits the panel).
+struct PlaneReq {
+  float bound = 0.f;
+  bool keep_f32 = true;
+};
+struct PlaneOut {
+  _Float16* planes;
+  int64_t rows;
+  float bound;
+};
 template <int NB>
 static void launch_atb_variant(int prec, dim3 grid, hipStream_t st, const float* A, int64_t lda,
                                const float* B, int ldb, float* out, int L, int64_t M, int64_t K,
                                int64_t kps, int col_base, float a_scale, const float* b_absmax,
                                const AffView* aff = nullptr, const float* A2 = nullptr, const float* B2 = nullptr,
-                               int s_half = 0, int sym = 0, unsigned* amax_out = nullptr, int l_valid = 128) {
-  if (prec == EOFX_PREC_F16X3 && A2)
+                               int s_half = 0, int sym = 0, unsigned* amax_out = nullptr, int l_valid = 128,
+                               const PlaneOut* po = nullptr) {
+  if constexpr (NB > 2) po = nullptr;      // (launch_atb asks for planes in 64 / 32-column tiles only)
+  if (po) {      // the raw view, one split: the tile as float32 (unless out is null) AND as the fp16 planes of the X Y pass
+    constexpr int NP = NB > 2 ? 2 : NB;
+    if (aff->masked)
+      hipLaunchKernelGGL((atb_f16_kernel<NP, true, true, true>), grid, dim3(256), 0, st, A, lda, B, ldb, out, L, M, K, kps, col_base,
+                         a_scale, b_absmax, aff->aff, aff->ld, aff->rows, aff->cols, (const float*)nullptr, (const float*)nullptr, 0, 0, amax_out,
+                         l_valid, po->planes, po->rows, po->bound);
+    else
+      hipLaunchKernelGGL((atb_f16_kernel<NP, true, false, true>), grid, dim3(256), 0, st, A, lda, B, ldb, out, L, M, K, kps, col_base,
+                         a_scale, b_absmax, aff->aff, aff->ld, aff->rows, aff->cols, (const float*)nullptr, (const float*)nullptr, 0, 0, amax_out,
+                         l_valid, po->planes, po->rows, po->bound);
+  } else if (prec == EOFX_PREC_F16X3 && A2)
     hipLaunchKernelGGL(atb_f16_kernel<NB>, grid, dim3(256), 0, st, A, lda, B, ldb, out, L, M, K, kps, col_base,
                        a_scale, b_absmax, (const float*)nullptr, (int64_t)0, 0, (int64_t)0, A2, B2, s_half, 0, amax_out, l_valid);
   else if (prec == EOFX_PREC_F16X3 && aff && aff->masked)
@@ -589,7 +635,7 @@ static void launch_atb_variant(int prec, dim3 grid, hipStream_t st, const float*
 static int launch_atb(eofx_ctx* ctx, const float* A, int64_t lda, int64_t K, int64_t M,
                       const float* B, int ldb, int L, float* C, int prec = EOFX_PREC_F32,
                       float a_absmax = 0.f, const float* b_absmax_dev = nullptr, const AffView* aff = nullptr,
-                      const float* A2 = nullptr, const float* B2 = nullptr, int sym = 0) {
+                      const float* A2 = nullptr, const float* B2 = nullptr, int sym = 0, const PlaneReq* planes = nullptr) {
   if (aff && prec != EOFX_PREC_F16X3) return set_err(ctx, EOFX_ERR_ARG, "atb: the raw view needs the f16x3 kernel");
   if (A2 && (prec != EOFX_PREC_F16X3 || aff || !B2)) return set_err(ctx, EOFX_ERR_ARG, "atb: the two-matrix form needs the f16x3 kernel");
   if (M % ATB_BM || K % ATB_KG || L % 32 || L <= 0)
@@ -674,19 +720,42 @@ static int launch_atb(eofx_ctx* ctx, const float* A, int64_t lda, int64_t K, int
     return EOFX_OK;
   }
   unsigned* amax_direct = best_s == 1 ? amax_out : nullptr;   // single split: the kernels' own epilogues take the maximum
+  // The product as fp16 planes as well (PlaneReq): C's rows are the features of the in-place matrix whose X Y pass reads the
+  // panel next, aff->cols of them.  Needs the amax word (it carries the bound to that pass) and room for the planes.
+  PlaneOut po_{nullptr, 0, 0.f};
+  const PlaneOut* po = nullptr;
+  if (planes && aff && !sym && !A2 && best_s == 1 && amax_direct && planes->bound > 0.f && std::isfinite(planes->bound)) {
+    const int64_t K_all = round_up(aff->cols, AXB_KG);
+    if (K_all <= M && axb_planes_reserve(ctx, axb_planes_bytes(K_all, L))) {
+      po_ = {ctx->axb_planes, K_all, planes->bound};
+      po = &po_;
+      if (L % 64)      // the last column block is half a tile: its other 32 columns are zero, as axb_bsplit_kernel leaves them
+        HIPCHK(hipMemsetAsync(reinterpret_cast<char*>(ctx->axb_planes) + (size_t)(L / 64) * (K_all / AXB_KG) * AXB_PAIR_BYTES, 0,
+                              (size_t)(K_all / AXB_KG) * AXB_PAIR_BYTES, ctx->stream));
+      if (!planes->keep_f32 && !plane_check_on(ctx)) out = nullptr;
+    }
+  }
   for (int i = 0; i < tiles.n; ++i) {
     const ColTile& t = tiles.t[i];
     const dim3 grid(bx, best_s, t.count);
     if (t.width >= 96)       // a 128-column tile, or the partial one with 96 valid columns
       launch_atb_variant<4>(prec, grid, ctx->stream, A, lda, B, ldb, out, L, M, K, best_kps, t.col_base, a_scale, b_absmax_dev, aff, A2, B2, s_half,
-                            sym, amax_direct, t.width);
+                            sym, amax_direct, t.width, po);
     else if (t.width == 64)
       launch_atb_variant<2>(prec, grid, ctx->stream, A, lda, B, ldb, out, L, M, K, best_kps, t.col_base, a_scale, b_absmax_dev, aff, A2, B2, s_half,
-                            sym, amax_direct);
+                            sym, amax_direct, 128, po);
     else
       launch_atb_variant<1>(prec, grid, ctx->stream, A, lda, B, ldb, out, L, M, K, best_kps, t.col_base, a_scale, b_absmax_dev, aff, A2, B2, s_half,
-                            sym, amax_direct);
+                            sym, amax_direct, 128, po);
     KCHK();
+  }
+  if (po) {
+    ctx->planes_known.panel = C;
+    ctx->planes_known.L = L;
+    ctx->planes_known.K_all = po->rows;
+    ctx->planes_known.bound = po->bound;
+    ctx->planes_known.f32 = out != nullptr;
+    ++ctx->plane_produced[0];
   }
   if (ctx->profile) {
     HIPCHK(hipEventRecord(ev1, ctx->stream));
@@ -709,6 +778,65 @@ static int launch_atb(eofx_ctx* ctx, const float* A, int64_t lda, int64_t K, int
   return EOFX_OK;
 }
 
+
+// Does an in-place X Y pass of this size go through the LDS-DMA kernel (and so read its panel as fp16 planes)?
+// The LDS-DMA kernel costs a second launch and wins 3-5 % of the kernel: it pays from about 16 GB of field per pass on
+// (config 4 and 5; measured on one box each: 10000 x 1 036 800 -2.8 %, 10000 x 129 600 +0.9 %, 5000 x 259 200 +4.4 %,
+// profiles/r04_axb_dma_ab.txt)
+static bool axb_takes_dma(eofx_ctx* ctx, int64_t rows_pad, int64_t K_all) {
+  if (ctx->axb_dma < 0) {      // 0 never, 1 by size (the default), 2 always (EOFX_AXB_DMA=1: the tests run small shapes over it)
+    const char* ev = std::getenv("EOFX_AXB_DMA");
+    ctx->axb_dma = ev ? (atoi(ev) != 0 ? 2 : 0) : EOFX_AXB_DMA_DEFAULT;
+  }
+  return ctx->axb_dma == 2 || (ctx->axb_dma == 1 && (double)rows_pad * (double)K_all >= 4.0e9);
+}
+// room for `need` bytes of planes in the context's grow-only buffer (false: no memory for them)
+static bool axb_planes_reserve(eofx_ctx* ctx, size_t need) {
+  if (ctx->axb_planes_bytes >= need) return true;
+  (void)hipStreamSynchronize(ctx->stream);
+  if (ctx->axb_planes) (void)hipFree(ctx->axb_planes);
+  ctx->axb_planes = nullptr;
+  ctx->axb_planes_bytes = 0;
+  ctx->planes_known = {};
+  if (hipMalloc((void**)&ctx->axb_planes, need) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->axb_planes = nullptr;
+    return false;
+  }
+  ctx->axb_planes_bytes = need;
+  return true;
+}
+static bool plane_check_on(eofx_ctx* ctx) {
+  if (ctx->plane_check < 0) {
+    const char* ev = std::getenv("EOFX_AXB_CHECK_BOUND");
+    ctx->plane_check = ev ? atoi(ev) : 0;      // (2: also one line per verified pass on stderr)
+  }
+  return ctx->plane_check >= 1;
+}
+// EOFX_AXB_CHECK_BOUND=1 (tests, the slack measurement of docs/EXPERIMENTS.md): max |panel| of a produced panel against the
+// bound its planes were split with.  Synchronises; a panel above its bound is an error, not an fp16 overflow.
+static int plane_bound_check(eofx_ctx* ctx, const float* Y, int64_t K_all, int L, float bound) {
+  ArenaScope scope(ctx);
+  unsigned* bm = arena_alloc<unsigned>(ctx, 1);
+  if (!bm) return set_err(ctx, EOFX_ERR_NOMEM, "arena exhausted (panel max)");
+  HIPCHK(hipMemsetAsync(bm, 0, sizeof(unsigned), ctx->stream));
+  const int64_t total4 = K_all * (L / 4);
+  hipLaunchKernelGGL(panel_absmax_kernel, dim3((int)std::max<int64_t>(1, std::min<int64_t>((total4 + 1023) / 1024, 1024))),
+                     dim3(256), 0, ctx->stream, Y, K_all, L, (int64_t)L, bm);
+  KCHK();
+  float mx = 0.f;
+  HIPCHK(hipMemcpyAsync(&mx, bm, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ++ctx->plane_checked;
+  if (ctx->plane_check >= 2) fprintf(stderr, "eofx: X Y pass over produced planes: bound %g, max |panel| %g, bound / max %g\n", (double)bound, (double)mx, mx > 0.f ? (double)bound / (double)mx : 0.0);
+  if (!(mx <= bound)) return set_err(ctx, EOFX_ERR_LINALG, "panel maximum %g above the bound %g its fp16 planes were split with", (double)mx, (double)bound);
+  if (mx > 0.f) {
+    const double slack = (double)bound / (double)mx;
+    if (ctx->plane_min_slack == 0.0 || slack < ctx->plane_min_slack) ctx->plane_min_slack = slack;
+    if (slack > ctx->plane_max_slack) ctx->plane_max_slack = slack;
+  }
+  return EOFX_OK;
+}
 
 // W[n_pad x L] = X' Y with X' = the raw field [rows x cols] (ld) through the affine map, read in place (axb_f16_kernel).
 // Y: [>= round_up(cols, 64) x L] panel whose rows >= cols are zero.  L a multiple of 32.
@@ -760,33 +888,24 @@ static int launch_axb(eofx_ctx* ctx, const float* raw, int64_t ld, int64_t rows,
     HIPCHK(hipEventRecord(ev0, ctx->stream));
   }
   const int gx = plan.S > 1 ? 8 * rt * ((plan.S + 7) / 8) : rt;
-  if (ctx->axb_dma < 0) {      // 0 never, 1 by size (the default), 2 always (EOFX_AXB_DMA=1: the tests run small shapes over it)
-    const char* ev = std::getenv("EOFX_AXB_DMA");
-    ctx->axb_dma = ev ? (atoi(ev) != 0 ? 2 : 0) : EOFX_AXB_DMA_DEFAULT;
-  }
-  // The LDS-DMA kernel costs a second launch and the split pass (~20 us together) and wins 3-5 % of the kernel: it pays from
-  // about 16 GB of field per pass on (config 4 and 5; measured on one box each: 10000 x 1 036 800 -2.8 %, 10000 x 129 600
-  // +0.9 %, 5000 x 259 200 +4.4 %, profiles/r04_axb_dma_ab.txt)
-  bool dma = ctx->axb_dma == 2 || (ctx->axb_dma == 1 && (double)rows_pad * (double)K_all >= 4.0e9);
+  bool dma = axb_takes_dma(ctx, rows_pad, K_all);
   const int ncb = tiles.columns();
-  if (dma) {            // the panel's fp16 planes: one grow-only buffer per context (K_all x 64 ncb x 4 bytes)
-    const size_t need = (size_t)ncb * (size_t)(K_all / AXB_KG) * AXB_PAIR_BYTES;
-    if (ctx->axb_planes_bytes < need) {
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      if (ctx->axb_planes) (void)hipFree(ctx->axb_planes);
-      ctx->axb_planes = nullptr;
-      ctx->axb_planes_bytes = 0;
-      if (hipMalloc((void**)&ctx->axb_planes, need) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->axb_planes = nullptr;
-        dma = false;    // no room for the planes: the register path needs none (same bits)
-      } else {
-        ctx->axb_planes_bytes = need;
-      }
-    }
-  }
+  // the panel's fp16 planes: one grow-only buffer per context (K_all x 64 ncb x 4 bytes); no room for them: the register path
+  // needs none (same bits)
+  if (dma && !axb_planes_reserve(ctx, axb_planes_bytes(K_all, L))) dma = false;
   const int64_t pairs_all = K_all / AXB_KG;
-  if (dma) {   // the B panel as fp16 planes, moved by LDS-DMA (eofx_axb_dma.hpp); same bits in W
+  // planes the panel's producer has already written (rsvd_core asks for them): nothing to split.  bmax then holds the bound
+  // the producer split with, for this kernel's out_scale as for the register path's.
+  const eofx_ctx::PlanesKnown& pk = ctx->planes_known;
+  const bool produced = dma && pk.panel == Y && pk.L == L && pk.K_all == K_all && amax_get(ctx, Y) == bmax;
+  if (produced) {
+    ++ctx->plane_consumed;
+    if (pk.f32 && plane_check_on(ctx)) CHK(plane_bound_check(ctx, Y, K_all, L, pk.bound));
+  } else if (pk.panel == Y && !pk.f32) {
+    return set_err(ctx, EOFX_ERR_ARG, "axb: the panel exists as fp16 planes only and they cannot be used here");
+  }
+  if (dma && !produced) {   // the B panel as fp16 planes, moved by LDS-DMA (eofx_axb_dma.hpp); same bits in W
+    ctx->planes_known = {};
     hipLaunchKernelGGL(axb_bsplit_kernel, dim3((unsigned)((K_all + 31) / 32), ncb), dim3(256), 0, ctx->stream, Y, L, L, K_all, bmax,
                        ctx->axb_planes);
     KCHK();
@@ -843,8 +962,10 @@ static int launch_gram(eofx_ctx* ctx, const float* P, int64_t rows, int L, doubl
   KCHK();
   return EOFX_OK;
 }
+// planes_rows > 0 (with Lo == L): out is the tall panel of an in-place X Y pass over planes_rows features (a multiple of 64):
+// it is ALSO written as that pass's fp16 planes, with the scale of planes_bound (see eofx_ctx::planes_known)
 static int launch_matmul(eofx_ctx* ctx, const float* P, int64_t rows, int L, const double* Mx, int Lo,
-                         float* out, bool upper = false) {
+                         float* out, bool upper = false, int64_t planes_rows = 0, float planes_bound = 0.f) {
   int KW = (int)std::min<int64_t>(round_up(L, 64), 256);            // rows of Mx held in LDS at a time
   if (L > 256) {                                                    // windowed form: tuning hook (tools/wide_small_probe.py)
     static const int kw_env = std::getenv("EOFX_PMM_KW") ? atoi(std::getenv("EOFX_PMM_KW")) : 0;
@@ -858,7 +979,24 @@ static int launch_matmul(eofx_ctx* ctx, const float* P, int64_t rows, int L, con
   const int64_t units = (rows + 127) / 128;        // 4 waves x 32 rows
   const int64_t gx = L <= KW ? std::min<int64_t>(units, 1024) : units;   // windowed form: one group per wave
   dim3 grid((int)std::max<int64_t>(1, gx), (Lo + 63) / 64);
-  hipLaunchKernelGGL(panel_matmul_kernel<false>, grid, dim3(256), smem, ctx->stream, P, rows, L, Mx, Lo, out, KW, amax_new(ctx, out),
+  unsigned* amax_out = amax_new(ctx, out);
+  if (planes_rows > 0 && Lo == L && amax_out && planes_rows % AXB_KG == 0 && planes_rows <= rows && rows % 8 == 0 && planes_bound > 0.f &&
+      std::isfinite(planes_bound) && axb_planes_reserve(ctx, axb_planes_bytes(planes_rows, Lo))) {
+    if (smem > 64 * 1024)
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_matmul_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)smem));
+    hipLaunchKernelGGL((panel_matmul_kernel<false, true>), grid, dim3(256), smem, ctx->stream, P, rows, L, Mx, Lo, out, KW, amax_out,
+                       (int64_t)0, (int64_t)0, 1, (const float*)nullptr, upper ? 1 : 0, ctx->axb_planes, planes_rows, planes_bound);
+    KCHK();
+    ctx->planes_known.panel = out;
+    ctx->planes_known.L = Lo;
+    ctx->planes_known.K_all = planes_rows;
+    ctx->planes_known.bound = planes_bound;
+    ctx->planes_known.f32 = true;
+    ++ctx->plane_produced[1];
+    return EOFX_OK;
+  }
+  hipLaunchKernelGGL(panel_matmul_kernel<false>, grid, dim3(256), smem, ctx->stream, P, rows, L, Mx, Lo, out, KW, amax_out,
                      (int64_t)0, (int64_t)0, 1, (const float*)nullptr, upper ? 1 : 0);
   KCHK();
   return EOFX_OK;
@@ -896,15 +1034,18 @@ static int launch_xgram(eofx_ctx* ctx, const float* Pa, int64_t lda, int La, con
 static int launch_rinv(eofx_ctx* ctx, const double* G, int L, int l, double* Rinv);
 static size_t matmul_nt_scratch(eofx_ctx* ctx, int64_t rows, int L, int Lo);
 static int launch_matmul_nt(eofx_ctx* ctx, const float* P, int64_t rows, int L, const double* Mx, int Lo, float* out);
+// |q| <= 2 for every entry of a Cholesky-QR output: its columns are orthonormal to float32 rounding (dead columns are zero)
+constexpr float EOFX_CHOLQR_BOUND = 2.f;
+// planes_rows > 0: out is the tall panel of the in-place X Y pass that follows (see launch_matmul)
 static int launch_cholqr(eofx_ctx* ctx, const float* P, int64_t rows, int L, int l, const double* G,
-                         float* out) {
+                         float* out, int64_t planes_rows = 0) {
   ArenaScope scope(ctx);
   ARENA(double, Rinv, (size_t)L * L);
   CHK(launch_rinv(ctx, G, L, l, Rinv));
   // (Also for wide sketches the product with R^-1 stays in the float64 kernel: through fp16 planes -- 22-bit operands against the
   // matrix' largest entry, and R^-1 spans orders of magnitude -- Q lost orthonormality, 1.5e-6 instead of 4e-9 at 1510 columns,
   // for 0.75 ms per factorisation.)
-  return launch_matmul(ctx, P, rows, L, Rinv, L, out, /*upper=*/true);      // (R^-1 is upper triangular, zero below)
+  return launch_matmul(ctx, P, rows, L, Rinv, L, out, /*upper=*/true, planes_rows, EOFX_CHOLQR_BOUND);      // (R^-1 is upper triangular, zero below)
 }
 
 static int launch_colminmax(eofx_ctx* ctx, const float* P, int64_t rows, int L, float* mx, float* mn) {
@@ -1034,6 +1175,7 @@ extern "C" int eofx_ctx_trim(eofx_ctx* ctx) {
     (void)hipFree(ctx->axb_planes);
     ctx->axb_planes = nullptr;
     ctx->axb_planes_bytes = 0;
+    ctx->planes_known = {};
   }
   return EOFX_OK;
 }
@@ -1684,7 +1826,7 @@ extern "C" int eofx_resample_f32(eofx_ctx* ctx, const eofx_mat* src, const int64
 static bool tmul_nt_ok(const eofx_mat* m, int L);
 static size_t tmul_nt_scratch(eofx_ctx* ctx, const eofx_mat* m, int L);
 static int mat_tmul_nt(eofx_ctx* ctx, const eofx_mat* m, const float* Zn, float* Yp, int L);
-static int panel_tmul(eofx_ctx* ctx, const eofx_mat* m, const float* Zn, float* Yp, int L, int prec) {
+static int panel_tmul(eofx_ctx* ctx, const eofx_mat* m, const float* Zn, float* Yp, int L, int prec, const PlaneReq* planes = nullptr) {
   // panels of 512 columns and more (PCA pre-reduction): the MFMA-bound NT kernel over transposed fp16 planes (eofx_gram.hpp)
   if (prec == EOFX_PREC_F16X3 && tmul_nt_ok(m, L) && tmul_nt_scratch(ctx, m, L) > 0 &&
       ctx->arena_size - ctx->arena_off >= tmul_nt_scratch(ctx, m, L))   // (too little arena: the streaming tiles below, same result)
@@ -1696,7 +1838,8 @@ static int panel_tmul(eofx_ctx* ctx, const eofx_mat* m, const float* Zn, float* 
     av.rows = (int)m->n;
     av.cols = m->p;
     av.masked = m->masked;
-    return launch_atb(ctx, m->raw, m->raw_ld, round_up(m->n, ATB_KG), m->p_pad, Zn, L, L, Yp, prec, m->absmax, nullptr, &av);
+    return launch_atb(ctx, m->raw, m->raw_ld, round_up(m->n, ATB_KG), m->p_pad, Zn, L, L, Yp, prec, m->absmax, nullptr, &av, nullptr, nullptr, 0,
+                      planes);
   }
   CHK(ensure_X(ctx, m));
   return launch_atb(ctx, m->X, m->p_pad, round_up(m->n, ATB_KG), m->p_pad, Zn, L, L, Yp, prec, m->absmax);
@@ -1728,6 +1871,26 @@ static int ensure_active_pairs(eofx_ctx* ctx, const eofx_mat* cm) {
   return EOFX_OK;
 }
 
+// Yp = X'^T Zs for the panel_mul that follows, with Zs the output of a Cholesky-QR (orthonormal columns): should the product
+// be written as that pass's fp16 planes by its own kernel?  Yes where panel_mul will take the in-place LDS-DMA route for
+// certain.  The bound: |y| <= ||x'_f||_2 ||z_c||_2 <= sqrt(n) max |x'| ||z_c||_2 (Cauchy-Schwarz), with ||z_c||_2 <= 2 --
+// a factor 2 over the 1 + O(eps cond^2) of a Cholesky-QR output, which also covers the rounding of the product itself.
+// rows of the fp16 planes panel_mul(m, .., L, prec) reads its panel as, 0 unless it takes the in-place LDS-DMA route for certain
+static int64_t panel_mul_plane_rows(eofx_ctx* ctx, const eofx_mat* m, int L, int prec) {
+  if (m->Xt || !m->raw || !m->aff || prec != EOFX_PREC_F16X3) return 0;
+  if (!m->masked && L >= 96 && !std::getenv("EOFX_NO_WIDE_XT")) return 0;      // (panel_mul may build the sample layout)
+  const int64_t K_all = round_up(m->p, AXB_KG);
+  if (K_all * (int64_t)L >= ((int64_t)1 << 30) || 64 * m->raw_ld + K_all >= ((int64_t)1 << 30)) return 0;
+  return axb_takes_dma(ctx, m->n_pad, K_all) ? K_all : 0;
+}
+static bool panel_tmul_plane_req(eofx_ctx* ctx, const eofx_mat* m, int L, int prec, bool keep_f32, PlaneReq* req) {
+  if (m->X || panel_mul_plane_rows(ctx, m, L, prec) == 0) return false;
+  const float bound = 2.f * std::sqrt((float)m->n) * m->absmax;
+  if (!(bound > 0.f) || !std::isfinite(bound)) return false;
+  req->bound = bound;
+  req->keep_f32 = keep_f32;
+  return true;
+}
 static int panel_mul(eofx_ctx* ctx, const eofx_mat* m, const float* Yp, float* Wn, int L, int prec) {
   // Wide panels (96 columns and more: EOF with 55+ modes) on an in-place matrix: axb_f16 takes 64 columns per launch, so
   // every X Y pass would read the field L / 64 times, while the 128-column tile of atb_f16 over the sample-contiguous
@@ -1777,6 +1940,88 @@ extern "C" int eofx_panel_mul_f32(eofx_ctx* ctx, const eofx_mat* m, const float*
   ENTER(ctx);
   CHK(arena_reserve(ctx, atb_scratch_bytes(m->n_pad, round_up(m->p, ATB_KG), L)));
   return panel_mul(ctx, m, Yp, Wn, L, prec);
+}
+extern "C" int eofx_ctx_plane_stats(eofx_ctx* ctx, int64_t* counts4, double* slack2) {
+  if (!ctx) return EOFX_ERR_ARG;
+  if (counts4) {
+    counts4[0] = ctx->plane_produced[0];
+    counts4[1] = ctx->plane_produced[1];
+    counts4[2] = ctx->plane_consumed;
+    counts4[3] = ctx->plane_checked;
+  }
+  if (slack2) {
+    slack2[0] = ctx->plane_min_slack;
+    slack2[1] = ctx->plane_max_slack;
+  }
+  ctx->plane_produced[0] = ctx->plane_produced[1] = ctx->plane_consumed = ctx->plane_checked = 0;
+  ctx->plane_min_slack = ctx->plane_max_slack = 0.0;
+  return EOFX_OK;
+}
+// The producer route of the in-place X Y pass, laid open for the tests (tests/test_gpu_plane_producers.py): the tall panel
+// Y = X'^T Zn (producer 0: written as planes by atb_f16_kernel's epilogue) or its Cholesky-QR Q (producer 1: by
+// panel_matmul_kernel's), split with the scale of `bound` (0: the driver's own rule), and then W = X' Y four ways --
+// w_prod from the producer's planes, w_split from axb_bsplit_kernel's planes with the SAME bound, w_reg by the register
+// kernel with the same bound, w_max with the panel's measured maximum (today's scale).  planes_prod / planes_split: the
+// two sets of planes (host, plane_bytes each; eofx_plans.hpp axb_planes_bytes).  All W and y_out are device [.. x L].
+extern "C" int eofx_axb_planes_probe_f32(eofx_ctx* ctx, const eofx_mat* m, const float* Zn, int L, int producer, float bound,
+                                         void* planes_prod, void* planes_split, size_t plane_bytes, float* w_prod, float* w_split,
+                                         float* w_reg, float* w_max, float* y_out, float* bound_out) {
+  if (!ctx || !m || !Zn || !planes_prod || !planes_split || !w_prod || !w_split || !w_reg || !w_max || L <= 0 || L % 32 ||
+      (producer != 0 && producer != 1))
+    return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  ENTER(ctx);
+  const int prec = EOFX_PREC_F16X3;
+  const int64_t K_all = panel_mul_plane_rows(ctx, m, L, prec);
+  if (K_all == 0 || m->X) return set_err(ctx, EOFX_ERR_ARG, "planes probe: the matrix does not take the in-place LDS-DMA route");
+  if (plane_bytes != axb_planes_bytes(K_all, L)) return set_err(ctx, EOFX_ERR_ARG, "planes probe: plane_bytes");
+  CHK(arena_reserve(ctx, 2 * (size_t)m->p_pad * L * sizeof(float) + 4 * (size_t)L * L * sizeof(double) + (size_t)(4 * gram_parts(m->p_pad, L) + 1) * L * L * sizeof(double) +
+                             std::max(atb_scratch_bytes(m->p_pad, round_up(m->n, ATB_KG), L), atb_scratch_bytes(m->n_pad, K_all, L)) + 65536));
+  ArenaScope scope(ctx);
+  AmaxScope amax_scope(ctx);
+  ARENA(float, Y0, (size_t)m->p_pad * L);
+  ARENA(float, Y1, (size_t)m->p_pad * L);
+  ARENA(double, G, (size_t)L * L);
+  float* Y = Y0;
+  PlaneReq req;
+  if (producer == 0) {
+    if (!panel_tmul_plane_req(ctx, m, L, prec, true, &req)) return set_err(ctx, EOFX_ERR_ARG, "planes probe: no request");
+    if (bound > 0.f) req.bound = bound;
+    CHK(panel_tmul(ctx, m, Zn, Y0, L, prec, &req));
+  } else {
+    CHK(panel_tmul(ctx, m, Zn, Y0, L, prec));
+    CHK(launch_gram(ctx, Y0, m->p_pad, L, G));
+    if (bound > 0.f) {
+      ArenaScope inner(ctx);
+      ARENA(double, Rinv, (size_t)L * L);
+      CHK(launch_rinv(ctx, G, L, L, Rinv));
+      CHK(launch_matmul(ctx, Y0, m->p_pad, L, Rinv, L, Y1, true, K_all, bound));
+    } else {
+      CHK(launch_cholqr(ctx, Y0, m->p_pad, L, L, G, Y1, K_all));
+    }
+    Y = Y1;
+  }
+  const eofx_ctx::PlanesKnown pk = ctx->planes_known;
+  if (pk.panel != Y || pk.K_all != K_all || pk.L != L) return set_err(ctx, EOFX_ERR_ARG, "planes probe: the producer wrote no planes");
+  if (bound_out) *bound_out = pk.bound;
+  HIPCHK(hipMemcpyAsync(planes_prod, ctx->axb_planes, plane_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (y_out) HIPCHK(hipMemcpyAsync(y_out, Y, sizeof(float) * (size_t)m->p_pad * L, hipMemcpyDeviceToDevice, ctx->stream));
+  CHK(panel_mul(ctx, m, Y, w_prod, L, prec));
+  if (ctx->planes_known.panel != Y) return set_err(ctx, EOFX_ERR_ARG, "planes probe: the planes were not taken as written");
+  ctx->planes_known = {};                                      // the same bound (the panel's amax word), split by axb_bsplit_kernel
+  HIPCHK(hipMemsetAsync(ctx->axb_planes, 0xff, plane_bytes, ctx->stream));
+  CHK(panel_mul(ctx, m, Y, w_split, L, prec));
+  HIPCHK(hipMemcpyAsync(planes_split, ctx->axb_planes, plane_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  const int dma_mode = ctx->axb_dma;
+  ctx->axb_dma = 0;                                            // the register kernel, same bound
+  int rc = panel_mul(ctx, m, Y, w_reg, L, prec);
+  if (rc == EOFX_OK) {
+    amax_forget(ctx, Y);                                       // ... and with the maximum measured from the panel
+    rc = panel_mul(ctx, m, Y, w_max, L, prec);
+  }
+  ctx->axb_dma = dma_mode;
+  if (rc != EOFX_OK) return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return EOFX_OK;
 }
 extern "C" int eofx_panel_gram_f64(eofx_ctx* ctx, const float* P, int64_t rows_pad, int L, double* G) {
   if (!ctx || !P || !G || L % 32) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
@@ -1843,6 +2088,13 @@ struct LinOp {
   int64_t tall, small, tall_pad, small_pad;
   std::function<int(const float*, float*, int, int)> fwd;  // tall panel  = A   * small panel (.., L, prec)
   std::function<int(const float*, float*, int, int)> bwd;  // small panel = A^T * tall panel
+  // optional: fwd for a tall panel that goes to bwd as it is (a power iteration that does not re-orthonormalise it) and may be
+  // written in whatever form bwd reads -- (.., L, prec, keep): keep = something else reads the float32 panel too.  The small
+  // panel is then the output of a Cholesky-QR.  Drivers that leave it empty keep the plain fwd everywhere.
+  std::function<int(const float*, float*, int, int, bool)> fwd_to_bwd;
+  // optional: does bwd(.., L, prec) read its tall panel as the fp16 planes of the in-place X Y pass (eofx_ctx::planes_known)?
+  // Then the Cholesky-QR that produces such a panel writes them.  Its answer: the plane rows (0 = no).
+  std::function<int64_t(int, int)> bwd_plane_rows;
   // rows of the tall side sharded over ranks (eofx_fit_sharded_f32): every L x L float64 Gram matrix of a tall panel is
   // summed over the ranks by this hook (count doubles, device, in place, stream order); bwd then includes its own reduction
   std::function<int(double*, int64_t)> reduce_tall_gram;
@@ -2006,12 +2258,14 @@ static int rsvd_core(eofx_ctx* ctx, const LinOp& op, int k, int l, int n_iter, c
 
   CHK(import_panel(ctx, omega, op.small, l, Zs, op.small_pad, L));
   bool first_done = false;
-  auto fwd = [&](const float* z, float* y, int prec) -> int {
+  // to_bwd: 0 plain, 1 y goes to bwd as it is but is read here as well, 2 y goes to bwd and nowhere else
+  auto fwd = [&](const float* z, float* y, int prec, int to_bwd = 0) -> int {
     if (first_fwd && !first_done) {
       first_done = true;
       return (*first_fwd)(z, y, L);
     }
     first_done = true;
+    if (to_bwd && op.fwd_to_bwd) return op.fwd_to_bwd(z, y, L, prec, to_bwd == 1);
     return op.fwd(z, y, L, prec);
   };
   auto gram_tall = [&](const float* Pn, double* Gout) -> int {
@@ -2040,7 +2294,9 @@ static int rsvd_core(eofx_ctx* ctx, const LinOp& op, int k, int l, int n_iter, c
   bool peaked_pending = false;
   int rc = EOFX_OK;
   for (int it = 0; it < (range ? 0 : n_iter) && rc == EOFX_OK; ++it) {
-    rc = fwd(Zs, Yt, pp);
+    // from the second iteration on the tall panel goes straight to bwd unless the spectrum is peaked -- a question still open
+    // while the second product is launched (the Gram matrix of Yt may then be wanted: its float32 form is kept)
+    rc = fwd(Zs, Yt, pp, it == 0 ? 0 : peaked_pending ? 1 : orth_rest ? 0 : 2);
     if (rc != EOFX_OK) break;
     if (peaked_pending) {
       peaked_pending = false;
@@ -2050,7 +2306,7 @@ static int rsvd_core(eofx_ctx* ctx, const LinOp& op, int k, int l, int n_iter, c
     }
     if (it == 0 || orth_rest) {
       if ((rc = gram_tall(Yt, G)) != EOFX_OK) break;
-      if ((rc = launch_cholqr(ctx, Yt, op.tall_pad, L, l, G, Qt)) != EOFX_OK) break;
+      if ((rc = launch_cholqr(ctx, Yt, op.tall_pad, L, l, G, Qt, op.bwd_plane_rows ? op.bwd_plane_rows(L, pp) : 0)) != EOFX_OK) break;
       rc = op.bwd(Qt, Ws, L, pp);
     } else {
       rc = op.bwd(Yt, Ws, L, pp);
@@ -2083,7 +2339,7 @@ static int rsvd_core(eofx_ctx* ctx, const LinOp& op, int k, int l, int n_iter, c
   if (range) CHK((*range)(Zs, Yt, L));
   else CHK(fwd(Zs, Yt, pp));
   CHK(gram_tall(Yt, G));
-  CHK(launch_cholqr(ctx, Yt, op.tall_pad, L, l, G, Qt));      // Q1
+  CHK(launch_cholqr(ctx, Yt, op.tall_pad, L, l, G, Qt, op.bwd_plane_rows ? op.bwd_plane_rows(L, pf) : 0));      // Q1
   CHK(gram_tall(Qt, G));
   CHK(launch_rinv(ctx, G, L, l, R2));                          // R2^-1
   // B^T = A^T Q  (small x l);  B B^T = (B^T)^T (B^T)
@@ -2291,6 +2547,11 @@ extern "C" int eofx_rsvd_f32(eofx_ctx* ctx, const eofx_mat* m, int k, int n_over
     op = {p, n, m->p_pad, m->n_pad,
           [&](const float* z, float* y, int L, int pr) { return panel_tmul(ctx, m, z, y, L, pr); },
           [&](const float* y, float* w, int L, int pr) { return panel_mul(ctx, m, y, w, L, pr); }};
+    op.fwd_to_bwd = [&](const float* z, float* y, int L, int pr, bool keep) {
+      PlaneReq req;
+      return panel_tmul(ctx, m, z, y, L, pr, panel_tmul_plane_req(ctx, m, L, pr, keep, &req) ? &req : nullptr);
+    };
+    op.bwd_plane_rows = [&](int L, int pr) { return panel_mul_plane_rows(ctx, m, L, pr); };
   } else {
     op = {n, p, m->n_pad, m->p_pad,
           [&](const float* z, float* y, int L, int pr) { return panel_mul(ctx, m, z, y, L, pr); },
@@ -2563,6 +2824,11 @@ static int fit_fused(eofx_ctx* ctx, const float* Xd, int64_t n, int64_t P, int c
   LinOp op = {P, n, p_pad, n_pad,
               [&](const float* z, float* y, int LL, int pr) { return panel_tmul(ctx, m, z, y, LL, pr); },
               [&](const float* y, float* w, int LL, int pr) { return panel_mul(ctx, m, y, w, LL, pr); }};
+  op.fwd_to_bwd = [&](const float* z, float* y, int LL, int pr, bool keep) {
+    PlaneReq req;
+    return panel_tmul(ctx, m, z, y, LL, pr, panel_tmul_plane_req(ctx, m, LL, pr, keep, &req) ? &req : nullptr);
+  };
+  op.bwd_plane_rows = [&](int LL, int pr) { return panel_mul_plane_rows(ctx, m, LL, pr); };
   RsvdOut ro;
   rc = rsvd_core(ctx, op, k, l, n_iter, omega, ro, &first);
   if (rc != EOFX_OK) return rc;
@@ -4823,6 +5089,10 @@ extern "C" int eofx_mat_sumsq_f64(eofx_ctx* ctx, const eofx_mat* m, double* out)
 extern "C" int eofx_sketch_gaussian_f32(uint32_t seed, int64_t rows, int64_t cols, float* out) {
   if (!out || rows < 0 || cols < 0) return EOFX_ERR_ARG;
   eofx_sketch::gaussian_f32(seed, rows, cols, out);
+  return EOFX_OK;
+}
+extern "C" int eofx_sketch_cache_drop(void) {
+  eofx_sketch::sketch_memo_drop();
   return EOFX_OK;
 }
 

@@ -29,9 +29,8 @@ namespace eofx {
 // and map-triple loads are inline assembly into v176 .. v251, the pair id of a masked matrix into v252; the DMA itself is
 // the builtin (with nothing else of the compiler's in flight it adds no waits of its own).  See the file header for why.
 // ---------------------------------------------------------------------------------
-constexpr int AXB_PAIR_BYTES = 2 * 8 * 64 * 16;   // one feature pair (64 features) x 64 columns, two fp16 planes
-
-// planes[cb][P][plane][g][slot][8]: element (k = 64 P + 8 g + t, column 64 cb + c) at slot c ^ ((c >> 3) & 7), half t.
+// planes[cb][P][plane][g][slot][8]: element (k = 64 P + 8 g + t, column 64 cb + c) at slot c ^ ((c >> 3) & 7), half t
+// (axb_plane_offset and AXB_PAIR_BYTES, eofx_plans.hpp: the one statement of the layout for everything that WRITES planes).
 // Columns >= L are zero.  grid = (K_all / 32, column blocks), block = 256 = 4 k-groups x 64 columns.
 __global__ __launch_bounds__(256) void axb_bsplit_kernel(const float* __restrict__ B, int ldb, int L, int64_t K_all,
                                                           const float* __restrict__ b_absmax, _Float16* __restrict__ planes) {
@@ -54,11 +53,9 @@ __global__ __launch_bounds__(256) void axb_bsplit_kernel(const float* __restrict
     hi[t >> 1] = __builtin_bit_cast(unsigned, h);
     lo[t >> 1] = __builtin_bit_cast(unsigned, l);
   }
-  const int64_t P = kg >> 3;
-  const int g = (int)(kg & 7), slot = c ^ ((c >> 3) & 7);
-  char* base = reinterpret_cast<char*>(planes) + ((int64_t)cb * (K_all / AXB_KG) + P) * AXB_PAIR_BYTES + (g * 64 + slot) * 16;
+  char* base = reinterpret_cast<char*>(planes) + axb_plane_offset(cb, K_all, kg * 8, c, 0);
   *reinterpret_cast<u32x4*>(base) = hi;
-  *reinterpret_cast<u32x4*>(base + 8192) = lo;
+  *reinterpret_cast<u32x4*>(base + AXB_PLANE_BYTES) = lo;
 }
 
 template <int NQ, int DBG = 0, bool MASK = false>

@@ -414,7 +414,13 @@ __device__ __forceinline__ float f16_scale_for(float m) {
 // kept as zero columns instead of being compacted away: their bits are ANDed to +0 before the map, so NaN never reaches
 // the matrix cores (one v_and per element; a NaN inside a VALID feature still propagates, as it must).
 // amax_out (may be null; single split only): max |C| by atomicMax on the float bits -- the next pass' panel maximum.
-template <int NB, bool AFF = false, bool MASK = false>
+// PLANES (single split only): the epilogue ALSO writes the tile as the hi / lo fp16 planes the X Y pass reads by LDS-DMA
+// (axb_plane_offset, eofx_plans.hpp) -- the split of axb_bsplit_kernel, bit for bit, with the scale of plane_bound, a bound
+// on max |C| known BEFORE the launch (the scale needs a power of two no element exceeds, not the maximum) -- for the rows
+// below plane_rows.  A lane owns 8 consecutive features of a column (acc[0..3][q][r], acc[0..3][q][r + 1], r even): one
+// 16-byte unit of a plane per store, no LDS.  C may then be null (nothing but the X Y pass reads the panel: no float32
+// store), and amax_out receives the bound: the scalar every consumer of the panel derives its scale from.
+template <int NB, bool AFF = false, bool MASK = false, bool PLANES = false>
 __global__ __launch_bounds__(256, NB > 2 ? 1 : 2) void atb_f16_kernel(const float* __restrict__ A, int64_t lda,
                                                           const float* __restrict__ B, int ldb,
                                                           float* __restrict__ C, int ldc, int64_t M,
@@ -425,7 +431,10 @@ __global__ __launch_bounds__(256, NB > 2 ? 1 : 2) void atb_f16_kernel(const floa
                                                           int64_t aff_ld = 0, int a_rows = 0, int64_t a_cols = 0,
                                                           const float* A2 = nullptr, const float* B2 = nullptr,
                                                           int s_half = 0, int sym = 0,
-                                                          unsigned* __restrict__ amax_out = nullptr, int l_valid = 128) {
+                                                          unsigned* __restrict__ amax_out = nullptr, int l_valid = 128,
+                                                          void* __restrict__ planes = nullptr, int64_t plane_rows = 0,
+                                                          float plane_bound = 0.f) {
+  // (planes is a void*: with a _Float16 in the signature the profiler's tables list the kernel under its mangled name)
   // l_valid (NB = 4 only): columns of this 128-column tile that exist in B and C (96 for the tail of a 96 / 224-column
   // panel: one partial wide tile instead of a 64- and a 32-column launch that would each read the field again).
   // Two-matrix form (complex passes, eofx_rsvd_c64): splits [s_half, 2 s_half) stream a second matrix A2 (same shape)
@@ -632,17 +641,52 @@ __global__ __launch_bounds__(256, NB > 2 ? 1 : 2) void atb_f16_kernel(const floa
 #undef EOFX_STORE_B
 
   float* Cs = C + (int64_t)blockIdx.y * M * ldc;
+  if (!PLANES || C != nullptr) {
 #pragma unroll
-  for (int j = 0; j < 4; ++j)
+    for (int j = 0; j < 4; ++j)
 #pragma unroll
-    for (int q = 0; q < NB; ++q)
+      for (int q = 0; q < NB; ++q)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int ii = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const int64_t m = m0 + 4 * ii + j;
-        if (NB < 4 || 32 * q + li < l_valid) Cs[m * ldc + bcol0 + 32 * q + li] = acc[j][q][r] * out_scale;
+        for (int r = 0; r < 16; ++r) {
+          const int ii = (r & 3) + 8 * (r >> 2) + 4 * lh;
+          const int64_t m = m0 + 4 * ii + j;
+          if (NB < 4 || 32 * q + li < l_valid) Cs[m * ldc + bcol0 + 32 * q + li] = acc[j][q][r] * out_scale;
+        }
+  }
+  if constexpr (PLANES) {
+    // features m0 + 4 ii + j with ii = (r & 3) + 8 (r >> 2) + 4 lh: for even r, (r, j), (r + 1, j), j = 0 .. 3, are the eight
+    // features m0 + 32 (r >> 2) + 16 lh + 4 (r & 3) + {0 .. 7} -- half t of the unit is acc[t & 3][q][r + (t >> 2)]
+    const float p_scale = f16_scale_for(plane_bound);
+    char* const pb = reinterpret_cast<char*>(planes);
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      const int col = bcol0 + 32 * q + li;
+      if (NB < 4 || 32 * q + li < l_valid) {
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+          const int64_t k = m0 + 32 * (r >> 2) + 16 * lh + 4 * (r & 3);
+          if (k < plane_rows) {
+            u32x4 hi, lo;
+#pragma unroll
+            for (int t = 0; t < 8; t += 2) {
+              const float v0 = (acc[t & 3][q][r + (t >> 2)] * out_scale) * p_scale;
+              const float v1 = (acc[(t + 1) & 3][q][r + (t >> 2)] * out_scale) * p_scale;
+              const fp16x2_t h = cvt_pk_rn(v0, v1);
+              fp16x2_t l;
+              l[0] = (__fp16)__builtin_fmaf((float)h[0], m1, v0);
+              l[1] = (__fp16)__builtin_fmaf((float)h[1], m1, v1);
+              hi[t >> 1] = __builtin_bit_cast(unsigned, h);
+              lo[t >> 1] = __builtin_bit_cast(unsigned, l);
+            }
+            char* base = pb + axb_plane_offset(col >> 6, plane_rows, k, col & 63, 0);
+            *reinterpret_cast<u32x4*>(base) = hi;
+            *reinterpret_cast<u32x4*>(base + AXB_PLANE_BYTES) = lo;
+          }
+        }
       }
-  if (amax_out) {
+    }
+    if (amax_out && blockIdx.x == 0 && blockIdx.z == 0 && tid == 0) *amax_out = __float_as_uint(plane_bound);
+  } else if (amax_out) {
     float mx = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -1620,14 +1664,23 @@ constexpr int PMM_LD = 66;   // doubles per staged row of Mx
 // P + (c / cpb) * slab + (c % cpb) * 64 with row stride ldp (a wide row-major panel: cpb = all its chunks, ldp = its width; a
 // stack of separate panels of cpb chunks each: slab = rows_pad * 64 cpb, ldp = 64 cpb), and with `sub` the kernel writes
 // sub - P Mx (a projection step).
-template <bool GEN = false>
+// PLANES (not GEN; Lo = the panel width of an in-place X Y pass): the result ALSO as that pass's hi / lo fp16 planes
+// (axb_plane_offset, eofx_plans.hpp), split from the float32-rounded values exactly as axb_bsplit_kernel splits them, with the
+// scale of plane_bound -- a bound on max |out| known before the launch (2 for the Q of a Cholesky-QR) -- for the rows below
+// plane_rows.  The rows of a 32-row group are then dealt to the MFMA row slots so that a lane ends up with 8 CONSECUTIVE rows
+// of a column (slot a of tile t = row 8 (a & 3) + 4 t + (a >> 2) instead of 16 t + a): one 16-byte unit of a plane per store,
+// no LDS and no cross-lane traffic; which lane computes a row does not change the row's value.  amax_out receives the bound.
+template <bool GEN = false, bool PLANES = false>
 __global__ __launch_bounds__(256) void panel_matmul_kernel(const float* __restrict__ P,
                                                            int64_t rows, int L,
                                                            const double* __restrict__ Mx, int Lo,
                                                            float* __restrict__ out, int KW,
                                                            unsigned* __restrict__ amax_out = nullptr,
                                                            int64_t ldp = 0, int64_t slab = 0, int cpb = 1,
-                                                           const float* __restrict__ sub = nullptr, int upper = 0) {
+                                                           const float* __restrict__ sub = nullptr, int upper = 0,
+                                                           void* __restrict__ planes = nullptr, int64_t plane_rows = 0,
+                                                           float plane_bound = 0.f) {
+  static_assert(!(GEN && PLANES), "the plane epilogue belongs to the plain form");
   // upper != 0: Mx is upper triangular (the R^-1 of a Cholesky-QR): output column block b needs the K chunks 0 .. b only --
   // half the products of a wide panel; the skipped ones are exact zeros, the result is the same bits
   extern __shared__ __attribute__((aligned(16))) double Ms[];
@@ -1651,7 +1704,7 @@ __global__ __launch_bounds__(256) void panel_matmul_kernel(const float* __restri
   auto fetch = [&](bool valid, int64_t g, int kc, f32x4 (&a)[2][4]) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      const int64_t r = 32 * g + 16 * t + li;
+      const int64_t r = 32 * g + (PLANES ? 8 * (li & 3) + 4 * t + (li >> 2) : 16 * t + li);
 #pragma unroll
       for (int tt = 0; tt < 4; ++tt) {
         const int k = kc + 16 * tt + 4 * lk;
@@ -1691,7 +1744,7 @@ __global__ __launch_bounds__(256) void panel_matmul_kernel(const float* __restri
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int64_t row = 32 * g + 16 * t + lk + 4 * r;
+          const int64_t row = 32 * g + (PLANES ? 8 * lk + 4 * t + r : 16 * t + lk + 4 * r);
           if (row >= rows) continue;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
@@ -1706,6 +1759,36 @@ __global__ __launch_bounds__(256) void panel_matmul_kernel(const float* __restri
             }
           }
         }
+      if constexpr (PLANES) {      // this lane's rows 32 g + 8 lk + {0 .. 7} (half 4 t + r) of the columns c0 + 16 q + li
+        const int64_t k = 32 * g + 8 * lk;
+        if (k < plane_rows) {
+          const float p_scale = f16_scale_for(plane_bound);
+          float m1 = -1.f;
+          asm volatile("" : "+v"(m1));
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int col = c0 + 16 * q + li;
+            u32x4 hi, lo;
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+              for (int r = 0; r < 4; r += 2) {
+                const bool in_ = col < Lo && k + 4 * t + r < rows;      // (rows is a multiple of 8 wherever planes are asked for)
+                const float v0 = (in_ ? (float)acc[t][q][r] : 0.f) * p_scale;
+                const float v1 = (in_ ? (float)acc[t][q][r + 1] : 0.f) * p_scale;
+                const fp16x2_t h = cvt_pk_rn(v0, v1);
+                fp16x2_t l;
+                l[0] = (__fp16)__builtin_fmaf((float)h[0], m1, v0);
+                l[1] = (__fp16)__builtin_fmaf((float)h[1], m1, v1);
+                hi[2 * t + (r >> 1)] = __builtin_bit_cast(unsigned, h);
+                lo[2 * t + (r >> 1)] = __builtin_bit_cast(unsigned, l);
+              }
+            char* base = reinterpret_cast<char*>(planes) + axb_plane_offset(by, plane_rows, k, 16 * q + li, 0);
+            *reinterpret_cast<u32x4*>(base) = hi;
+            *reinterpret_cast<u32x4*>(base + AXB_PLANE_BYTES) = lo;
+          }
+        }
+      }
     }
   };
   f32x4 a0[2][4], a1[2][4];
@@ -1746,7 +1829,11 @@ __global__ __launch_bounds__(256) void panel_matmul_kernel(const float* __restri
       }
     }
   }
-  if (amax_out) amax_commit(amx, amax_out);
+  if constexpr (PLANES) {
+    if (amax_out && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *amax_out = __float_as_uint(plane_bound);
+  } else if (amax_out) {
+    amax_commit(amx, amax_out);
+  }
 }
 
 // per-column max/min over rows [0, rows): partial per block, then a second tiny pass.

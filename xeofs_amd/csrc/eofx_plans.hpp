@@ -46,6 +46,26 @@ constexpr int EOFX_LAG_GROUP_COLS = 1024;
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
+#if defined(__HIPCC__)
+#define EOFX_HOST_DEVICE __host__ __device__
+#else
+#define EOFX_HOST_DEVICE
+#endif
+// ---- the fp16 planes of an X Y pass's panel (eofx_axb_dma.hpp) -----------------------------------------------------------
+// A tall panel [K_all x L] (K_all a multiple of AXB_KG) as two fp16 planes (hi, lo) in the order axb_f16_dma_kernel's LDS buffer
+// holds them: [column block of 64][feature pair of 64 features][plane][k-group of 8 features][column slot][8 halves], the slot
+// of column c being c ^ ((c >> 3) & 7).  One pair is AXB_PAIR_BYTES; a (k-group, column) of one plane is one 16-byte unit.
+constexpr int AXB_PLANE_BYTES = 8 * 64 * 16;              // one plane of a feature pair: 8 k-groups x 64 slots x 16 bytes
+constexpr int AXB_PAIR_BYTES = 2 * AXB_PLANE_BYTES;       // one feature pair (64 features) x 64 columns, two fp16 planes
+// byte offset of the half that holds feature k of column c (0 .. 63) of column block cb in plane 0 (hi) or 1 (lo)
+EOFX_HOST_DEVICE inline int64_t axb_plane_offset(int64_t cb, int64_t K_all, int64_t k, int c, int plane) {
+  const int64_t pair = k >> 6;
+  const int g = (int)(k >> 3) & 7, t = (int)k & 7;
+  const int slot = c ^ ((c >> 3) & 7);
+  return (cb * (K_all / AXB_KG) + pair) * AXB_PAIR_BYTES + (int64_t)plane * AXB_PLANE_BYTES + (g * 64 + slot) * 16 + t * 2;
+}
+inline size_t axb_planes_bytes(int64_t K_all, int L) { return (size_t)((L + 63) / 64) * (size_t)(K_all / AXB_KG) * AXB_PAIR_BYTES; }
+
 // ---- the two streaming products ------------------------------------------------------------------------------------------
 struct AtbPlan {
   int S;
@@ -66,6 +86,10 @@ inline AtbPlan atb_plan(int64_t M, int64_t K, int L, bool wide = false) {
   const int bz = wide ? (L + 127) / 128 : (L + 63) / 64;
   const double resident = wide ? 256.0 : 512.0;
   AtbPlan best{1, K};
+  // tuning / test hook: EOFX_ATB_SPLITS=1 keeps small products in ONE split, where the kernels' own epilogues finish the tile
+  // (tests/test_gpu_plane_producers.py runs the plane epilogue of atb_f16_kernel at small shapes that way)
+  if (const char* ev = std::getenv("EOFX_ATB_SPLITS"))
+    if (atoi(ev) == 1) return best;
   double best_t = 1e30;
   for (int S = 1; S <= 128; ++S) {
     const int64_t kps = round_up((K + S - 1) / S, ATB_KG);

@@ -188,8 +188,8 @@ struct SpinWait {
 // than expected, at least a few (a round that accepts too few is followed by another)
 inline int64_t candidates(int64_t need) { return (int64_t)((double)need / 0.7853981633974483 * 1.01) + 64; }
 
-// out[rows x cols] (host), row-major
-inline void gaussian_f32(uint32_t seed, int64_t rows, int64_t cols, float* out) {
+// out[rows x cols] (host), row-major: one draw of the stream (no memo)
+inline void gaussian_f32_draw(uint32_t seed, int64_t rows, int64_t cols, float* out) {
   const int64_t total = rows * cols;
   if (total == 0) return;
   const int64_t npairs = (total + 1) / 2;
@@ -312,6 +312,52 @@ inline void gaussian_f32(uint32_t seed, int64_t rows, int64_t cols, float* out) 
     const int64_t o = std::min<int64_t>(total, obase + off[(size_t)nchunks]);
     done_pairs = (o + 1) / 2;
     if (o >= total) break;
+  }
+}
+
+// The matrix depends on (seed, rows, cols) and nothing else, and a caller that fixes random_state and fits again and again (the
+// Bootstrapper, fits over a moving window) asks for the same one every time: the last matrix drawn is kept, ONE entry for the
+// process, and a hit is a copy (2.4 MB for the 10000 x 60 sketch against 0.58 ms of drawing).  Matrices above the cap are never kept.
+constexpr size_t SKETCH_MEMO_MAX_BYTES = (size_t)64 << 20;
+struct SketchMemo {
+  std::mutex mu;
+  bool valid = false;
+  uint32_t seed = 0;
+  int64_t rows = 0, cols = 0;
+  std::vector<float> data;
+};
+inline SketchMemo& sketch_memo() {
+  static SketchMemo* memo = new SketchMemo();     // leaked on purpose, like the pool: callers may outlive static destruction
+  return *memo;
+}
+inline void sketch_memo_drop() {
+  SketchMemo& mm = sketch_memo();
+  std::lock_guard<std::mutex> lk(mm.mu);
+  mm.valid = false;
+  std::vector<float>().swap(mm.data);
+}
+// out[rows x cols] (host), row-major; safe under concurrent callers (a hit copies under the memo's lock, a miss draws outside it)
+inline void gaussian_f32(uint32_t seed, int64_t rows, int64_t cols, float* out) {
+  if (rows <= 0 || cols <= 0) return;
+  const size_t total = (size_t)rows * (size_t)cols;
+  const bool keep = total <= SKETCH_MEMO_MAX_BYTES / sizeof(float);
+  SketchMemo& mm = sketch_memo();
+  if (keep) {
+    std::lock_guard<std::mutex> lk(mm.mu);
+    if (mm.valid && mm.seed == seed && mm.rows == rows && mm.cols == cols) {
+      std::memcpy(out, mm.data.data(), sizeof(float) * total);
+      return;
+    }
+  }
+  gaussian_f32_draw(seed, rows, cols, out);
+  if (keep) {
+    std::lock_guard<std::mutex> lk(mm.mu);
+    mm.valid = false;
+    mm.data.assign(out, out + total);
+    mm.seed = seed;
+    mm.rows = rows;
+    mm.cols = cols;
+    mm.valid = true;
   }
 }
 

@@ -305,6 +305,12 @@ def sketch_matrix(rows: int, size: int, random_state=None) -> np.ndarray:
     return np.ascontiguousarray(rs.normal(size=(rows, size)).astype(np.float32))
 
 
+def sketch_cache_drop() -> None:
+    """Release the engine's one-entry cache of the last sketch matrix drawn from an integer seed (it only saves the redraw
+    when the same (seed, rows, size) is asked for again; the matrix returned is the same either way)."""
+    raise_for(_lib.load().eofx_sketch_cache_drop())
+
+
 class SketchFuture:
     """Draws the sketch matrix on a worker thread so the ~10 ms of legacy-RandomState sampling
     (600k normals at n=10000, l=60) overlap the preprocess kernels of the same fit (the ctypes
@@ -906,6 +912,36 @@ def panel_mul(ctx: Context, mat: ResidentMatrix, Yp, out=None, prec="f32"):
         out = torch.empty((mat.n_pad, L), dtype=torch.float32, device=Yp.device)
     raise_for(ctx.lib.eofx_panel_mul_f32(ctx.handle, mat.handle, ptr(Yp), ptr(out), L, _lib.PREC[prec]), ctx.handle)
     return out
+
+
+def plane_stats(ctx: Context):
+    """-> dict(produced_tmul, produced_cholqr, consumed, checked, min_slack, max_slack): tall panels the rSVD drivers wrote as the
+    fp16 planes of the in-place X Y pass (by the X^T Z kernel / by the Cholesky-QR), passes that took them as written, and -- with EOFX_AXB_CHECK_BOUND=1 -- passes whose panel was measured
+    against its bound, with the extremes of bound / maximum (include/eofx.h, eofx_ctx_plane_stats).  Restarts the counters."""
+    cnt, sl = (C.c_int64 * 4)(), (C.c_double * 2)()
+    raise_for(ctx.lib.eofx_ctx_plane_stats(ctx.handle, cnt, sl), ctx.handle)
+    return dict(produced_tmul=int(cnt[0]), produced_cholqr=int(cnt[1]), consumed=int(cnt[2]), checked=int(cnt[3]),
+                min_slack=float(sl[0]), max_slack=float(sl[1]))
+
+
+def axb_plane_bytes(mat: ResidentMatrix, L: int) -> int:
+    """bytes of the fp16 planes of a [p_pad x L] panel of `mat` (eofx_plans.hpp, axb_planes_bytes)"""
+    return ((L + 63) // 64) * ((mat.p + 63) // 64) * 16384
+
+
+def axb_planes_probe(ctx: Context, mat: ResidentMatrix, Zn, producer: int, bound: float = 0.0):
+    """The plane producers of the in-place X Y pass, laid open (include/eofx.h, eofx_axb_planes_probe_f32) ->
+    dict(planes_prod, planes_split (uint16 arrays), w_prod, w_split, w_reg, w_max, y (device tensors), bound)."""
+    torch = _torch()
+    L = Zn.shape[1]
+    nb = axb_plane_bytes(mat, L)
+    pp, ps = np.empty(nb // 2, np.uint16), np.empty(nb // 2, np.uint16)
+    w = [torch.empty((mat.n_pad, L), dtype=torch.float32, device=Zn.device) for _ in range(4)]
+    y = torch.empty((mat.p_pad, L), dtype=torch.float32, device=Zn.device)
+    b = C.c_float()
+    raise_for(ctx.lib.eofx_axb_planes_probe_f32(ctx.handle, mat.handle, ptr(Zn), L, int(producer), float(bound), ptr(pp), ptr(ps), nb,
+                                                ptr(w[0]), ptr(w[1]), ptr(w[2]), ptr(w[3]), ptr(y), C.byref(b)), ctx.handle)
+    return dict(planes_prod=pp, planes_split=ps, w_prod=w[0], w_split=w[1], w_reg=w[2], w_max=w[3], y=y, bound=float(b.value))
 
 
 def panel_gram(ctx: Context, P, out=None):
