@@ -4189,7 +4189,7 @@ extern "C" int eofx_hilbert_sumsq_f64(eofx_ctx* ctx, const eofx_mat* a, int padd
   }
   const cfloat* chat = nullptr;
   const float *hperm = nullptr, *u = nullptr;
-  CHK(get_hilbert_setup(ctx, n, padding ? 1 : 0, decay_factor, P, true, &chat, &hperm, &u));
+  CHK(get_hilbert_setup(ctx, n, padding ? 1 : 0, padding ? decay_factor : 0.0, P, true, &chat, &hperm, &u));   // (one cached setup for every unpadded call)
   const bool lean = a->raw && a->aff && !a->X;
   const bool from_rawT = lean && a->rawT && !a->Xt;
   const bool xt_transient = lean && !a->Xt && !from_rawT;
