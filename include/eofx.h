@@ -630,6 +630,27 @@ int eofx_simplex_rows_f32(eofx_ctx *ctx, const float *V, int64_t r, int64_t m, i
  * EOFX_ERR_SHAPE for k > 32 (SIMPLEX_KMAX).                                                                               */
 int eofx_simplex_pg_f32(eofx_ctx *ctx, const float *A, int64_t lda, const float *Q, int64_t ldq, const double *M, float inv_L,
                         int iters, int64_t n, int k, float *out, int64_t ldo);
+/* ---- the Lloyd solver of weather-regime clustering (Michelangeli, Vautard & Legras 1995; xeofs_amd/single/kmeans.py,
+ * csrc/eofx_kmeans.hpp) ----
+ * kmeans_lloyd: Z [n x q] a float32 device panel (row stride ldz >= q), C0 [R x k x q] float32 device start centroids of R
+ * independent restarts.  Every restart runs, in one launch and on one workgroup,
+ *   assign:  d[i, c] = sum_j (Z[i, j] - c[c, j])^2   (a float32 fmaf chain from 0, j ascending: the direct form)
+ *            label[i] = the c of the smallest d[i, c], the lowest index among equals; mind2[i] = that d[i, c]
+ *   stop     when no label differs from the assignment before (converged = 1; never at the first assignment of a launch) or
+ *            when iters == max_iter (converged = 0)
+ *   update:  counts[c] = the rows labelled c; c[c, j] = (float)(sum_{i: label[i] = c} (double)Z[i, j] / counts[c]), the sum in
+ *            float64 in an order fixed by (n, q, k); a cluster without rows keeps its centroid;  ++iters
+ * so that labels [R x n] int32, counts [R x k] int32, mind2 [R x n] float32 (or NULL) and inertia [R] float64 (the float64 sum
+ * of mind2 in a fixed order) always belong to the returned C [R x k x q]: the last thing a launch does is an assignment.
+ * iters [R] and converged [R] are int32.  max_iter = 0 is the assignment alone against C0.  One launch with max_iter = T
+ * returns the C, labels, counts, mind2 and inertia of T chained launches with max_iter = 1, bit for bit.  A row of Z that holds
+ * a NaN or an infinity gets label -1 and mind2 = NaN and takes part in nothing.  No atomics: two runs are equal bit for bit.
+ * C may alias C0.  All buffers are device buffers; a non-finite C0 is the caller's to refuse.  EOFX_ERR_ARG for n, q, k or
+ * R < 1, max_iter < 0, k > n, ldz < q, a null or host buffer; EOFX_ERR_SHAPE for n > 262144, q > 32, k > 32, R > 4096 or
+ * max_iter > 1000 (KMEANS_NMAX, KMEANS_QMAX, KMEANS_KMAX, KMEANS_RMAX, KMEANS_ITER_MAX).                                    */
+int eofx_kmeans_lloyd_f32(eofx_ctx *ctx, const float *Z, int64_t n, int64_t q, int64_t ldz, const float *C0, int64_t k, int64_t R,
+                          int64_t max_iter, int32_t *labels, float *C, int32_t *counts, double *inertia, int32_t *iters,
+                          int32_t *converged, float *mind2);
 /* ---- the three operators of spectral EOF analysis (Towne, Schmidt & Colonius 2018; Schmidt et al. 2019;
  * xeofs_amd/single/spectral_eof.py, csrc/eofx_spectral.hpp).  Generic linear algebra: none of them knows about Fourier. ----
  * blockxform: T [p x n] a SERIES-MAJOR float32 device panel (row stride ld >= n), B [ncoef x n_fft] a float32 device matrix

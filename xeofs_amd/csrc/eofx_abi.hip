@@ -18,6 +18,7 @@
 #include "eofx_colquad.hpp"
 #include "eofx_pairmin.hpp"
 #include "eofx_simplex.hpp"
+#include "eofx_kmeans.hpp"
 #include "eofx_spectral.hpp"
 #include "eofx_pcmul.hpp"
 #include "eofx_viewcov.hpp"
@@ -6082,6 +6083,48 @@ extern "C" int eofx_simplex_pg_f32(eofx_ctx* ctx, const float* A, int64_t lda, c
   }
   KCHK();
   if (host_m) HIPCHK(hipStreamSynchronize(ctx->stream));       // (stage_small; a device M returns without one)
+  return EOFX_OK;
+}
+
+// ---- the Lloyd solver of weather-regime clustering (csrc/eofx_kmeans.hpp) ------------------------------------------------
+template <int QP>
+static int launch_kmeans(eofx_ctx* ctx, const KmeansPlan& pl, const float* Z, int64_t n, int q, int64_t ldz, const float* C0, int k,
+                         int max_iter, int32_t* labels, float* C, int32_t* counts, double* inertia, int32_t* iters, int32_t* converged,
+                         float* mind2) {
+  HIPCHK(hipFuncSetAttribute((const void*)kmeans_lloyd_kernel<QP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+  hipLaunchKernelGGL((kmeans_lloyd_kernel<QP>), dim3((unsigned)pl.grid), dim3(pl.threads), pl.lds, ctx->stream, Z, n, q, ldz, C0, k, max_iter,
+                     pl, labels, C, counts, inertia, iters, converged, mind2);
+  return EOFX_OK;
+}
+
+extern "C" int eofx_kmeans_lloyd_f32(eofx_ctx* ctx, const float* Z, int64_t n, int64_t q, int64_t ldz, const float* C0, int64_t k, int64_t R,
+                                     int64_t max_iter, int32_t* labels, float* C, int32_t* counts, double* inertia, int32_t* iters,
+                                     int32_t* converged, float* mind2) {
+  if (!ctx) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (n < 1 || q < 1 || k < 1 || R < 1 || max_iter < 0)
+    return set_err(ctx, EOFX_ERR_ARG, "n, q, k and R must be >= 1 and max_iter >= 0 (n = %lld, q = %lld, k = %lld, R = %lld, max_iter = %lld)",
+                   (long long)n, (long long)q, (long long)k, (long long)R, (long long)max_iter);
+  if (n > KMEANS_NMAX || q > KMEANS_QMAX || k > KMEANS_KMAX || R > KMEANS_RMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the Lloyd solver takes n <= %d, q <= %d, k <= %d and R <= %d, got n = %lld, q = %lld, k = %lld, R = %lld",
+                   KMEANS_NMAX, KMEANS_QMAX, KMEANS_KMAX, KMEANS_RMAX, (long long)n, (long long)q, (long long)k, (long long)R);
+  if (max_iter > KMEANS_ITER_MAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "one launch runs at most %d iterations, got max_iter = %lld (chain the launches)", KMEANS_ITER_MAX,
+                   (long long)max_iter);
+  if (k > n) return set_err(ctx, EOFX_ERR_ARG, "more clusters than rows: k = %lld, n = %lld", (long long)k, (long long)n);
+  if (ldz < q) return set_err(ctx, EOFX_ERR_ARG, "the row stride of Z is below q = %lld (ldz = %lld)", (long long)q, (long long)ldz);
+  if (!Z || !C0 || !labels || !C || !counts || !inertia || !iters || !converged) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (!is_device_ptr(Z) || !is_device_ptr(C0) || !is_device_ptr(labels) || !is_device_ptr(C) || !is_device_ptr(counts) ||
+      !is_device_ptr(inertia) || !is_device_ptr(iters) || !is_device_ptr(converged) || (mind2 && !is_device_ptr(mind2)))
+    return set_err(ctx, EOFX_ERR_ARG, "Z, C0 and the outputs must be device buffers");
+  ENTER(ctx);
+  const KmeansPlan pl = kmeans_plan(n, (int)q, (int)k, R);
+  switch (pl.qp) {
+    case 4: CHK(launch_kmeans<4>(ctx, pl, Z, n, (int)q, ldz, C0, (int)k, (int)max_iter, labels, C, counts, inertia, iters, converged, mind2)); break;
+    case 8: CHK(launch_kmeans<8>(ctx, pl, Z, n, (int)q, ldz, C0, (int)k, (int)max_iter, labels, C, counts, inertia, iters, converged, mind2)); break;
+    case 16: CHK(launch_kmeans<16>(ctx, pl, Z, n, (int)q, ldz, C0, (int)k, (int)max_iter, labels, C, counts, inertia, iters, converged, mind2)); break;
+    default: CHK(launch_kmeans<32>(ctx, pl, Z, n, (int)q, ldz, C0, (int)k, (int)max_iter, labels, C, counts, inertia, iters, converged, mind2)); break;
+  }
+  KCHK();
   return EOFX_OK;
 }
 

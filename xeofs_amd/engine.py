@@ -1694,6 +1694,63 @@ def simplex_pg(ctx: Context, A, Q, M, inv_L: float, iters: int, out=None):
 
 
 # --------------------------------------------------------------------------- #
+# the Lloyd solver of weather-regime clustering (eofx_kmeans_lloyd_f32, csrc/eofx_kmeans.hpp)                    #
+# --------------------------------------------------------------------------- #
+KMEANS_KMAX = 32            # clusters
+KMEANS_QMAX = 32            # columns of the score panel
+KMEANS_NMAX = 262144        # rows
+KMEANS_RMAX = 4096          # restarts of one launch
+KMEANS_ITER_MAX = 1000      # updates of one launch
+_KMEANS_OUT = (("labels", "int32"), ("centroids", "float32"), ("counts", "int32"), ("inertia", "float64"), ("iters", "int32"),
+               ("converged", "int32"), ("mind2", "float32"))
+
+
+def kmeans_lloyd(ctx: Context, Z, C0, max_iter: int, out=None, want_mind2: bool = False) -> dict:
+    """Lloyd's k-means iteration of R independent restarts on the float32 panel Z [n x q] -- a host array or a device tensor whose
+    row stride may exceed q -- from the start centroids C0 [R x k x q] (float32, host or device; finite), all restarts and
+    all iterations in one launch: assign (float32 fmaf chain of (z - c)^2, the lowest index among equals), stop when no label
+    changed (converged = 1) or after `max_iter` <= KMEANS_ITER_MAX updates, otherwise update (float64 sums in a fixed order,
+    an empty cluster keeps its centroid).  max_iter = 0 is the assignment alone.  -> a dict of device tensors: labels [R x n]
+    int32 (-1 for a row with a NaN or an infinity), centroids [R x k x q] float32, counts [R x k] int32, inertia [R] float64,
+    iters [R] int32, converged [R] int32 and, with `want_mind2`, mind2 [R x n] float32 -- all of them belonging to the
+    returned centroids.  `out`: a dict holding any of these as contiguous device tensors to write (giving mind2 asks for it).
+    Two calls are equal bit for bit; T chained calls with max_iter = 1 equal one call with max_iter = T (include/eofx.h)."""
+    torch = _torch()
+    Z = device_panel(ctx, Z, "Z", (torch.float32,))
+    n, q = Z.shape
+    if not hasattr(C0, "data_ptr"):
+        C0 = torch.from_numpy(np.ascontiguousarray(C0, dtype=np.float32))
+    if C0.dim() != 3 or C0.shape[2] != q:
+        raise ValueError(f"C0 must be [R x k x q] with q = {q} columns, got shape {tuple(C0.shape)}")
+    C0 = C0.to(device=Z.device, dtype=torch.float32).contiguous()
+    R, k = int(C0.shape[0]), int(C0.shape[1])
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)):
+        raise ValueError(f"max_iter must be an integer, got {max_iter!r}")
+    if C0.numel() and not bool(torch.isfinite(C0).all()):
+        raise ValueError("C0 holds a NaN or an infinity")
+    shapes = dict(labels=(R, n), centroids=(R, k, q), counts=(R, k), inertia=(R,), iters=(R,), converged=(R,), mind2=(R, n))
+    out = dict(out or {})
+    if set(out) - set(shapes):
+        raise ValueError(f"out holds unknown entries {sorted(set(out) - set(shapes))}")
+    res = {}
+    for name, dt in _KMEANS_OUT:
+        dtype = getattr(torch, dt)
+        t = out.get(name)
+        if t is None:
+            if name == "mind2" and not want_mind2:
+                continue
+            t = torch.empty(shapes[name], dtype=dtype, device=Z.device)
+        elif (not hasattr(t, "data_ptr") or tuple(t.shape) != shapes[name] or t.dtype != dtype or not t.is_contiguous()
+              or t.device != Z.device):
+            raise ValueError(f"out[{name!r}] must be a contiguous {dt} device tensor of shape {shapes[name]}")
+        res[name] = t
+    raise_for(ctx.lib.eofx_kmeans_lloyd_f32(ctx.handle, ptr(Z), n, q, Z.stride(0) if n else q, ptr(C0), k, R, int(max_iter),
+                                            ptr(res["labels"]), ptr(res["centroids"]), ptr(res["counts"]), ptr(res["inertia"]),
+                                            ptr(res["iters"]), ptr(res["converged"]), ptr(res.get("mind2"))), ctx.handle)
+    return res
+
+
+# --------------------------------------------------------------------------- #
 # the operators of spectral EOF analysis (eofx_blockxform_f32, eofx_mat_blockxform_f32, eofx_rowgram_f32, eofx_slabmul_f32, csrc/eofx_spectral.hpp) #
 # --------------------------------------------------------------------------- #
 BLOCKXFORM_NFFT_MAX = 16384       # samples per block
