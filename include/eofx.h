@@ -651,6 +651,34 @@ int eofx_simplex_pg_f32(eofx_ctx *ctx, const float *A, int64_t lda, const float 
 int eofx_kmeans_lloyd_f32(eofx_ctx *ctx, const float *Z, int64_t n, int64_t q, int64_t ldz, const float *C0, int64_t k, int64_t R,
                           int64_t max_iter, int32_t *labels, float *C, int32_t *counts, double *inertia, int32_t *iters,
                           int32_t *converged, float *mind2);
+/* ---- the FastICA solver of independent component analysis (Hyvarinen & Oja 2000; xeofs_amd/single/ica.py,
+ * csrc/eofx_ica.hpp) ----
+ * fastica: Z [n x q] a WHITE float32 device panel (row stride ldz >= q; not checked), W [R x q x q] float64 device, in/out: row j
+ * of restart r is the unmixing vector of source j, orthogonal on entry.  status [R] int32 in/out (0 running, 1 converged,
+ * 2 degenerate), iters [R] int32 in/out.  A call advances every restart with status 0 by at most max_iter iterations of
+ *   s_j = the float32 fmaf chain sum_i (float)W[j, i] z_i from 0, i ascending;  g, g', G of the contrast in float32
+ *         (fun 0 logcosh: tanh(alpha s), alpha (1 - g^2), log cosh(alpha s) / alpha;  1 exp: s e, (1 - s^2) e, -e with
+ *         e = exp(-s^2 / 2);  2 cube: s^3, 3 s^2, s^4 / 4)
+ *   W1 = sum_rows g z^T / nused - diag(sum_rows g' / nused) W   (float64 sums in an order fixed by (n, q); a row of Z with a
+ *         NaN or an infinity takes part in nothing, nused counts the others)
+ *   W+ = (W1 W1^T)^-1/2 W1 in float64;  nused = 0, a W1 that is not finite or not of full rank to working accuracy
+ *         (sigma_min^2 <= q 2^-52 sigma_max^2): status = 2, W stays.  Otherwise lim = max_j | |sum_i W+[j, i] W[j, i]| - 1 |,
+ *         W = W+, ++iters, status = 1 when lim < tol.
+ * W1 [R x q x q], gmean [R x q] (the mean of G(s_j)), lim [R] (all float64) and nused [1] (int64) may be NULL; they come from
+ * the last moment pass a restart ran.  A restart whose status is not 0 on entry is not touched.  max_iter = 0 is the moment
+ * pass alone for every restart whatever its status: W1, gmean and nused are written, W, status, iters and lim are not.
+ * Two launches per iteration, enqueued without a host synchronisation; no atomics: two calls are equal bit for bit, T calls
+ * with max_iter = 1 equal one call with max_iter = T, and a restart's result does not depend on the others.
+ * The partial sums take R B (q^2 + 2 q + 1) float64 words of the context's arena, B = ceil(n / (256 max(1, ceil(n / 131072))))
+ * <= 512 row blocks: 2.2 MB at (n, q, R) = (10000, 32, 50), 357 MB at (10000, 32, 1024), 4.6 GB at the limits; the arena grows
+ * to it and keeps it until the context is destroyed (EOFX_ERR_NOMEM where the device cannot give it).  A decorrelation whose
+ * Jacobi iteration still rotates in its 60th sweep is degenerate too (status 2).
+ * EOFX_ERR_ARG for n, q or R < 1, max_iter < 0, fun outside 0..2, alpha outside [1, 2], tol outside (0, 1], ldz < q, a null or
+ * host buffer; EOFX_ERR_SHAPE for n > 4194304, q > 32, R > 1024 or max_iter > 64 (ICA_NMAX, ICA_QMAX, ICA_RMAX,
+ * ICA_ITER_MAX).                                                                                                          */
+int eofx_fastica_f32(eofx_ctx *ctx, const float *Z, int64_t n, int64_t q, int64_t ldz, double *W, int64_t R, int fun, double alpha,
+                     double tol, int64_t max_iter, int32_t *status, int32_t *iters, double *W1, double *gmean, double *lim,
+                     int64_t *nused);
 /* ---- the three operators of spectral EOF analysis (Towne, Schmidt & Colonius 2018; Schmidt et al. 2019;
  * xeofs_amd/single/spectral_eof.py, csrc/eofx_spectral.hpp).  Generic linear algebra: none of them knows about Fourier. ----
  * blockxform: T [p x n] a SERIES-MAJOR float32 device panel (row stride ld >= n), B [ncoef x n_fft] a float32 device matrix

@@ -131,6 +131,7 @@ SIGNATURES = {
     "eofx_simplex_rows_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, C.c_float, _vp, _i64]),
     "eofx_simplex_pg_f32": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, C.c_float, _int, _i64, _int, _vp, _i64]),
     "eofx_kmeans_lloyd_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "eofx_fastica_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _int, C.c_double, C.c_double, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eofx_blockxform_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "eofx_mat_blockxform_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "eofx_rowgram_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _vp]),

@@ -19,6 +19,7 @@
 #include "eofx_pairmin.hpp"
 #include "eofx_simplex.hpp"
 #include "eofx_kmeans.hpp"
+#include "eofx_ica.hpp"
 #include "eofx_spectral.hpp"
 #include "eofx_pcmul.hpp"
 #include "eofx_viewcov.hpp"
@@ -6123,6 +6124,69 @@ extern "C" int eofx_kmeans_lloyd_f32(eofx_ctx* ctx, const float* Z, int64_t n, i
     case 8: CHK(launch_kmeans<8>(ctx, pl, Z, n, (int)q, ldz, C0, (int)k, (int)max_iter, labels, C, counts, inertia, iters, converged, mind2)); break;
     case 16: CHK(launch_kmeans<16>(ctx, pl, Z, n, (int)q, ldz, C0, (int)k, (int)max_iter, labels, C, counts, inertia, iters, converged, mind2)); break;
     default: CHK(launch_kmeans<32>(ctx, pl, Z, n, (int)q, ldz, C0, (int)k, (int)max_iter, labels, C, counts, inertia, iters, converged, mind2)); break;
+  }
+  KCHK();
+  return EOFX_OK;
+}
+
+// ---- the FastICA solver of independent component analysis (csrc/eofx_ica.hpp) --------------------------------------------
+template <int FUN, int QP>
+static int launch_ica_moments(eofx_ctx* ctx, const IcaPlan& pl, const float* Z, int64_t n, int q, int64_t ldz, const double* W,
+                              const int32_t* status, int64_t R, int force, float alpha, double* part, bool first) {
+  if (first)                                                      // (once per call: the attribute outlives the launch)
+    HIPCHK(hipFuncSetAttribute((const void*)ica_moments_kernel<FUN, QP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+  hipLaunchKernelGGL((ica_moments_kernel<FUN, QP>), dim3((unsigned)pl.blocks, (unsigned)R), dim3(ICA_WG), pl.lds, ctx->stream, Z, n, q, ldz,
+                     W, status, force, alpha, pl, part);
+  return EOFX_OK;
+}
+template <int FUN>
+static int launch_ica_moments_q(eofx_ctx* ctx, const IcaPlan& pl, const float* Z, int64_t n, int q, int64_t ldz, const double* W,
+                                const int32_t* status, int64_t R, int force, float alpha, double* part, bool first) {
+  switch (pl.qp) {
+    case 4: return launch_ica_moments<FUN, 4>(ctx, pl, Z, n, q, ldz, W, status, R, force, alpha, part, first);
+    case 8: return launch_ica_moments<FUN, 8>(ctx, pl, Z, n, q, ldz, W, status, R, force, alpha, part, first);
+    case 16: return launch_ica_moments<FUN, 16>(ctx, pl, Z, n, q, ldz, W, status, R, force, alpha, part, first);
+    default: return launch_ica_moments<FUN, 32>(ctx, pl, Z, n, q, ldz, W, status, R, force, alpha, part, first);
+  }
+}
+
+extern "C" int eofx_fastica_f32(eofx_ctx* ctx, const float* Z, int64_t n, int64_t q, int64_t ldz, double* W, int64_t R, int fun,
+                                double alpha, double tol, int64_t max_iter, int32_t* status, int32_t* iters, double* W1, double* gmean,
+                                double* lim, int64_t* nused) {
+  if (!ctx) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (n < 1 || q < 1 || R < 1 || max_iter < 0)
+    return set_err(ctx, EOFX_ERR_ARG, "n, q and R must be >= 1 and max_iter >= 0 (n = %lld, q = %lld, R = %lld, max_iter = %lld)",
+                   (long long)n, (long long)q, (long long)R, (long long)max_iter);
+  if (n > ICA_NMAX || q > ICA_QMAX || R > ICA_RMAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "the FastICA solver takes n <= %d, q <= %d and R <= %d, got n = %lld, q = %lld, R = %lld", ICA_NMAX,
+                   ICA_QMAX, ICA_RMAX, (long long)n, (long long)q, (long long)R);
+  if (max_iter > ICA_ITER_MAX)
+    return set_err(ctx, EOFX_ERR_SHAPE, "one call runs at most %d iterations, got max_iter = %lld (chain the calls)", ICA_ITER_MAX,
+                   (long long)max_iter);
+  if (fun < 0 || fun > 2) return set_err(ctx, EOFX_ERR_ARG, "fun must be 0 (logcosh), 1 (exp) or 2 (cube), got %d", fun);
+  if (!(alpha >= 1.0 && alpha <= 2.0)) return set_err(ctx, EOFX_ERR_ARG, "alpha must lie in [1, 2], got %g", alpha);
+  if (!(tol > 0.0) || !(tol <= 1.0)) return set_err(ctx, EOFX_ERR_ARG, "tol must lie in (0, 1], got %g", tol);
+  if (ldz < q) return set_err(ctx, EOFX_ERR_ARG, "the row stride of Z is below q = %lld (ldz = %lld)", (long long)q, (long long)ldz);
+  if (!Z || !W || !status || !iters) return set_err(ctx, EOFX_ERR_ARG, "bad argument");
+  if (!is_device_ptr(Z) || !is_device_ptr(W) || !is_device_ptr(status) || !is_device_ptr(iters) || (W1 && !is_device_ptr(W1)) ||
+      (gmean && !is_device_ptr(gmean)) || (lim && !is_device_ptr(lim)) || (nused && !is_device_ptr(nused)))
+    return set_err(ctx, EOFX_ERR_ARG, "Z, W, status, iters and the outputs must be device buffers");
+  ENTER(ctx);
+  const IcaPlan pl = ica_plan(n, (int)q);
+  const size_t words = ica_scratch(n, (int)q, R);
+  CHK(arena_reserve(ctx, words * sizeof(double)));
+  ArenaScope scope(ctx);
+  ARENA(double, part, words);
+  const int force = max_iter == 0;
+  const int64_t T = force ? 1 : max_iter;
+  for (int64_t t = 0; t < T; ++t) {
+    switch (fun) {
+      case 0: CHK(launch_ica_moments_q<0>(ctx, pl, Z, n, (int)q, ldz, W, status, R, force, (float)alpha, part, t == 0)); break;
+      case 1: CHK(launch_ica_moments_q<1>(ctx, pl, Z, n, (int)q, ldz, W, status, R, force, (float)alpha, part, t == 0)); break;
+      default: CHK(launch_ica_moments_q<2>(ctx, pl, Z, n, (int)q, ldz, W, status, R, force, (float)alpha, part, t == 0)); break;
+    }
+    hipLaunchKernelGGL(ica_update_kernel, dim3((unsigned)R), dim3(ICA_WG), 0, ctx->stream, part, pl.blocks, (int)q, tol, force ? 0 : 1, W,
+                       status, iters, W1, gmean, lim, (long long*)nused);
   }
   KCHK();
   return EOFX_OK;

@@ -1751,6 +1751,63 @@ def kmeans_lloyd(ctx: Context, Z, C0, max_iter: int, out=None, want_mind2: bool 
 
 
 # --------------------------------------------------------------------------- #
+# the FastICA solver of independent component analysis (eofx_fastica_f32, csrc/eofx_ica.hpp)                      #
+# --------------------------------------------------------------------------- #
+ICA_QMAX = 32               # sources
+ICA_NMAX = 4194304          # rows
+ICA_RMAX = 1024             # restarts of one call
+ICA_ITER_MAX = 64           # iterations of one call
+ICA_FUNS = ("logcosh", "exp", "cube")
+_ICA_OUT = (("W1", "float64"), ("gmean", "float64"), ("lim", "float64"), ("nused", "int64"))
+
+
+def fastica(ctx: Context, Z, W, status, iters, fun: str = "logcosh", alpha: float = 1.0, tol: float = 1e-4, max_iter: int = 1,
+            out=None, want=("W1", "gmean", "lim", "nused")) -> dict:
+    """The parallel FastICA iteration of R independent restarts on the WHITE float32 panel Z [n x q] -- a host array or a device
+    tensor whose row stride may exceed q.  W [R x q x q] float64, status [R] and iters [R] int32 are contiguous DEVICE tensors
+    and are updated in place: every restart with status 0 advances by at most `max_iter` <= ICA_ITER_MAX iterations (project in
+    float32, contrast `fun` in float32, float64 moments in a fixed order, symmetric decorrelation in float64), status 1 =
+    converged (scikit-learn's lim < tol), 2 = degenerate.  max_iter = 0 is the moment pass alone for every restart.  -> a dict
+    of the outputs named in `want` (or given in `out` as contiguous device tensors): W1 [R x q x q], gmean [R x q], lim [R]
+    float64 and nused [1] int64, from the last moment pass a restart ran; an output not asked for is not written.  The call
+    enqueues its launches and returns.  Two calls are equal bit for bit (include/eofx.h)."""
+    torch = _torch()
+    Z = device_panel(ctx, Z, "Z", (torch.float32,))
+    n, q = Z.shape
+    if fun not in ICA_FUNS:
+        raise ValueError(f"fun must be one of {ICA_FUNS}, got {fun!r}")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)):
+        raise ValueError(f"max_iter must be an integer, got {max_iter!r}")
+    if not hasattr(W, "data_ptr") or W.dim() != 3 or W.shape[1] != q or W.shape[2] != q or W.dtype != torch.float64 \
+            or not W.is_contiguous() or W.device != Z.device:
+        raise ValueError(f"W must be a contiguous float64 device tensor [R x q x q] with q = {q}")
+    R = int(W.shape[0])
+    for name, t in (("status", status), ("iters", iters)):
+        if not hasattr(t, "data_ptr") or tuple(t.shape) != (R,) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != Z.device:
+            raise ValueError(f"{name} must be a contiguous int32 device tensor of shape ({R},)")
+    shapes = dict(W1=(R, q, q), gmean=(R, q), lim=(R,), nused=(1,))
+    out = dict(out or {})
+    if set(out) - set(shapes) or set(want) - set(shapes):
+        raise ValueError(f"unknown outputs {sorted((set(out) | set(want)) - set(shapes))}")
+    res = {}
+    for name, dt in _ICA_OUT:
+        dtype = getattr(torch, dt)
+        t = out.get(name)
+        if t is None:
+            if name not in want:
+                continue
+            t = torch.zeros(shapes[name], dtype=dtype, device=Z.device)
+        elif (not hasattr(t, "data_ptr") or tuple(t.shape) != shapes[name] or t.dtype != dtype or not t.is_contiguous()
+              or t.device != Z.device):
+            raise ValueError(f"out[{name!r}] must be a contiguous {dt} device tensor of shape {shapes[name]}")
+        res[name] = t
+    raise_for(ctx.lib.eofx_fastica_f32(ctx.handle, ptr(Z), n, q, Z.stride(0) if n else q, ptr(W), R, ICA_FUNS.index(fun), float(alpha),
+                                       float(tol), int(max_iter), ptr(status), ptr(iters), ptr(res.get("W1")), ptr(res.get("gmean")),
+                                       ptr(res.get("lim")), ptr(res.get("nused"))), ctx.handle)
+    return res
+
+
+# --------------------------------------------------------------------------- #
 # the operators of spectral EOF analysis (eofx_blockxform_f32, eofx_mat_blockxform_f32, eofx_rowgram_f32, eofx_slabmul_f32, csrc/eofx_spectral.hpp) #
 # --------------------------------------------------------------------------- #
 BLOCKXFORM_NFFT_MAX = 16384       # samples per block

@@ -4,6 +4,7 @@ from .eeof import ExtendedEOF  # noqa: F401
 from .eof import EOF, ComplexEOF, HilbertEOF  # noqa: F401
 from .eot import EOT  # noqa: F401
 from .gwpca import GWPCA  # noqa: F401
+from .ica import ICA  # noqa: F401
 from .kmeans import KMeans  # noqa: F401
 from .lfca import LFCA  # noqa: F401
 from .opa import OPA  # noqa: F401
